@@ -17,8 +17,11 @@ region).  `--config` picks the BASELINE.json configuration; the default is #2 on
   #5  the config #4 graph, 10 M updates per step whose sources follow Zipf(1.2) (hot-vertex rebalance cascades)
 
 Launch for N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N
-Prints ONE JSON line on rank 0 (DESIGN.md section 6 defines the fields).  Unless --no-check, the state of the timed
-engines is compared slot by slot with the reference / oracle after the timed region (`parity_checked`).
+Prints ONE JSON line on rank 0 (DESIGN.md section 6 defines the fields).  A plain run sets up, warms up, times --steps
+steps and reports them (`value`, `ms_per_step`); --dump-outputs DIR also writes the state the last timed step left.
+Everything else is measured with --full only: unless --no-check, the state of the timed engines is compared slot by slot
+with the reference / oracle after the timed region (`parity_checked`); the CPU baseline, the profiled replay (`roofline`),
+the end-to-end run from host memory and the secondary legs (scan, rebalance, consumers, other configs) follow.
 """
 import argparse
 import glob
@@ -65,6 +68,34 @@ def csrc_sha256():
 def log(rank, *a):
     if rank == 0:
         print(f"[bench +{time.time() - T_BENCH0:5.1f}s]", *a, file=sys.stderr, flush=True)
+
+
+# rows of each dumped array (all ranks together): edges 2^20 x 3 and nodes 2^19 x 3 float64 values plus their row numbers
+# are 50 MB, under the 64 MB a dump may hold
+DUMP_ROWS = {"edges": 1 << 20, "nodes": 1 << 19}
+
+
+def write_outputs(out_dir, states, geometries, world=1, rank=0):
+    """--dump-outputs: what a caller of the timed path receives, the exported state of every partition on this rank
+    (edges[] and nodes[] triples, concatenated in partition order; geometry (N, logN, H) per partition) as float64, which
+    holds every uint32 exactly.  An array with more rows than its share of DUMP_ROWS is written as a fixed sample of rows
+    (seed 0, ascending) with the row numbers beside it in <name>_rows.npy.  Returns the file names written."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if world == 1 else f"_rank{rank}"
+    arrays = {"geometry": np.asarray(geometries, np.float64).reshape(-1, 3)}
+    for i, name in enumerate(("edges", "nodes")):
+        rows = np.concatenate([np.asarray(st[i], np.uint32).reshape(-1, 3) for st in states])
+        cap = DUMP_ROWS[name] // world
+        if len(rows) > cap:
+            pick = np.sort(np.random.default_rng(0).choice(len(rows), cap, replace=False))
+            arrays[name + "_rows"] = pick.astype(np.float64)
+            rows = rows[pick]
+        arrays[name] = rows.astype(np.float64)
+    written = []
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), a)
+        written.append(name + sfx + ".npy")
+    return written
 
 
 class Workload:
@@ -150,7 +181,14 @@ def main():
                          "preflight that runs small ragged blocks through BOTH carriers and compares the partitions bit for bit; if the "
                          "native carrier errs or disagrees, the run says so and continues on the torch carrier")
     ap.add_argument("--backend", default="nccl", help="process-group backend; 'gloo' only for functional tests of the N > 1 path on one GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: parity check, CPU baseline, profiled replay (roofline), end to end from host memory, "
+                         "secondary legs (the --no-* options switch single parts off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the last timed step left (edges[] / nodes[] / geometry) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -361,8 +399,9 @@ def main():
             return
         torch_exchange_apply(pp, ops_dev, n_global)
 
-    def run_workload(wl_, label, steps, warmup, want_profile, after_core=None):
-        """core load (untimed), snapshot, warm-up, timed steps [, profiled replay]; returns a result dict.
+    def run_workload(wl_, label, steps, warmup, want_profile, after_core=None, dump_dir=None):
+        """core load (untimed), snapshot, warm-up, timed steps [, dump of the last step's state] [, end to end, profiled
+        replay (--full)]; returns a result dict.
         after_core(pp, es) -> es: hook between the core load and the snapshot (the repartitioning leg)"""
         t0 = time.time()
         core_blk = wl_.core(rank * my_core, my_core)
@@ -426,7 +465,10 @@ def main():
         res = {"value": total_updates / elapsed, "ms_per_step": elapsed / steps * 1e3, "engine": dstat,
                "N_slots": [int(x) for x in s1["N"]], "logN": int(s1["logN"][0]), "last_k": (warmup + steps - 1) % nb,
                "core_blk": core_blk, "upd": upd, "es": es, "pp": pp, "step": step}
-        if single and N == 1:
+        if dump_dir:
+            files = write_outputs(dump_dir, [e.state() for e in es], [e.geometry() for e in es], N, rank)
+            log(rank, f"{label}: state of the last timed step written to {dump_dir}: {', '.join(files)}")
+        if args.full and single and N == 1:
             # end to end (the reference's own clock covers its whole apply phase: thread_pool.cpp:79,110): the
             # op array starts in HOST memory — ppcsr_apply_batch uploads it (12 B per update over PCIe) and applies it; wall clock
             # around restore + upload + apply, same steps as the device-only figure above.  Never `value`.
@@ -553,9 +595,10 @@ def main():
         return ok, ("reference (oracle/_ref)" if use_ref else "oracle"), max(secs), sum(len(s) for s in seqs)
 
     # ================================================ headline ====================================================
-    res = run_workload(wl, f"config#{wl.cfg}", args.steps, args.warmup, not args.no_profile)
+    res = run_workload(wl, f"config#{wl.cfg}", args.steps, args.warmup, args.full and not args.no_profile,
+                       dump_dir=args.dump_outputs)
     extra = {}
-    if not args.no_check:
+    if args.full and not args.no_check:
         t0 = time.time()
         ok, against, osecs, nops = parity_check(wl, res)
         log(rank, f"parity vs {against}: {'bit-exact' if ok else 'MISMATCH'} ({nops} updates replayed per rank, {osecs:.1f}s, total {time.time() - t0:.1f}s)")
@@ -567,7 +610,7 @@ def main():
 
     # ---- CPU baseline beside it (rank 0, N == 1): the reference's own CLI binary with its thread pools on this box's cores
     cpu = None
-    if rank == 0 and N == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and N == 1 and not args.no_cpu_baseline:
         from oracle_lib import Oracle, RefPCSR, have_ref
         try:
             cores = len(os.sched_getaffinity(0))
@@ -675,7 +718,8 @@ def main():
 
     # ================================================ secondary legs ===============================================
     es = res["es"]
-    if rank == 0 and not args.no_secondary:
+    secondary = args.full and not args.no_secondary
+    if rank == 0 and secondary:
         try:
             eng = es[0]
             ms, tot = eng.bench_scan_all()
@@ -779,7 +823,7 @@ def main():
         except Exception as e:
             extra[key + "_error"] = str(e)
 
-    if not args.no_secondary and cfg == 4 and not args.zipf:
+    if secondary and cfg == 4 and not args.zipf:
         # the same graph with raw labels (the faithful input: partition 0 holds 44 % of the edges), and config #5's stream
         if permute:
             side_leg("raw_labels", Workload(streams, 4, n_global, scale, core_edges, batch, False), max(1, min(args.steps, 2)), 1, False)
@@ -805,7 +849,7 @@ def main():
                 side_leg("raw_labels_repartitioned", Workload(streams, 4, n_global, scale, core_edges, batch, False), max(1, min(args.steps, 2)), 1,
                          False, after_core=rebalance_parts, more=info)
         side_leg("config5_zipf", Workload(streams, 5, n_global, scale, core_edges, batch, permute), 1, 1, True)
-    if not args.no_secondary and cfg == 2 and N == 1 and not args.zipf:
+    if secondary and cfg == 2 and N == 1 and not args.zipf:
         # config #3 and the config #5 stream shape on this one-GPU graph
         side_leg("config3_mixed", Workload(streams, 3, n_global, scale, core_edges, batch, permute), max(1, min(args.steps, 3)), 1, True)
         side_leg("config5_shape_zipf", Workload(streams, 5, n_global, scale, core_edges, batch, permute), max(1, min(args.steps, 2)), 1, True)

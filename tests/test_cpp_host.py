@@ -1,7 +1,8 @@
 """GPU: the C++ host side (header-compatible PCSR / PPPCSR shims, pool shims, CLI) above the C ABI.
 * tests/cpp/test_datastructure.cpp = the reference's gtest suite restated, run as a binary;
-* ppcsr_cli against the reference's own CLI binary (oracle/_ref/ref_cli, built from the reference sources where
-  they lie) on the same text edge lists: same stdout protocol and the same final array geometry."""
+* ppcsr_cli against the reference's own CLI binary on the same text edge lists: same stdout protocol and the same final
+  array geometry (the reference's lines are recorded in tests/golden/ref_cli_protocol.json)."""
+import json
 import os
 import re
 import subprocess
@@ -17,6 +18,7 @@ CLI = os.path.join(ROOT, "parallel-packed-csr_amd", "host", "ppcsr_cli")
 CPP_TEST = os.path.join(ROOT, "tests", "cpp", "test_datastructure")
 CPP_PAR_TEST = os.path.join(ROOT, "tests", "cpp", "test_parallel")
 REF_CLI = os.path.join(ROOT, "oracle", "_ref", "ref_cli")
+REF_CLI_RECORD = os.path.join(ROOT, "tests", "golden", "ref_cli_protocol.json")
 
 
 def _ensure_built():
@@ -115,30 +117,37 @@ def _filtered(out):
     return keep, elapsed, (edges[-1] if edges else None)
 
 
-@pytest.mark.parametrize("flags", [["-ppcsr", "-insert"], ["-ppcsr", "-delete"], ["-pppcsr", "-insert", "-partitions_per_domain=1"]])
-def test_cli_protocol_matches_reference(tmp_path, flags):
-    _ensure_built()
+CLI_CASES = [["-ppcsr", "-insert"], ["-ppcsr", "-delete"], ["-pppcsr", "-insert", "-partitions_per_domain=1"]]
+
+
+def cli_protocol(binary, workdir, flags):
+    """run `binary` (ppcsr_cli or the reference's CLI) on the protocol case of `flags`, its edge files written into workdir and
+    named relative to it; returns (kept lines, number of elapsed-time lines, last resize line)"""
     st = load_streams()
     s, d = st.rmat_edges(12, 40000, seed=1)
     core = st.adds(s, d)
     fresh = st.random_stream(4096, 6000, seed=2)
     upd = st.mixed_existing_stream(core, fresh, seed=3) if "-delete" in flags else fresh
-    cf, uf = str(tmp_path / "core.txt"), str(tmp_path / "upd.txt")
-    _write_edges(cf, core, False)
-    _write_edges(uf, upd, "-delete" not in flags and False)
-    args = ["-threads=1", "-size=8000"] + flags + [f"-core_graph={cf}", f"-update_file={uf}"]
-    mine = subprocess.run([CLI] + args, capture_output=True, text=True, timeout=300)
-    assert mine.returncode == 0, mine.stdout + mine.stderr
-    keep, elapsed, last_edges = _filtered(mine.stdout)
+    _write_edges(os.path.join(workdir, "core.txt"), core, False)
+    _write_edges(os.path.join(workdir, "upd.txt"), upd, False)
+    args = ["-threads=1", "-size=8000"] + flags + ["-core_graph=core.txt", "-update_file=upd.txt"]
+    r = subprocess.run([binary] + args, capture_output=True, text=True, timeout=300, cwd=workdir)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return _filtered(r.stdout)
+
+
+@pytest.mark.parametrize("flags", CLI_CASES)
+def test_cli_protocol_matches_reference(tmp_path, flags):
+    """the same lines as the reference's CLI on the same files: its output is recorded in tests/golden/ref_cli_protocol.json
+    (tests/golden/make_ref_digests.py)"""
+    _ensure_built()
+    keep, elapsed, last_edges = cli_protocol(CLI, str(tmp_path), flags)
     assert elapsed == 2  # phase 1 (core load) and phase 2 (updates): the bench scripts scrape the second
     assert any(l.startswith("Core graph size: 40000") for l in keep)
-    if os.path.exists(REF_CLI):
-        ref = subprocess.run([REF_CLI] + args, capture_output=True, text=True, timeout=300)
-        assert ref.returncode == 0
-        rkeep, relapsed, rlast = _filtered(ref.stdout)
-        assert rkeep == keep and relapsed == elapsed
-        if "-ppcsr" in flags:  # one PCSR: the last resize line is the final geometry
-            assert rlast == last_edges, (rlast, last_edges)
+    ref = json.load(open(REF_CLI_RECORD))[" ".join(flags)]
+    assert ref["keep"] == keep and ref["elapsed"] == elapsed, (ref, keep, elapsed)
+    if "-ppcsr" in flags:  # one PCSR: the last resize line is the final geometry
+        assert ref["last_edges"] == last_edges, (ref["last_edges"], last_edges)
 
 
 def test_cli_bulk_core_keeps_the_protocol(tmp_path):

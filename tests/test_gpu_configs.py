@@ -229,7 +229,7 @@ def test_bench_two_ranks_on_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--config", "4",
            "--vertices", "200000", "--scale", "18", "--core-edges", "2000000", "--batch", "200000", "--steps", "1", "--warmup", "1",
-           "--no-secondary", "--no-cpu-baseline", "--no-profile"]
+           "--full", "--no-secondary", "--no-cpu-baseline", "--no-profile"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -248,7 +248,7 @@ def test_bench_config4_legs_small():
     import sys
     from helpers import ROOT
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "4", "--vertices", "200000", "--scale", "18", "--core-edges", "2000000",
-           "--batch", "200000", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-profile"]
+           "--batch", "200000", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-profile"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -6,7 +6,7 @@ for rep in 1 2; do
   for var in "$@"; do
     opts=""
     if [ "$var" != "-" ]; then for kv in ${var//,/ }; do opts="$opts --opt $kv"; done; fi
-    python3 bench.py --no-cpu-baseline --no-ref-cli --no-check --steps 5 --warmup 2 $EXTRA $opts 2>/dev/null > /tmp/oc.json
+    python3 bench.py --full --no-cpu-baseline --no-ref-cli --no-check --steps 5 --warmup 2 $EXTRA $opts 2>/dev/null > /tmp/oc.json
     echo "[$var]"; python3 tools/bench_brief.py /tmp/oc.json | head -2
   done
 done

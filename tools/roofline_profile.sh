@@ -15,7 +15,7 @@ OUT="$ROOT/gpurun_out/roofline"
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd "$ROOT"
-ARGS="bench.py --markers --no-cpu-baseline --no-ref-cli --no-check --steps 5 --warmup 2"
+ARGS="bench.py --full --markers --no-cpu-baseline --no-ref-cli --no-check --steps 5 --warmup 2"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- python3 $ARGS > "$OUT/bench_trace.json" 2> "$OUT/bench_trace.err" || { echo "trace pass failed"; tail -5 "$OUT/bench_trace.err"; exit 1; }
 echo "trace pass done"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o run -- python3 $ARGS > "$OUT/bench_fetch.json" 2> "$OUT/bench_fetch.err" || { echo "FETCH_SIZE pass failed"; tail -5 "$OUT/bench_fetch.err"; exit 1; }
