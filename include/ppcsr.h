@@ -93,6 +93,23 @@ int ppcsr_get_neighbourhood(ppcsr_t h, int src, int *out, uint64_t cap, uint64_t
 int ppcsr_read_neighbourhood(ppcsr_t h, int src);
 /* bulk neighbour scan: get_neighbourhood for every vertex at once as CSR (row_offsets[n+1], dests[total]) */
 int ppcsr_scan_all(ppcsr_t h, uint64_t *row_offsets, int *dests, uint64_t cap, uint64_t *total);
+/* Batched reads.  Synchronous on the engine's stream (they see every batch applied before them); they write nothing to the
+ * graph (state, stats, dirty tags and the snapshot are unchanged).  The host-buffer forms stage through bounded buffers.
+ * lookup_edges — PCSR::edge_exists (PCSR.cpp:860-869) for n pairs at once, with the value: values[i] = value of edge
+ *   (src[i], dst[i]) exactly when ppcsr_edge_exists would report it (the same search, the same slot), else PPCSR_NO_EDGE;
+ *   src[i] >= n gives PPCSR_NO_EDGE (not EINVAL). */
+#define PPCSR_NO_EDGE 0xFFFFFFFFu /* cannot be a stored value: see the sentinel precondition at the top */
+int ppcsr_lookup_edges(ppcsr_t h, const uint32_t *src, const uint32_t *dst, uint64_t n, uint32_t *values);
+int ppcsr_lookup_edges_device(ppcsr_t h, const uint32_t *d_src, const uint32_t *d_dst, uint64_t n, uint32_t *d_values);
+/* gather_neighbourhoods — PCSR::get_neighbourhood (PCSR.cpp:901-912) for k vertices at once, as CSR in query order: row i
+ *   holds the live slots of (beginning, end) of vertices[i] in slot order, dests[] with the edge value beside each in values[];
+ *   vertices >= n give empty rows, repeats are allowed.  row_offsets[k + 1] (may be NULL); dests and values may be NULL (both
+ *   NULL: *total only); at most cap edges are written and ERANGE is returned when cap < *total (as ppcsr_scan_all). */
+int ppcsr_gather_neighbourhoods(ppcsr_t h, const uint32_t *vertices, uint64_t k, uint64_t *row_offsets, int *dests, uint32_t *values,
+                                uint64_t cap, uint64_t *total);
+/* the same, every array in this GPU's HBM (total: host) */
+int ppcsr_gather_neighbourhoods_device(ppcsr_t h, const uint32_t *d_vertices, uint64_t k, uint64_t *d_row_offsets, int *d_dests,
+                                       uint32_t *d_values, uint64_t cap, uint64_t *total);
 /* Bulk build of an EMPTY graph from a list of adds — an explicit NON-parity fast path: the reference can
  * only build a graph by single inserts (src/main.cpp:160-189 feeds add_edge one line at a time) and the array layout that
  * produces depends on the insertion history.  This call yields a valid packed-memory array with the same neighbourhoods,
@@ -164,6 +181,13 @@ int pppcsr_get_neighbourhood(pppcsr_t h, int src, int *out, uint64_t cap, uint64
 int pppcsr_get_node(pppcsr_t h, uint32_t v, ppcsr_node *out);
 int pppcsr_get_n(pppcsr_t h, uint64_t *n);
 int pppcsr_add_node(pppcsr_t h);
+/* PPPCSR::edge_exists / get_neighbourhood (PPPCSR.cpp:36-80) batched: queries are routed by owner (src made partition-local,
+ * PPPCSR.cpp:46-52), answered per partition by ppcsr_lookup_edges / ppcsr_gather_neighbourhoods on its device and returned in
+ * the caller's order (same arguments and results as those).  A query owned by a partition this process does not hold fails
+ * with EINVAL, as the single calls do. */
+int pppcsr_lookup_edges(pppcsr_t h, const uint32_t *src, const uint32_t *dst, uint64_t n, uint32_t *values);
+int pppcsr_gather_neighbourhoods(pppcsr_t h, const uint32_t *vertices, uint64_t k, uint64_t *row_offsets, int *dests, uint32_t *values,
+                                 uint64_t cap, uint64_t *total);
 /* bucket a host stream by owner (stable: per-partition order == stream order, src made partition-local as in
  * PPPCSR.cpp:46-52) and apply each bucket on its partition's GPU */
 int pppcsr_apply_batch(pppcsr_t h, const ppcsr_op *ops, uint64_t n);

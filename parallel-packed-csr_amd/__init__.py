@@ -50,8 +50,11 @@ EXPORTED = [
     "pppcsr_xchg_create", "pppcsr_xchg_destroy", "pppcsr_xchg_pack", "pppcsr_xchg_layout", "pppcsr_xchg_apply",
     "pppcsr_repartition_export", "pppcsr_repartition", "pppcsr_balanced_starts", "pppcsr_set_num_neighbors_device",
     "pppcsr_xchg_set_num_neighbors", "pppcsr_exchange_set_num_neighbors", "pppcsr_bulk_build_device", "pppcsr_xchg_bulk_build",
-    "pppcsr_exchange_bulk_build",
+    "pppcsr_exchange_bulk_build", "ppcsr_lookup_edges", "ppcsr_lookup_edges_device", "ppcsr_gather_neighbourhoods",
+    "ppcsr_gather_neighbourhoods_device", "pppcsr_lookup_edges", "pppcsr_gather_neighbourhoods",
 ]
+
+NO_EDGE = 0xFFFFFFFF  # PPCSR_NO_EDGE: what lookup_edges reports for a pair that is not an edge
 
 _LIBS = {}
 
@@ -103,6 +106,12 @@ def load_library(path=None):
     L.ppcsr_get_neighbourhood.argtypes = [c_vp, c_int, c_vp, c_u64, ctypes.POINTER(c_u64)]
     L.ppcsr_read_neighbourhood.argtypes = [c_vp, c_int]
     L.ppcsr_scan_all.argtypes = [c_vp, c_vp, c_vp, c_u64, ctypes.POINTER(c_u64)]
+    L.ppcsr_lookup_edges.argtypes = [c_vp, c_vp, c_vp, c_u64, c_vp]
+    L.ppcsr_lookup_edges_device.argtypes = [c_vp, c_vp, c_vp, c_u64, c_vp]
+    L.ppcsr_gather_neighbourhoods.argtypes = [c_vp, c_vp, c_u64, c_vp, c_vp, c_vp, c_u64, ctypes.POINTER(c_u64)]
+    L.ppcsr_gather_neighbourhoods_device.argtypes = [c_vp, c_vp, c_u64, c_vp, c_vp, c_vp, c_u64, ctypes.POINTER(c_u64)]
+    L.pppcsr_lookup_edges.argtypes = [c_vp, c_vp, c_vp, c_u64, c_vp]
+    L.pppcsr_gather_neighbourhoods.argtypes = [c_vp, c_vp, c_u64, c_vp, c_vp, c_vp, c_u64, ctypes.POINTER(c_u64)]
     L.ppcsr_bulk_build.argtypes = [c_vp, c_vp, c_u64, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_bfs.argtypes = [c_vp, c_u32, c_vp, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_pagerank.argtypes = [c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_double)]
@@ -165,6 +174,33 @@ def _ops(a):
     return a
 
 
+def _u32(a):
+    return np.ascontiguousarray(a, dtype=np.uint32).reshape(-1)
+
+
+def _lookup(fn, h, src, dst):
+    s, d = _u32(src), _u32(dst)
+    assert s.size == d.size, "src and dst must have the same length"
+    out = np.empty(s.size, np.uint32)
+    return fn(h, s.ctypes.data, d.ctypes.data, s.size, out.ctypes.data), out
+
+
+def _gather(fn, h, vertices, with_values):
+    """(rc, row_offsets, dests, values|None): the size query, then the gather into arrays of that size"""
+    q = _u32(vertices)
+    rows = np.zeros(q.size + 1, np.uint64)
+    tot = c_u64()
+    rc = fn(h, q.ctypes.data, q.size, rows.ctypes.data, None, None, 0, ctypes.byref(tot))
+    if rc != 0:
+        return rc, None, None, None
+    dests = np.empty(tot.value, np.int32)
+    vals = np.empty(tot.value, np.uint32) if with_values else None
+    if tot.value:
+        rc = fn(h, q.ctypes.data, q.size, rows.ctypes.data, dests.ctypes.data, vals.ctypes.data if with_values else None, tot.value,
+                ctypes.byref(tot))
+    return rc, rows, dests, vals
+
+
 class PCSR:
     """Mirror of the reference class PCSR (PCSR.h:64-124) on one GPU."""
 
@@ -223,6 +259,34 @@ class PCSR:
         return out
 
     def read_neighbourhood(self, src): self._chk(self.L.ppcsr_read_neighbourhood(self.h, src))
+
+    # batched reads (include/ppcsr.h: ppcsr_lookup_edges / ppcsr_gather_neighbourhoods)
+    def lookup_edges(self, src, dst):
+        """uint32 array: value of edge (src[i], dst[i]), NO_EDGE where edge_exists would say no (src >= n included)"""
+        rc, out = _lookup(self.L.ppcsr_lookup_edges, self.h, src, dst)
+        self._chk(rc)
+        return out
+
+    def edges_exist(self, src, dst):
+        return self.lookup_edges(src, dst) != NO_EDGE
+
+    def lookup_edges_device(self, src_ptr, dst_ptr, n, out_ptr):
+        """the same on device arrays (uint32, n entries each; e.g. torch tensors' data_ptr())"""
+        self._chk(self.L.ppcsr_lookup_edges_device(self.h, src_ptr, dst_ptr, n, out_ptr))
+
+    def gather_neighbourhoods(self, vertices, with_values=True):
+        """get_neighbourhood of every vertex as CSR in query order -> (row_offsets uint64[k + 1], dests int32, values uint32 | None)"""
+        rc, rows, dests, vals = _gather(self.L.ppcsr_gather_neighbourhoods, self.h, vertices, with_values)
+        self._chk(rc)
+        return rows, dests, vals
+
+    def gather_neighbourhoods_device(self, vertices_ptr, k, rows_ptr, dests_ptr, values_ptr, cap):
+        """device arrays (vertices uint32[k], rows uint64[k + 1], dests int32[cap], values uint32[cap]; pointers may be 0 / None
+        as in the C call) -> total edges; raises when cap is too small for them"""
+        tot = c_u64()
+        self._chk(self.L.ppcsr_gather_neighbourhoods_device(self.h, vertices_ptr, k, rows_ptr or None, dests_ptr or None, values_ptr or None,
+                                                            cap, ctypes.byref(tot)))
+        return tot.value
 
     # batch + state
     def apply(self, ops):
@@ -397,6 +461,19 @@ class PPPCSR:
         if cnt.value:
             self._chk(self.L.pppcsr_get_neighbourhood(self.h, src, out.ctypes.data, cnt.value, ctypes.byref(cnt)))
         return out
+
+    def lookup_edges(self, src, dst):
+        rc, out = _lookup(self.L.pppcsr_lookup_edges, self.h, src, dst)
+        self._chk(rc)
+        return out
+
+    def edges_exist(self, src, dst):
+        return self.lookup_edges(src, dst) != NO_EDGE
+
+    def gather_neighbourhoods(self, vertices, with_values=True):
+        rc, rows, dests, vals = _gather(self.L.pppcsr_gather_neighbourhoods, self.h, vertices, with_values)
+        self._chk(rc)
+        return rows, dests, vals
 
     def apply(self, ops):
         a = _ops(ops)

@@ -125,6 +125,28 @@ int ppcsr_scan_all(ppcsr_t h, uint64_t *row_offsets, int *dests, uint64_t cap, u
   H_CHECK();
   return ret(h->e, h->e->scan_all(row_offsets, dests, cap, total));
 }
+int ppcsr_lookup_edges(ppcsr_t h, const uint32_t *src, const uint32_t *dst, uint64_t n, uint32_t *values) {
+  H_CHECK();
+  if (n && (!src || !dst || !values)) return bad("lookup_edges: null argument");
+  return ret(h->e, h->e->lookup_edges(src, dst, n, values, false));
+}
+int ppcsr_lookup_edges_device(ppcsr_t h, const uint32_t *d_src, const uint32_t *d_dst, uint64_t n, uint32_t *d_values) {
+  H_CHECK();
+  if (n && (!d_src || !d_dst || !d_values)) return bad("lookup_edges: null argument");
+  return ret(h->e, h->e->lookup_edges(d_src, d_dst, n, d_values, true));
+}
+int ppcsr_gather_neighbourhoods(ppcsr_t h, const uint32_t *vertices, uint64_t k, uint64_t *row_offsets, int *dests, uint32_t *values,
+                                uint64_t cap, uint64_t *total) {
+  H_CHECK();
+  if (k && !vertices) return bad("gather_neighbourhoods: null vertices");
+  return ret(h->e, h->e->gather_neighbourhoods(vertices, k, row_offsets, dests, values, cap, total, false));
+}
+int ppcsr_gather_neighbourhoods_device(ppcsr_t h, const uint32_t *d_vertices, uint64_t k, uint64_t *d_row_offsets, int *d_dests,
+                                       uint32_t *d_values, uint64_t cap, uint64_t *total) {
+  H_CHECK();
+  if (k && !d_vertices) return bad("gather_neighbourhoods: null vertices");
+  return ret(h->e, h->e->gather_neighbourhoods(d_vertices, k, d_row_offsets, d_dests, d_values, cap, total, true));
+}
 int ppcsr_bulk_build(ppcsr_t h, const ppcsr_op *adds, uint64_t n, double *device_ms) {
   H_CHECK();
   if (!adds && n) return bad("bulk_build: null input");
@@ -463,6 +485,122 @@ int pppcsr_apply_batch(pppcsr_t h, const ppcsr_op *ops, uint64_t n) {
     off += counts[k];
   }
   return apply_parts(h, 0, P, ptrs.data(), counts.data(), PARTS_HOST);
+}
+
+// batched reads over the partitions: queries are bucketed by owner (stable, partition-local src) one bounded block at a time,
+// every partition answers its bucket with the single-engine call on its own device, and the answers go back to the caller's order
+static constexpr uint64_t kPartQueryBlock = 1ull << 20;  // queries routed at a time
+static constexpr uint64_t kPartGatherStage = 1ull << 22; // edges fetched from a partition at a time (a larger single row: its size)
+
+// owner of every query of [q, q + m): per-partition local ids in stable order (loc), their caller index (idx), bucket starts
+static int route_queries(pppcsr_t h, const uint32_t *q, uint64_t m, std::vector<uint32_t> &loc, std::vector<uint32_t> &idx,
+                         std::vector<uint64_t> &start) {
+  const uint64_t P = h->parts.size();
+  std::vector<uint32_t> own(m);
+  start.assign(P + 1, 0);
+  for (uint64_t i = 0; i < m; i++) {
+    own[i] = (uint32_t)owner_of(h->distribution, q[i]);
+    start[own[i] + 1]++;
+  }
+  for (uint64_t k = 0; k < P; k++) {
+    if (start[k + 1] && !h->parts[k]) return bad("partition not resident in this process");
+    start[k + 1] += start[k];
+  }
+  loc.resize(m);
+  idx.resize(m);
+  std::vector<uint64_t> at(start.begin(), start.end() - 1);
+  for (uint64_t i = 0; i < m; i++) {
+    const uint64_t j = at[own[i]]++;
+    loc[j] = (uint32_t)(q[i] - h->distribution[own[i]]);
+    idx[j] = (uint32_t)i;
+  }
+  return 0;
+}
+
+int pppcsr_lookup_edges(pppcsr_t h, const uint32_t *src, const uint32_t *dst, uint64_t n, uint32_t *values) {
+  PP_CHECK();
+  if (n && (!src || !dst || !values)) return bad("lookup_edges: null argument");
+  std::vector<uint32_t> loc, idx, d, val;
+  std::vector<uint64_t> start;
+  for (uint64_t i0 = 0; i0 < n; i0 += kPartQueryBlock) {
+    const uint64_t m = std::min(kPartQueryBlock, n - i0);
+    int rc = route_queries(h, src + i0, m, loc, idx, start);
+    if (rc != 0) return rc;
+    d.resize(m);
+    val.resize(m);
+    for (uint64_t j = 0; j < m; j++) d[j] = dst[i0 + idx[j]];
+    for (uint64_t k = 0; k + 1 < start.size(); k++) {
+      const uint64_t a = start[k], c = start[k + 1] - a;
+      if (c == 0) continue;
+      rc = ppcsr_lookup_edges(h->parts[k], loc.data() + a, d.data() + a, c, val.data() + a);
+      if (rc != 0) return rc;
+    }
+    for (uint64_t j = 0; j < m; j++) values[i0 + idx[j]] = val[j];
+  }
+  return 0;
+}
+
+int pppcsr_gather_neighbourhoods(pppcsr_t h, const uint32_t *vertices, uint64_t k, uint64_t *row_offsets, int *dests, uint32_t *values,
+                                 uint64_t cap, uint64_t *total) {
+  PP_CHECK();
+  if (k && !vertices) return bad("gather_neighbourhoods: null vertices");
+  const bool want = dests || values;
+  std::vector<uint32_t> loc, idx, sval;
+  std::vector<uint64_t> start, len, off, r;
+  std::vector<int> sdst;
+  uint64_t base = 0;  // edges of the blocks before
+  for (uint64_t i0 = 0; i0 < k; i0 += kPartQueryBlock) {
+    const uint64_t m = std::min(kPartQueryBlock, k - i0);
+    int rc = route_queries(h, vertices + i0, m, loc, idx, start);
+    if (rc != 0) return rc;
+    // row lengths from every partition (bucket order), then the rows' offsets in the caller's order
+    len.assign(m, 0);
+    for (uint64_t p = 0; p + 1 < start.size(); p++) {
+      const uint64_t a = start[p], c = start[p + 1] - a;
+      if (c == 0) continue;
+      r.assign(c + 1, 0);
+      uint64_t t = 0;
+      rc = ppcsr_gather_neighbourhoods(h->parts[p], loc.data() + a, c, r.data(), nullptr, nullptr, 0, &t);
+      if (rc != 0) return rc;
+      for (uint64_t j = 0; j < c; j++) len[a + j] = r[j + 1] - r[j];
+    }
+    off.assign(m + 1, 0);
+    for (uint64_t j = 0; j < m; j++) off[idx[j] + 1] = len[j];
+    off[0] = base;
+    for (uint64_t i = 0; i < m; i++) off[i + 1] += off[i];
+    if (row_offsets) std::copy(off.begin(), off.end(), row_offsets + i0);
+    // the edges: every partition's bucket in stretches of about kPartGatherStage edges, each row copied to its place
+    for (uint64_t p = 0; want && p + 1 < start.size(); p++) {
+      for (uint64_t a = start[p]; a < start[p + 1];) {
+        uint64_t b = a, cnt = 0;
+        bool any = false;
+        while (b < start[p + 1] && (b == a || cnt + len[b] <= kPartGatherStage)) {
+          any = any || (len[b] && off[idx[b]] < cap);
+          cnt += len[b++];
+        }
+        if (any) {
+          if (dests) sdst.resize(std::max<uint64_t>(cnt, 1));
+          if (values) sval.resize(std::max<uint64_t>(cnt, 1));
+          uint64_t t = 0;
+          rc = ppcsr_gather_neighbourhoods(h->parts[p], loc.data() + a, b - a, nullptr, dests ? sdst.data() : nullptr,
+                                           values ? sval.data() : nullptr, cnt, &t);
+          if (rc != 0) return rc;
+          uint64_t s = 0;
+          for (uint64_t j = a; j < b; s += len[j], j++) {
+            const uint64_t o = off[idx[j]];
+            const uint64_t c = o < cap ? std::min(len[j], cap - o) : 0;
+            if (dests) std::copy(sdst.begin() + s, sdst.begin() + s + c, dests + o);
+            if (values) std::copy(sval.begin() + s, sval.begin() + s + c, values + o);
+          }
+        }
+        a = b;
+      }
+    }
+    base = off[m];
+  }
+  if (k == 0 && row_offsets) row_offsets[0] = 0;
+  if (total) *total = base;
+  return (want && base > cap) ? PPCSR_STATUS_ERANGE : 0;
 }
 
 int pppcsr_apply_parts_device(pppcsr_t h, uint64_t first_part, uint64_t n_parts, const ppcsr_op *const *d_ops, const uint64_t *counts) {

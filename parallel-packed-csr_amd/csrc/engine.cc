@@ -205,6 +205,23 @@ struct Engine::Impl {
   uint32_t *d_dg = nullptr;  // diag >= 2: per-update trace of the batch (OptArgs::dg)
   uint64_t dg_cap = 0;
   std::vector<gpu::Event> events;  // init failed half-way: destructor frees only what exists
+  // scratch of the batched reads (lookup_edges / gather_neighbourhoods): bounded by the staging sizes below, except the
+  // per-chunk arrays of a gather block, which grow with the chunks of its rows (at most the largest row's, kGatherChunks else)
+  struct Query {
+    uint32_t *src = nullptr, *dst = nullptr, *val = nullptr;  // host lookups: kLookupStage queries
+    uint64_t lookup_cap = 0;
+    uint32_t *q = nullptr, *lo = nullptr, *len = nullptr, *nch = nullptr;  // gather rows: kGatherRows
+    unsigned long long *choff = nullptr, *rows = nullptr;                 // kGatherRows + 1
+    uint64_t rows_cap = 0;
+    uint32_t *crow = nullptr, *ccnt = nullptr;  // per chunk
+    unsigned long long *ooff = nullptr;         // per chunk + 1
+    uint64_t chunk_cap = 0;
+    int *sdst = nullptr;  // host gathers: output window of kGatherStage edges
+    uint32_t *sval = nullptr;
+    uint64_t stage_cap = 0;
+    unsigned long long *xs = nullptr;  // tile sums of the scans
+    uint64_t xs_cap = 0;
+  } q;
 };
 
 Engine::Engine() : p_(new Impl()) {}
@@ -474,6 +491,10 @@ Engine::~Engine() {
   if (p.d_jobs) GPU_DFREE(p.d_jobs);
   if (p.d_bigscratch) GPU_DFREE(p.d_bigscratch);
   if (p.d_dg) GPU_DFREE(p.d_dg);
+  for (void *b : {(void *)p.q.src, (void *)p.q.dst, (void *)p.q.val, (void *)p.q.q, (void *)p.q.lo, (void *)p.q.len, (void *)p.q.nch,
+                  (void *)p.q.choff, (void *)p.q.rows, (void *)p.q.crow, (void *)p.q.ccnt, (void *)p.q.ooff, (void *)p.q.sdst,
+                  (void *)p.q.sval, (void *)p.q.xs})
+    if (b) gpu::dfree(b);
   for (Impl::Snap *sp : {&p.snap, &p.esnap}) {
     if (sp->v.items) GPU_DFREE(sp->v.items);
     if (sp->v.nodes) GPU_DFREE(sp->v.nodes);
@@ -1693,6 +1714,223 @@ int Engine::get_neighbourhood(int src, int *out, uint64_t cap, uint64_t *count) 
 int Engine::read_neighbourhood(int src) {
   uint64_t c = 0;
   return get_neighbourhood(src, nullptr, 0, &c);
+}
+
+// ---- batched reads (pma_query.h) -----------------------------------------------------------------------------------
+// staging of the host-buffer calls and the block sizes of a gather: no allocation grows with the number of queries
+constexpr uint64_t kLookupStage = 1ull << 22;   // queries per H2D / D2H round trip of lookup_edges
+constexpr uint64_t kGatherRows = 1ull << 20;    // queried vertices per gather block
+constexpr uint64_t kGatherChunks = 1ull << 22;  // 64-slot chunks per gather block (a single row may need more: it gets them)
+constexpr uint64_t kGatherStage = 1ull << 22;   // edges per D2H window of a host gather
+
+// (re)allocate a device buffer to hold `need` elements; the old contents are not kept
+template <class T>
+static int grow_buf(T **b, uint64_t *cap, uint64_t need) {
+  if (need <= *cap && *b) return 0;
+  if (*b) gpu::dfree(*b);
+  *b = nullptr;
+  *cap = 0;
+  const int e = gpu::dmalloc((void **)b, need * sizeof(T));
+  if (e == 0) *cap = need;
+  return e;
+}
+
+// persistent grid of about `resident_waves` waves (the emulator reports none: a few workgroups) for `work` wave-sized items
+static uint32_t query_blocks(const Engine::Impl &p, uint64_t work) {
+  const uint64_t waves = std::min<uint64_t>(p.resident_waves ? p.resident_waves : 16u, std::max<uint64_t>(work, 1));
+  return (uint32_t)((waves + 3) / 4);
+}
+
+static uint64_t xs_scratch(uint64_t n) {
+  const uint64_t nb = (n + kXsTile - 1) / kXsTile;
+  return nb > 1 ? 2 * nb + 1 + xs_scratch(nb) : 0;
+}
+// scan of n elements of `in` into `out` (inclusive: n entries; else exclusive, n + 1 entries), by addition or (mx) maximum — the
+// gather uses three forms: u32 -> u64 add (in64 = false, out64 = true), u64 -> u64 add (the tile sums), u32 -> u32 max (in place)
+int Engine::xscan(const void *in, bool in64, uint64_t n, void *out, bool out64, bool mx, bool inclusive, unsigned long long *scr) {
+  Impl &p = *p_;
+  const uint32_t incl = inclusive ? 1u : 0u;
+  if (scr == nullptr) {
+    if (grow_buf(&p.q.xs, &p.q.xs_cap, xs_scratch(n) + 1)) return fail(PPCSR_ENOMEM, "gather: scan scratch");
+    scr = p.q.xs;
+  }
+  if (n == 0) {
+    if (!incl) GCHK(gpu::dset(out, 0, out64 ? 8 : 4, p.stream));
+    return PPCSR_OK;
+  }
+  const uint64_t nb = (n + kXsTile - 1) / kXsTile;
+  unsigned long long *bbase = nullptr;
+  if (nb > 1) {
+    unsigned long long *bsum = scr;
+    bbase = scr + nb;
+    if (in64) GPU_LAUNCH(p.stream, k_xs_reduce<unsigned long long>, nb, kXsThreads, (const unsigned long long *)in, n, (uint32_t)mx, bsum);
+    else GPU_LAUNCH(p.stream, k_xs_reduce<uint32_t>, nb, kXsThreads, (const uint32_t *)in, n, (uint32_t)mx, bsum);
+    const int rc = xscan(bsum, true, nb, bbase, true, mx, false, scr + 2 * nb + 1);  // (exclusive: bbase[b] = tiles before b)
+    if (rc != PPCSR_OK) return rc;
+  }
+  if (in64) GPU_LAUNCH(p.stream, (k_xs_scan<unsigned long long, unsigned long long>), nb, kXsThreads, (const unsigned long long *)in, n,
+                       (const unsigned long long *)bbase, (uint32_t)mx, incl, (unsigned long long *)out);
+  else if (out64) GPU_LAUNCH(p.stream, (k_xs_scan<uint32_t, unsigned long long>), nb, kXsThreads, (const uint32_t *)in, n,
+                             (const unsigned long long *)bbase, (uint32_t)mx, incl, (unsigned long long *)out);
+  else GPU_LAUNCH(p.stream, (k_xs_scan<uint32_t, uint32_t>), nb, kXsThreads, (const uint32_t *)in, n, (const unsigned long long *)bbase, (uint32_t)mx,
+                  incl, (uint32_t *)out);
+  return PPCSR_OK;
+}
+
+int Engine::lookup_edges(const uint32_t *src, const uint32_t *dst, uint64_t nq, uint32_t *values, bool on_device) {
+  Impl &p = *p_;
+  if (nq == 0) return PPCSR_OK;
+  GCHK(gpu::set_device(device_));
+  if (on_device) {
+    GPU_LAUNCH(p.stream, k_lookup_edges, query_blocks(p, (nq + 63) / 64), 256, p.v, src, dst, nq, values);
+  } else {
+    const uint64_t stage = std::min(nq, kLookupStage);
+    if (stage > p.q.lookup_cap) {
+      uint64_t c0 = p.q.lookup_cap, c1 = p.q.lookup_cap, c2 = p.q.lookup_cap;
+      if (grow_buf(&p.q.src, &c0, stage) || grow_buf(&p.q.dst, &c1, stage) || grow_buf(&p.q.val, &c2, stage)) {
+        p.q.lookup_cap = 0;
+        return fail(PPCSR_ENOMEM, "lookup_edges: staging");
+      }
+      p.q.lookup_cap = stage;
+    }
+    for (uint64_t i0 = 0; i0 < nq; i0 += stage) {
+      const uint64_t m = std::min(stage, nq - i0);
+      GCHK(gpu::h2d(p.q.src, src + i0, m * sizeof(uint32_t), p.stream));
+      GCHK(gpu::h2d(p.q.dst, dst + i0, m * sizeof(uint32_t), p.stream));
+      GPU_LAUNCH(p.stream, k_lookup_edges, query_blocks(p, (m + 63) / 64), 256, p.v, (const uint32_t *)p.q.src, (const uint32_t *)p.q.dst, m,
+                 p.q.val);
+      GCHK(gpu::d2h(values + i0, p.q.val, m * sizeof(uint32_t), p.stream));
+      GCHK(gpu::sync(p.stream));
+    }
+  }
+  GCHK(gpu::sync(p.stream));
+  GCHK(gpu::last_error());
+  return PPCSR_OK;
+}
+
+// rows [0, kb) of the device array q: slot ranges, chunk offsets, chunk -> row map, live slots per chunk and their scan.
+// Takes the longest prefix of the rows whose chunks fit kGatherChunks (at least one row): *kt rows, *C chunks, *T edges.
+int Engine::gather_prepare(const uint32_t *q, uint64_t kb, uint64_t *kt, uint64_t *C, uint64_t *T) {
+  Impl &p = *p_;
+  Impl::Query &g = p.q;
+  const uint32_t gb = grid_for(kb, 256, 4096);
+  GPU_LAUNCH(p.stream, k_gather_rows, gb, 256, p.v, q, kb, g.lo, g.len, g.nch);
+  int rc = xscan(g.nch, false, kb, g.choff, true, false, false);
+  if (rc != PPCSR_OK) return rc;
+  GCHK(gpu::d2h(p.h_total, g.choff + kb, sizeof(unsigned long long), p.stream));
+  GCHK(gpu::sync(p.stream));
+  uint64_t rows = kb, chunks = *p.h_total;
+  if (chunks > kGatherChunks && kb > 1) {
+    std::vector<unsigned long long> h(kb + 1);
+    GCHK(gpu::d2h(h.data(), g.choff, (kb + 1) * sizeof(unsigned long long), p.stream));
+    GCHK(gpu::sync(p.stream));
+    rows = (uint64_t)(std::upper_bound(h.begin(), h.end(), (unsigned long long)kGatherChunks) - h.begin()) - 1;  // h[rows] <= bound
+    if (rows < 1) rows = 1;
+    chunks = h[rows];
+  }
+  if (chunks + 1 > g.chunk_cap) {
+    const uint64_t need = std::max<uint64_t>(chunks + 1, 1024);
+    uint64_t c1 = g.chunk_cap, c2 = g.chunk_cap, c3 = g.chunk_cap;
+    if (grow_buf(&g.crow, &c1, need) || grow_buf(&g.ccnt, &c2, need) || grow_buf(&g.ooff, &c3, need)) {
+      g.chunk_cap = 0;
+      return fail(PPCSR_ENOMEM, "gather: chunk arrays");
+    }
+    g.chunk_cap = need;
+  }
+  if (chunks) {
+    GCHK(gpu::dset(g.crow, 0, chunks * sizeof(uint32_t), p.stream));
+    GPU_LAUNCH(p.stream, k_gather_mark, grid_for(rows, 256, 4096), 256, (const uint32_t *)g.nch, (const unsigned long long *)g.choff, rows, g.crow);
+    rc = xscan(g.crow, false, chunks, g.crow, false, true, true);
+    if (rc != PPCSR_OK) return rc;
+    GPU_LAUNCH(p.stream, k_gather_count, query_blocks(p, (chunks + 63) / 64), 256, p.v, (const uint32_t *)g.lo, (const uint32_t *)g.len,
+               (const unsigned long long *)g.choff, (const uint32_t *)g.crow, chunks, g.ccnt);
+  }
+  rc = xscan(g.ccnt, false, chunks, g.ooff, true, false, false);
+  if (rc != PPCSR_OK) return rc;
+  GCHK(gpu::d2h(p.h_total, g.ooff + chunks, sizeof(unsigned long long), p.stream));
+  GCHK(gpu::sync(p.stream));
+  *kt = rows;
+  *C = chunks;
+  *T = *p.h_total;
+  return PPCSR_OK;
+}
+
+int Engine::gather_neighbourhoods(const uint32_t *vertices, uint64_t k, uint64_t *row_offsets, int *dests, uint32_t *values, uint64_t cap,
+                                  uint64_t *total, bool on_device) {
+  Impl &p = *p_;
+  Impl::Query &g = p.q;
+  GCHK(gpu::set_device(device_));
+  const bool want = dests != nullptr || values != nullptr;
+  if (k) {
+    uint64_t c0 = g.rows_cap, c1 = g.rows_cap, c2 = g.rows_cap, c3 = g.rows_cap, c4 = g.rows_cap, c5 = g.rows_cap;
+    const uint64_t need = std::min(k, kGatherRows) + 1;
+    if (need > g.rows_cap) {
+      if (grow_buf(&g.q, &c0, need) || grow_buf(&g.lo, &c1, need) || grow_buf(&g.len, &c2, need) || grow_buf(&g.nch, &c3, need) ||
+          grow_buf(&g.choff, &c4, need) || grow_buf(&g.rows, &c5, need)) {
+        g.rows_cap = 0;
+        return fail(PPCSR_ENOMEM, "gather: row arrays");
+      }
+      g.rows_cap = need;
+    }
+  }
+  if (want && !on_device && cap) {
+    uint64_t c0 = g.stage_cap, c1 = g.stage_cap;
+    const uint64_t need = std::min(cap, kGatherStage);
+    if (need > g.stage_cap) {
+      if (grow_buf(&g.sdst, &c0, need) || grow_buf(&g.sval, &c1, need)) {
+        g.stage_cap = 0;
+        return fail(PPCSR_ENOMEM, "gather: output staging");
+      }
+      g.stage_cap = need;
+    }
+  }
+  uint64_t base = 0;  // edges of the rows before the block
+  for (uint64_t i0 = 0; i0 < k;) {
+    const uint64_t kb = std::min(k - i0, kGatherRows);
+    const uint32_t *q = vertices + i0;
+    if (!on_device) {
+      GCHK(gpu::h2d(g.q, vertices + i0, kb * sizeof(uint32_t), p.stream));
+      q = g.q;
+    }
+    uint64_t kt = 0, C = 0, T = 0;
+    int rc = gather_prepare(q, kb, &kt, &C, &T);
+    if (rc != PPCSR_OK) return rc;
+    if (row_offsets) {
+      unsigned long long *rows = on_device ? reinterpret_cast<unsigned long long *>(row_offsets) + i0 : g.rows;
+      GPU_LAUNCH(p.stream, k_gather_offsets, grid_for(kt + 1, 256, 4096), 256, (const unsigned long long *)g.choff, (const unsigned long long *)g.ooff,
+                 kt, base, rows);
+      if (!on_device) GCHK(gpu::d2h(row_offsets + i0, g.rows, (kt + 1) * sizeof(unsigned long long), p.stream));
+    }
+    const uint64_t lim = (want && base < cap) ? std::min(T, cap - base) : 0;  // edges of this block that fit the output
+    const uint32_t wb = query_blocks(p, (C + 63) / 64);
+    if (on_device) {
+      if (lim)
+        GPU_LAUNCH(p.stream, k_gather_write, wb, 256, p.v, (const uint32_t *)g.lo, (const uint32_t *)g.len, (const unsigned long long *)g.choff,
+                   (const uint32_t *)g.crow, C, (const unsigned long long *)g.ooff, (uint64_t)0, lim, dests ? dests + base : (int *)nullptr,
+                   values ? values + base : (uint32_t *)nullptr);
+    } else {
+      for (uint64_t w = 0; w < lim; w += kGatherStage) {
+        const uint64_t m = std::min(kGatherStage, lim - w);
+        GPU_LAUNCH(p.stream, k_gather_write, wb, 256, p.v, (const uint32_t *)g.lo, (const uint32_t *)g.len, (const unsigned long long *)g.choff,
+                   (const uint32_t *)g.crow, C, (const unsigned long long *)g.ooff, w, w + m, dests ? g.sdst : (int *)nullptr,
+                   values ? g.sval : (uint32_t *)nullptr);
+        if (dests) GCHK(gpu::d2h(dests + base + w, g.sdst, m * sizeof(int), p.stream));
+        if (values) GCHK(gpu::d2h(values + base + w, g.sval, m * sizeof(uint32_t), p.stream));
+        GCHK(gpu::sync(p.stream));
+      }
+    }
+    GCHK(gpu::sync(p.stream));
+    base += T;
+    i0 += kt;
+  }
+  if (k == 0 && row_offsets) {
+    if (on_device) GCHK(gpu::dset(row_offsets, 0, sizeof(uint64_t), p.stream));
+    else row_offsets[0] = 0;
+  }
+  GCHK(gpu::sync(p.stream));
+  GCHK(gpu::last_error());
+  if (total) *total = base;
+  return (want && base > cap) ? PPCSR_ERANGE : PPCSR_OK;
 }
 
 // bulk neighbour scan: live-edge count per 64-slot chunk from the leaf counts and the sentinel positions (no pass over

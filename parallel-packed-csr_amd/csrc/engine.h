@@ -45,6 +45,10 @@ class Engine {
   int get_node(uint32_t v, Node *out);
   int get_neighbourhood(int src, int *out, uint64_t cap, uint64_t *count);
   int read_neighbourhood(int src);
+  // batched reads (pma_query.h); the pointers are host memory, or this GPU's memory when on_device
+  int lookup_edges(const uint32_t *src, const uint32_t *dst, uint64_t n, uint32_t *values, bool on_device);
+  int gather_neighbourhoods(const uint32_t *vertices, uint64_t k, uint64_t *row_offsets, int *dests, uint32_t *values, uint64_t cap,
+                            uint64_t *total, bool on_device);
   int scan_all(uint64_t *row_offsets, int *dests, uint64_t cap, uint64_t *total);
   int export_triples_device(uint32_t src_base, Op *d_out, uint64_t cap, uint64_t *total);  // edges as adds of the global stream
   int export_num_neighbors_device(uint32_t base, Op *d_out);       // n records (vertex + base, num_neighbors, 1)
@@ -93,6 +97,8 @@ class Engine {
   int rebalance_fused(const View &nv, const Edge *src_items, uint64_t src_lo, uint64_t src_len, int src_sh, uint32_t *src_cnt,
                       bool inplace, uint64_t tb_index, uint64_t tb_len, Edge *dst, uint64_t dst_bias, uint32_t *dst_cnt, uint64_t dst_nleaves);
   int bulk_build_from(const Op *in_ops, bool on_device, uint64_t m, double *device_ms);
+  int xscan(const void *in, bool in64, uint64_t n, void *out, bool out64, bool mx, bool inclusive, unsigned long long *scr = nullptr);
+  int gather_prepare(const uint32_t *q, uint64_t kb, uint64_t *kt, uint64_t *C, uint64_t *T);
   int scan_launch(unsigned long long *d_rows, int *d_dst, uint64_t cap, const float *d_values = nullptr, float *d_contrib = nullptr,
                   Op *d_triples = nullptr, uint32_t src_base = 0);
 
