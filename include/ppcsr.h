@@ -139,7 +139,11 @@ int ppcsr_stats(ppcsr_t h, ppcsr_stats_t *out);
  *              rebalanced in place; 0 = always through the scratch array), "rb_inplace_cpw", "rb_inplace_lists"
  *   search     "search_narrow" (0: literal binary walk only)
  *   measuring  "profile" (1: HIP events around every round kernel, reported through ppcsr_stats), "diag" (1: why updates
- *              did not commit, per epoch, on stderr; 2: also a per-update dependency trace, PPCSR_DIAG_DUMP = file), "marker" (marker kernels for profile cuts), "test_block_rebalance" */
+ *              did not commit, per epoch, on stderr; 2: also a per-update dependency trace, PPCSR_DIAG_DUMP = file), "marker" (marker kernels for profile cuts), "test_block_rebalance"
+ *   reads      test hooks that move the seams of the batched reads (defaults = the shipped sizes; values in [1, 2^32]):
+ *              "query_lookup_stage" (host lookups per H2D / D2H round trip; 2^22), "query_gather_rows" (queried vertices
+ *              per gather block; 2^20), "query_gather_chunks" (64-slot chunks per gather block; 2^22), "query_gather_stage"
+ *              (edges per D2H window of a host gather; 2^22) */
 int ppcsr_set_option(ppcsr_t h, const char *key, int64_t value);
 /* device-side copy of the whole state and return to it (used by the benchmark to replay a batch on the same
  * core graph, and by the engine itself as the rollback point of speculative rounds); no reference equivalent.
@@ -188,6 +192,10 @@ int pppcsr_add_node(pppcsr_t h);
 int pppcsr_lookup_edges(pppcsr_t h, const uint32_t *src, const uint32_t *dst, uint64_t n, uint32_t *values);
 int pppcsr_gather_neighbourhoods(pppcsr_t h, const uint32_t *vertices, uint64_t k, uint64_t *row_offsets, int *dests, uint32_t *values,
                                  uint64_t cap, uint64_t *total);
+/* sizes of the two calls above (test hooks that move their seams; the defaults are the shipped sizes): "query_block" (queries
+ * routed at a time; default 2^20), "gather_stage" (edges fetched from one partition at a time; default 2^22).  Values in
+ * [1, 2^32]; any other key or value fails with EINVAL. */
+int pppcsr_set_option(pppcsr_t h, const char *key, int64_t value);
 /* bucket a host stream by owner (stable: per-partition order == stream order, src made partition-local as in
  * PPPCSR.cpp:46-52) and apply each bucket on its partition's GPU */
 int pppcsr_apply_batch(pppcsr_t h, const ppcsr_op *ops, uint64_t n);

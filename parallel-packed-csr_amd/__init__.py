@@ -51,7 +51,7 @@ EXPORTED = [
     "pppcsr_repartition_export", "pppcsr_repartition", "pppcsr_balanced_starts", "pppcsr_set_num_neighbors_device",
     "pppcsr_xchg_set_num_neighbors", "pppcsr_exchange_set_num_neighbors", "pppcsr_bulk_build_device", "pppcsr_xchg_bulk_build",
     "pppcsr_exchange_bulk_build", "ppcsr_lookup_edges", "ppcsr_lookup_edges_device", "ppcsr_gather_neighbourhoods",
-    "ppcsr_gather_neighbourhoods_device", "pppcsr_lookup_edges", "pppcsr_gather_neighbourhoods",
+    "ppcsr_gather_neighbourhoods_device", "pppcsr_lookup_edges", "pppcsr_gather_neighbourhoods", "pppcsr_set_option",
 ]
 
 NO_EDGE = 0xFFFFFFFF  # PPCSR_NO_EDGE: what lookup_edges reports for a pair that is not an edge
@@ -112,6 +112,7 @@ def load_library(path=None):
     L.ppcsr_gather_neighbourhoods_device.argtypes = [c_vp, c_vp, c_u64, c_vp, c_vp, c_vp, c_u64, ctypes.POINTER(c_u64)]
     L.pppcsr_lookup_edges.argtypes = [c_vp, c_vp, c_vp, c_u64, c_vp]
     L.pppcsr_gather_neighbourhoods.argtypes = [c_vp, c_vp, c_u64, c_vp, c_vp, c_vp, c_u64, ctypes.POINTER(c_u64)]
+    L.pppcsr_set_option.argtypes = [c_vp, ctypes.c_char_p, c_i64]
     L.ppcsr_bulk_build.argtypes = [c_vp, c_vp, c_u64, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_bfs.argtypes = [c_vp, c_u32, c_vp, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_pagerank.argtypes = [c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_double)]
@@ -474,6 +475,10 @@ class PPPCSR:
         rc, rows, dests, vals = _gather(self.L.pppcsr_gather_neighbourhoods, self.h, vertices, with_values)
         self._chk(rc)
         return rows, dests, vals
+
+    def set_option(self, key, value):
+        """sizes of the batched reads: "query_block", "gather_stage" (include/ppcsr.h: pppcsr_set_option)"""
+        self._chk(self.L.pppcsr_set_option(self.h, key.encode(), int(value)))
 
     def apply(self, ops):
         a = _ops(ops)

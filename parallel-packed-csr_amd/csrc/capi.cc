@@ -216,6 +216,10 @@ struct pppcsr_engine {
   ppcsr_op *d_bucketed = nullptr;
   uint64_t bucketed_cap = 0;
   uint64_t *d_counts = nullptr;
+  // sizes of the batched reads (pppcsr_set_option): queries routed at a time, edges fetched from a partition at a time (a
+  // larger single row: its size)
+  uint64_t query_block = 1ull << 20;
+  uint64_t gather_stage = 1ull << 22;
   // identity of this handle: a communicator's staging (pppcsr_comm::x) is keyed on it, not on the pointer — a destroyed handle's
   // address can be handed out again by the allocator
   uint64_t gen = next_generation();
@@ -489,8 +493,15 @@ int pppcsr_apply_batch(pppcsr_t h, const ppcsr_op *ops, uint64_t n) {
 
 // batched reads over the partitions: queries are bucketed by owner (stable, partition-local src) one bounded block at a time,
 // every partition answers its bucket with the single-engine call on its own device, and the answers go back to the caller's order
-static constexpr uint64_t kPartQueryBlock = 1ull << 20;  // queries routed at a time
-static constexpr uint64_t kPartGatherStage = 1ull << 22; // edges fetched from a partition at a time (a larger single row: its size)
+// (blocks of h->query_block queries, partition stretches of about h->gather_stage edges)
+int pppcsr_set_option(pppcsr_t h, const char *key, int64_t value) {
+  PP_CHECK();
+  const std::string k(key ? key : "");
+  if (k != "query_block" && k != "gather_stage") return bad("pppcsr_set_option: unknown key");
+  if (value < 1 || value > (1ll << 32)) return bad("pppcsr_set_option: value must be in [1, 2^32]");
+  (k == "query_block" ? h->query_block : h->gather_stage) = (uint64_t)value;
+  return 0;
+}
 
 // owner of every query of [q, q + m): per-partition local ids in stable order (loc), their caller index (idx), bucket starts
 static int route_queries(pppcsr_t h, const uint32_t *q, uint64_t m, std::vector<uint32_t> &loc, std::vector<uint32_t> &idx,
@@ -522,8 +533,8 @@ int pppcsr_lookup_edges(pppcsr_t h, const uint32_t *src, const uint32_t *dst, ui
   if (n && (!src || !dst || !values)) return bad("lookup_edges: null argument");
   std::vector<uint32_t> loc, idx, d, val;
   std::vector<uint64_t> start;
-  for (uint64_t i0 = 0; i0 < n; i0 += kPartQueryBlock) {
-    const uint64_t m = std::min(kPartQueryBlock, n - i0);
+  for (uint64_t i0 = 0; i0 < n; i0 += h->query_block) {
+    const uint64_t m = std::min(h->query_block, n - i0);
     int rc = route_queries(h, src + i0, m, loc, idx, start);
     if (rc != 0) return rc;
     d.resize(m);
@@ -549,8 +560,8 @@ int pppcsr_gather_neighbourhoods(pppcsr_t h, const uint32_t *vertices, uint64_t 
   std::vector<uint64_t> start, len, off, r;
   std::vector<int> sdst;
   uint64_t base = 0;  // edges of the blocks before
-  for (uint64_t i0 = 0; i0 < k; i0 += kPartQueryBlock) {
-    const uint64_t m = std::min(kPartQueryBlock, k - i0);
+  for (uint64_t i0 = 0; i0 < k; i0 += h->query_block) {
+    const uint64_t m = std::min(h->query_block, k - i0);
     int rc = route_queries(h, vertices + i0, m, loc, idx, start);
     if (rc != 0) return rc;
     // row lengths from every partition (bucket order), then the rows' offsets in the caller's order
@@ -569,12 +580,12 @@ int pppcsr_gather_neighbourhoods(pppcsr_t h, const uint32_t *vertices, uint64_t 
     off[0] = base;
     for (uint64_t i = 0; i < m; i++) off[i + 1] += off[i];
     if (row_offsets) std::copy(off.begin(), off.end(), row_offsets + i0);
-    // the edges: every partition's bucket in stretches of about kPartGatherStage edges, each row copied to its place
+    // the edges: every partition's bucket in stretches of about gather_stage edges, each row copied to its place
     for (uint64_t p = 0; want && p + 1 < start.size(); p++) {
       for (uint64_t a = start[p]; a < start[p + 1];) {
         uint64_t b = a, cnt = 0;
         bool any = false;
-        while (b < start[p + 1] && (b == a || cnt + len[b] <= kPartGatherStage)) {
+        while (b < start[p + 1] && (b == a || cnt + len[b] <= h->gather_stage)) {
           any = any || (len[b] && off[idx[b]] < cap);
           cnt += len[b++];
         }

@@ -206,17 +206,22 @@ struct Engine::Impl {
   uint64_t dg_cap = 0;
   std::vector<gpu::Event> events;  // init failed half-way: destructor frees only what exists
   // scratch of the batched reads (lookup_edges / gather_neighbourhoods): bounded by the staging sizes below, except the
-  // per-chunk arrays of a gather block, which grow with the chunks of its rows (at most the largest row's, kGatherChunks else)
+  // per-chunk arrays of a gather block, which grow with the chunks of its rows (at most the largest row's, gather_chunks else)
   struct Query {
-    uint32_t *src = nullptr, *dst = nullptr, *val = nullptr;  // host lookups: kLookupStage queries
+    // the sizes ("query_*" knobs, test hooks that reach the seams at small sizes; the defaults are the shipped sizes)
+    uint64_t lookup_stage = 1ull << 22;  // queries per H2D / D2H round trip of lookup_edges
+    uint64_t gather_rows = 1ull << 20;   // queried vertices per gather block
+    uint64_t gather_chunks = 1ull << 22; // 64-slot chunks per gather block (a single row may need more: it gets them)
+    uint64_t gather_stage = 1ull << 22;  // edges per D2H window of a host gather
+    uint32_t *src = nullptr, *dst = nullptr, *val = nullptr;  // host lookups: lookup_stage queries
     uint64_t lookup_cap = 0;
-    uint32_t *q = nullptr, *lo = nullptr, *len = nullptr, *nch = nullptr;  // gather rows: kGatherRows
-    unsigned long long *choff = nullptr, *rows = nullptr;                 // kGatherRows + 1
+    uint32_t *q = nullptr, *lo = nullptr, *len = nullptr, *nch = nullptr;  // gather rows: gather_rows
+    unsigned long long *choff = nullptr, *rows = nullptr;                 // gather_rows + 1
     uint64_t rows_cap = 0;
     uint32_t *crow = nullptr, *ccnt = nullptr;  // per chunk
     unsigned long long *ooff = nullptr;         // per chunk + 1
     uint64_t chunk_cap = 0;
-    int *sdst = nullptr;  // host gathers: output window of kGatherStage edges
+    int *sdst = nullptr;  // host gathers: output window of gather_stage edges
     uint32_t *sval = nullptr;
     uint64_t stage_cap = 0;
     unsigned long long *xs = nullptr;  // tile sums of the scans
@@ -621,6 +626,16 @@ int Engine::set_option(const char *key, int64_t value) {
   if (k == "rb_inplace_lists") {  // (test hook: 1, 2, 4 or 8 ticket lists whatever the probe saw)
     if (value != 1 && value != 2 && value != 4 && value != 8) return fail(PPCSR_EINVAL, "rb_inplace_lists must be 1, 2, 4 or 8");
     p.ip_lists = (uint32_t)value;
+    return PPCSR_OK;
+  }
+  // batched-read sizes (test hooks, as rb_inplace_lists: they move the seams of the staging and of the gather blocks; the
+  // scratch they size is regrown by the next call that needs more)
+  if (k == "query_lookup_stage" || k == "query_gather_rows" || k == "query_gather_chunks" || k == "query_gather_stage") {
+    if (value < 1 || value > (1ll << 32)) return fail(PPCSR_EINVAL, "query sizes must be in [1, 2^32]");
+    uint64_t &f = k == "query_lookup_stage" ? p.q.lookup_stage
+                : k == "query_gather_rows" ? p.q.gather_rows
+                : k == "query_gather_chunks" ? p.q.gather_chunks : p.q.gather_stage;
+    f = (uint64_t)value;
     return PPCSR_OK;
   }
   if (k == "rb_inplace_cpw") {
@@ -1717,11 +1732,8 @@ int Engine::read_neighbourhood(int src) {
 }
 
 // ---- batched reads (pma_query.h) -----------------------------------------------------------------------------------
-// staging of the host-buffer calls and the block sizes of a gather: no allocation grows with the number of queries
-constexpr uint64_t kLookupStage = 1ull << 22;   // queries per H2D / D2H round trip of lookup_edges
-constexpr uint64_t kGatherRows = 1ull << 20;    // queried vertices per gather block
-constexpr uint64_t kGatherChunks = 1ull << 22;  // 64-slot chunks per gather block (a single row may need more: it gets them)
-constexpr uint64_t kGatherStage = 1ull << 22;   // edges per D2H window of a host gather
+// staging of the host-buffer calls and the block sizes of a gather (Impl::Query: lookup_stage, gather_rows, gather_chunks,
+// gather_stage): no allocation grows with the number of queries
 
 // (re)allocate a device buffer to hold `need` elements; the old contents are not kept
 template <class T>
@@ -1784,7 +1796,7 @@ int Engine::lookup_edges(const uint32_t *src, const uint32_t *dst, uint64_t nq, 
   if (on_device) {
     GPU_LAUNCH(p.stream, k_lookup_edges, query_blocks(p, (nq + 63) / 64), 256, p.v, src, dst, nq, values);
   } else {
-    const uint64_t stage = std::min(nq, kLookupStage);
+    const uint64_t stage = std::min(nq, p.q.lookup_stage);
     if (stage > p.q.lookup_cap) {
       uint64_t c0 = p.q.lookup_cap, c1 = p.q.lookup_cap, c2 = p.q.lookup_cap;
       if (grow_buf(&p.q.src, &c0, stage) || grow_buf(&p.q.dst, &c1, stage) || grow_buf(&p.q.val, &c2, stage)) {
@@ -1809,7 +1821,7 @@ int Engine::lookup_edges(const uint32_t *src, const uint32_t *dst, uint64_t nq, 
 }
 
 // rows [0, kb) of the device array q: slot ranges, chunk offsets, chunk -> row map, live slots per chunk and their scan.
-// Takes the longest prefix of the rows whose chunks fit kGatherChunks (at least one row): *kt rows, *C chunks, *T edges.
+// Takes the longest prefix of the rows whose chunks fit gather_chunks (at least one row): *kt rows, *C chunks, *T edges.
 int Engine::gather_prepare(const uint32_t *q, uint64_t kb, uint64_t *kt, uint64_t *C, uint64_t *T) {
   Impl &p = *p_;
   Impl::Query &g = p.q;
@@ -1820,11 +1832,11 @@ int Engine::gather_prepare(const uint32_t *q, uint64_t kb, uint64_t *kt, uint64_
   GCHK(gpu::d2h(p.h_total, g.choff + kb, sizeof(unsigned long long), p.stream));
   GCHK(gpu::sync(p.stream));
   uint64_t rows = kb, chunks = *p.h_total;
-  if (chunks > kGatherChunks && kb > 1) {
+  if (chunks > g.gather_chunks && kb > 1) {
     std::vector<unsigned long long> h(kb + 1);
     GCHK(gpu::d2h(h.data(), g.choff, (kb + 1) * sizeof(unsigned long long), p.stream));
     GCHK(gpu::sync(p.stream));
-    rows = (uint64_t)(std::upper_bound(h.begin(), h.end(), (unsigned long long)kGatherChunks) - h.begin()) - 1;  // h[rows] <= bound
+    rows = (uint64_t)(std::upper_bound(h.begin(), h.end(), (unsigned long long)g.gather_chunks) - h.begin()) - 1;  // h[rows] <= bound
     if (rows < 1) rows = 1;
     chunks = h[rows];
   }
@@ -1863,7 +1875,7 @@ int Engine::gather_neighbourhoods(const uint32_t *vertices, uint64_t k, uint64_t
   const bool want = dests != nullptr || values != nullptr;
   if (k) {
     uint64_t c0 = g.rows_cap, c1 = g.rows_cap, c2 = g.rows_cap, c3 = g.rows_cap, c4 = g.rows_cap, c5 = g.rows_cap;
-    const uint64_t need = std::min(k, kGatherRows) + 1;
+    const uint64_t need = std::min(k, g.gather_rows) + 1;
     if (need > g.rows_cap) {
       if (grow_buf(&g.q, &c0, need) || grow_buf(&g.lo, &c1, need) || grow_buf(&g.len, &c2, need) || grow_buf(&g.nch, &c3, need) ||
           grow_buf(&g.choff, &c4, need) || grow_buf(&g.rows, &c5, need)) {
@@ -1875,7 +1887,7 @@ int Engine::gather_neighbourhoods(const uint32_t *vertices, uint64_t k, uint64_t
   }
   if (want && !on_device && cap) {
     uint64_t c0 = g.stage_cap, c1 = g.stage_cap;
-    const uint64_t need = std::min(cap, kGatherStage);
+    const uint64_t need = std::min(cap, g.gather_stage);
     if (need > g.stage_cap) {
       if (grow_buf(&g.sdst, &c0, need) || grow_buf(&g.sval, &c1, need)) {
         g.stage_cap = 0;
@@ -1886,7 +1898,7 @@ int Engine::gather_neighbourhoods(const uint32_t *vertices, uint64_t k, uint64_t
   }
   uint64_t base = 0;  // edges of the rows before the block
   for (uint64_t i0 = 0; i0 < k;) {
-    const uint64_t kb = std::min(k - i0, kGatherRows);
+    const uint64_t kb = std::min(k - i0, g.gather_rows);
     const uint32_t *q = vertices + i0;
     if (!on_device) {
       GCHK(gpu::h2d(g.q, vertices + i0, kb * sizeof(uint32_t), p.stream));
@@ -1909,8 +1921,8 @@ int Engine::gather_neighbourhoods(const uint32_t *vertices, uint64_t k, uint64_t
                    (const uint32_t *)g.crow, C, (const unsigned long long *)g.ooff, (uint64_t)0, lim, dests ? dests + base : (int *)nullptr,
                    values ? values + base : (uint32_t *)nullptr);
     } else {
-      for (uint64_t w = 0; w < lim; w += kGatherStage) {
-        const uint64_t m = std::min(kGatherStage, lim - w);
+      for (uint64_t w = 0; w < lim; w += g.gather_stage) {
+        const uint64_t m = std::min(g.gather_stage, lim - w);
         GPU_LAUNCH(p.stream, k_gather_write, wb, 256, p.v, (const uint32_t *)g.lo, (const uint32_t *)g.len, (const unsigned long long *)g.choff,
                    (const uint32_t *)g.crow, C, (const unsigned long long *)g.ooff, w, w + m, dests ? g.sdst : (int *)nullptr,
                    values ? g.sval : (uint32_t *)nullptr);

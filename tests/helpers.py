@@ -195,3 +195,93 @@ def check_repartitioned(new_states, old_states, old_starts, new_starts, total_n,
             check_pma_invariants(np.asarray(it, np.uint32).reshape(-1, 3), nd)
         if len(sub):
             np.testing.assert_array_equal(live_triples(it, lo), sub + np.array([lo, 0, 0], np.uint32))
+
+
+# ---- exact models of the batched reads (ppcsr_lookup_edges / ppcsr_gather_neighbourhoods) on an exported state ------------
+NO_EDGE = 0xFFFFFFFF
+ERANGE = 6  # PPCSR_STATUS_ERANGE
+
+
+def _live(items):
+    return (items[:, 2] != 0) & (items[:, 1] != 0xFFFFFFFF) & (items[:, 2] != 0xFFFFFFFF)
+
+
+def model_lookup(items, n, qs, qd):
+    """value of edge (qs[i], qd[i]) or NO_EDGE, from the sorted src << 32 | dst keys of the live slots (uint64)"""
+    live = _live(items)
+    keys = (items[live, 0].astype(np.uint64) << np.uint64(32)) | items[live, 1].astype(np.uint64)
+    vals = items[live, 2]
+    order = np.argsort(keys, kind="stable")
+    keys, vals = keys[order], vals[order]
+    assert np.all(np.diff(keys) > 0), "an edge in two live slots"
+    qk = (qs.astype(np.uint64) << np.uint64(32)) | qd.astype(np.uint64)
+    pos = np.minimum(np.searchsorted(keys, qk), max(len(keys) - 1, 0))
+    hit = (len(keys) > 0) & (keys[pos] == qk) & (qs < n) if len(keys) else np.zeros(len(qk), bool)
+    return np.where(hit, vals[pos] if len(keys) else 0, np.uint32(NO_EDGE)).astype(np.uint32)
+
+
+def model_gather(items, nodes, verts):
+    """(row_offsets uint64[k + 1], dests int32, values uint32): the live slots of (beginning, end) of every queried vertex"""
+    n = len(nodes)
+    v = verts.astype(np.int64)
+    ok = v < n
+    lo = np.zeros(len(v), np.int64)
+    hi = np.zeros(len(v), np.int64)
+    lo[ok] = nodes[v[ok], 0].astype(np.int64) + 1
+    hi[ok] = nodes[v[ok], 1].astype(np.int64)
+    lens = np.maximum(hi - lo, 0)
+    tot = int(lens.sum())
+    idx = np.repeat(lo - np.cumsum(lens) + lens, lens) + np.arange(tot, dtype=np.int64)
+    rid = np.repeat(np.arange(len(v)), lens)
+    keep = items[idx, 2] != 0
+    sel = idx[keep]
+    cnt = np.bincount(rid[keep], minlength=len(v))
+    rows = np.concatenate([[0], np.cumsum(cnt)]).astype(np.uint64)
+    return rows, items[sel, 1].astype(np.int32), items[sel, 2]
+
+
+def gather_chunks(nodes, verts):
+    """64-slot chunks of every queried vertex's range (what k_gather_rows counts), int64"""
+    n = len(nodes)
+    v = verts.astype(np.int64)
+    ok = v < n
+    lens = np.zeros(len(v), np.int64)
+    lens[ok] = np.maximum(nodes[v[ok], 1].astype(np.int64) - nodes[v[ok], 0].astype(np.int64) - 1, 0)
+    return (lens + 63) // 64
+
+
+def gather_blocks(nodes, verts, rows=1 << 20, chunks=1 << 22):
+    """the first row of every block a gather splits the queries into (Engine::gather_neighbourhoods / gather_prepare with
+    query_gather_rows = rows, query_gather_chunks = chunks), then k: a block takes up to `rows` rows, cut back to the longest
+    prefix whose chunks fit `chunks` (at least one row)"""
+    nch = gather_chunks(nodes, verts)
+    k = len(verts)
+    cs = np.concatenate([[0], np.cumsum(nch)])
+    out, i0 = [0], 0
+    while i0 < k:
+        kb = min(k - i0, rows)
+        if cs[i0 + kb] - cs[i0] > chunks and kb > 1:
+            kb = max(int(np.searchsorted(cs[i0:i0 + kb + 1] - cs[i0], chunks, side="right")) - 1, 1)
+        i0 += kb
+        out.append(i0)
+    return np.array(out, np.int64)
+
+
+def check_partial_gather(call, full_rows, full_dests, full_vals, cap, canary=-7):
+    """call(rows, dests, vals, cap, total) issues the gather into the given numpy arrays (total: a ctypes.c_uint64) and returns
+    the status: the first cap edges are the full result's, nothing past them is written, the total and the row offsets are
+    complete, and the status is ERANGE exactly when cap < total"""
+    import ctypes
+    T = len(full_dests)
+    rows = np.zeros(len(full_rows), np.uint64)
+    dests = np.full(T + 8, canary, np.int32)
+    vals = np.full(T + 8, 0xA5A5A5A5, np.uint32)
+    tot = ctypes.c_uint64(0)
+    rc = call(rows, dests, vals, cap, tot)
+    assert rc == (ERANGE if cap < T else 0), (rc, cap, T)
+    assert tot.value == T, (tot.value, T)
+    np.testing.assert_array_equal(rows, full_rows, err_msg=f"row offsets, cap {cap}")
+    m = min(cap, T)
+    np.testing.assert_array_equal(dests[:m], full_dests[:m], err_msg=f"dests, cap {cap}")
+    np.testing.assert_array_equal(vals[:m], full_vals[:m], err_msg=f"values, cap {cap}")
+    assert np.all(dests[m:] == canary) and np.all(vals[m:] == 0xA5A5A5A5), f"written past cap {cap}"

@@ -5,7 +5,7 @@ through torch tensors, and lookups interleaved with batches.  Answers are compar
 import numpy as np
 import pytest
 
-from helpers import load_pkg
+from helpers import _live, load_pkg, model_gather, model_lookup
 from oracle_lib import Oracle
 
 pytestmark = pytest.mark.gpu
@@ -18,42 +18,6 @@ def pkg():
     p = load_pkg()
     p.load_library()
     return p
-
-
-def _live(items):
-    return (items[:, 2] != 0) & (items[:, 1] != 0xFFFFFFFF) & (items[:, 2] != 0xFFFFFFFF)
-
-
-def model_lookup(items, n, qs, qd):
-    live = _live(items)
-    keys = (items[live, 0].astype(np.uint64) << np.uint64(32)) | items[live, 1].astype(np.uint64)
-    vals = items[live, 2]
-    order = np.argsort(keys, kind="stable")
-    keys, vals = keys[order], vals[order]
-    assert np.all(np.diff(keys) > 0), "an edge in two live slots"
-    qk = (qs.astype(np.uint64) << np.uint64(32)) | qd.astype(np.uint64)
-    pos = np.minimum(np.searchsorted(keys, qk), max(len(keys) - 1, 0))
-    hit = (len(keys) > 0) & (keys[pos] == qk) & (qs < n) if len(keys) else np.zeros(len(qk), bool)
-    return np.where(hit, vals[pos] if len(keys) else 0, np.uint32(NO_EDGE)).astype(np.uint32)
-
-
-def model_gather(items, nodes, verts):
-    n = len(nodes)
-    v = verts.astype(np.int64)
-    ok = v < n
-    lo = np.zeros(len(v), np.int64)
-    hi = np.zeros(len(v), np.int64)
-    lo[ok] = nodes[v[ok], 0].astype(np.int64) + 1
-    hi[ok] = nodes[v[ok], 1].astype(np.int64)
-    lens = np.maximum(hi - lo, 0)
-    tot = int(lens.sum())
-    idx = np.repeat(lo - np.cumsum(lens) + lens, lens) + np.arange(tot, dtype=np.int64)
-    rid = np.repeat(np.arange(len(v)), lens)
-    keep = items[idx, 2] != 0
-    sel = idx[keep]
-    cnt = np.bincount(rid[keep], minlength=len(v))
-    rows = np.concatenate([[0], np.cumsum(cnt)]).astype(np.uint64)
-    return rows, items[sel, 1].astype(np.int32), items[sel, 2]
 
 
 def check_queries(e, rng, n_lookup, n_gather, label):
