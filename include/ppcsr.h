@@ -196,6 +196,15 @@ int pppcsr_gather_neighbourhoods(pppcsr_t h, const uint32_t *vertices, uint64_t 
  * routed at a time; default 2^20), "gather_stage" (edges fetched from one partition at a time; default 2^22).  Values in
  * [1, 2^32]; any other key or value fails with EINVAL. */
 int pppcsr_set_option(pppcsr_t h, const char *key, int64_t value);
+/* bfs.h:15-36 / pagerank.h:15-29 instantiated with T = PPPCSR (get_neighbourhood / getNode routed as in PPPCSR.cpp:40-42,
+ * 76-80): the arguments and results of ppcsr_bfs / ppcsr_pagerank over the GLOBAL vertex ids (levels, node_values, out:
+ * pppcsr_get_n entries).  One device call over every partition's array: per BFS level one launch whatever the number of
+ * partitions; PageRank adds in ascending global source order, bit-identical to the template.  Destinations >= pppcsr_get_n
+ * are skipped, as the single calls skip those >= n.  Synchronous; sees every batch applied before it; writes nothing to any
+ * partition.  EINVAL: null handle or output, start >= pppcsr_get_n, or a partition not resident in this process.
+ * EUNSUPPORTED: the partitions sit on more than one device (pppcsr_create with several devices) — run the host template. */
+int pppcsr_bfs(pppcsr_t h, uint32_t start, uint32_t *levels, double *device_ms);
+int pppcsr_pagerank(pppcsr_t h, const float *node_values, float *out, double *device_ms);
 /* bucket a host stream by owner (stable: per-partition order == stream order, src made partition-local as in
  * PPPCSR.cpp:46-52) and apply each bucket on its partition's GPU */
 int pppcsr_apply_batch(pppcsr_t h, const ppcsr_op *ops, uint64_t n);

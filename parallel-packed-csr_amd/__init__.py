@@ -52,6 +52,7 @@ EXPORTED = [
     "pppcsr_xchg_set_num_neighbors", "pppcsr_exchange_set_num_neighbors", "pppcsr_bulk_build_device", "pppcsr_xchg_bulk_build",
     "pppcsr_exchange_bulk_build", "ppcsr_lookup_edges", "ppcsr_lookup_edges_device", "ppcsr_gather_neighbourhoods",
     "ppcsr_gather_neighbourhoods_device", "pppcsr_lookup_edges", "pppcsr_gather_neighbourhoods", "pppcsr_set_option",
+    "pppcsr_bfs", "pppcsr_pagerank",
 ]
 
 NO_EDGE = 0xFFFFFFFF  # PPCSR_NO_EDGE: what lookup_edges reports for a pair that is not an edge
@@ -113,6 +114,8 @@ def load_library(path=None):
     L.pppcsr_lookup_edges.argtypes = [c_vp, c_vp, c_vp, c_u64, c_vp]
     L.pppcsr_gather_neighbourhoods.argtypes = [c_vp, c_vp, c_u64, c_vp, c_vp, c_vp, c_u64, ctypes.POINTER(c_u64)]
     L.pppcsr_set_option.argtypes = [c_vp, ctypes.c_char_p, c_i64]
+    L.pppcsr_bfs.argtypes = [c_vp, c_u32, c_vp, ctypes.POINTER(ctypes.c_double)]
+    L.pppcsr_pagerank.argtypes = [c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_bulk_build.argtypes = [c_vp, c_vp, c_u64, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_bfs.argtypes = [c_vp, c_u32, c_vp, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_pagerank.argtypes = [c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_double)]
@@ -475,6 +478,21 @@ class PPPCSR:
         rc, rows, dests, vals = _gather(self.L.pppcsr_gather_neighbourhoods, self.h, vertices, with_values)
         self._chk(rc)
         return rows, dests, vals
+
+    # consumers on the device over every partition (include/ppcsr.h: pppcsr_bfs / pppcsr_pagerank; global vertex ids)
+    def bfs(self, start, with_ms=False):
+        out = np.empty(self.get_n(), np.uint32)
+        ms = ctypes.c_double(0.0)
+        self._chk(self.L.pppcsr_bfs(self.h, start, out.ctypes.data, ctypes.byref(ms)))
+        return (out, ms.value) if with_ms else out
+
+    def pagerank(self, node_values, with_ms=False):
+        vals = np.ascontiguousarray(node_values, np.float32)
+        assert len(vals) == self.get_n()
+        out = np.empty(len(vals), np.float32)
+        ms = ctypes.c_double(0.0)
+        self._chk(self.L.pppcsr_pagerank(self.h, vals.ctypes.data, out.ctypes.data, ctypes.byref(ms)))
+        return (out, ms.value) if with_ms else out
 
     def set_option(self, key, value):
         """sizes of the batched reads: "query_block", "gather_stage" (include/ppcsr.h: pppcsr_set_option)"""

@@ -614,6 +614,43 @@ int pppcsr_gather_neighbourhoods(pppcsr_t h, const uint32_t *vertices, uint64_t 
   return (want && base > cap) ? PPCSR_STATUS_ERANGE : 0;
 }
 
+// consumers over every partition (bfs.h / pagerank.h with T = PPPCSR): ONE device call over all partitions' arrays, run on the
+// first partition's stream — every partition resident here, all on one device
+static int consumer_parts(pppcsr_t h, std::vector<ppcsr::ConsumerRef> *refs) {
+  for (auto *q : h->parts)
+    if (!q) return bad("partition not resident in this process");
+  for (uint64_t k = 0; k < h->parts.size(); k++)
+    if (h->device[k] != h->device[0]) {
+      g_last_error = "pppcsr consumers: the partitions sit on more than one device";
+      return PPCSR_STATUS_EUNSUPPORTED;
+    }
+  for (uint64_t k = 0; k < h->parts.size(); k++) refs->push_back(ppcsr::ConsumerRef{h->parts[k]->e, (uint32_t)h->distribution[k]});
+  return 0;
+}
+int pppcsr_bfs(pppcsr_t h, uint32_t start, uint32_t *levels, double *device_ms) {
+  PP_CHECK();
+  if (!levels) return bad("bfs: null output");
+  std::vector<ppcsr::ConsumerRef> refs;
+  int rc = consumer_parts(h, &refs);
+  if (rc != 0) return rc;
+  uint64_t n = 0;
+  pppcsr_get_n(h, &n);
+  if (start >= n) return bad("bfs: start vertex out of range");
+  Engine *e = refs[0].e;
+  return ret(e, e->bfs_over(refs.data(), (uint32_t)refs.size(), (uint32_t)n, start, levels, device_ms));
+}
+int pppcsr_pagerank(pppcsr_t h, const float *node_values, float *out, double *device_ms) {
+  PP_CHECK();
+  if (!node_values || !out) return bad("pagerank: null argument");
+  std::vector<ppcsr::ConsumerRef> refs;
+  int rc = consumer_parts(h, &refs);
+  if (rc != 0) return rc;
+  uint64_t n = 0;
+  pppcsr_get_n(h, &n);
+  Engine *e = refs[0].e;
+  return ret(e, e->pagerank_over(refs.data(), (uint32_t)refs.size(), (uint32_t)n, node_values, out, device_ms));
+}
+
 int pppcsr_apply_parts_device(pppcsr_t h, uint64_t first_part, uint64_t n_parts, const ppcsr_op *const *d_ops, const uint64_t *counts) {
   PP_CHECK();
   if (!d_ops || !counts) return bad("null argument");

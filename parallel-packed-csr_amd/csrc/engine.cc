@@ -1951,7 +1951,16 @@ int Engine::gather_neighbourhoods(const uint32_t *vertices, uint64_t k, uint64_t
 //  1.5 K polling workgroups disturb the streaming loads — and was removed; see the git history, "one-pass bulk neighbour scan".)
 int Engine::scan_launch(unsigned long long *d_rows, int *d_dst, uint64_t cap, const float *d_values, float *d_contrib, Op *d_triples,
                         uint32_t src_base) {
-  Impl &p = *p_;
+  uint32_t tile = 0;
+  uint64_t ntiles = 0;
+  int rc = scan_count(this, &tile, &ntiles);
+  if (rc != PPCSR_OK) return rc;
+  scan_write(this, tile, ntiles, d_rows, d_dst, cap, d_values, d_contrib, d_triples, src_base, n());
+  return PPCSR_OK;
+}
+int Engine::scan_count(Engine *part, uint32_t *tile_out, uint64_t *ntiles_out) {
+  Impl &p = *part->p_;
+  const gpu::stream_t st = p_->stream;
   const uint64_t N = p.v.g.N, nchunks = (N + 63) / 64;
   bool fresh_state = (p.scan_nchunks != nchunks);  // the sentinel counts are laid out (and left zeroed) per array size
   p.scan_nchunks = nchunks;
@@ -1967,15 +1976,22 @@ int Engine::scan_launch(unsigned long long *d_rows, int *d_dst, uint64_t cap, co
   uint32_t tile = 256;
   while (tile > 16 && nchunks / tile < p.rb_min_tiles) tile >>= 1;
   const uint64_t ntiles = (nchunks + tile - 1) / tile;
-  int rc = ensure_tiles(ntiles);
-  if (rc != PPCSR_OK) return rc;
-  if (fresh_state) GCHK(gpu::dset(d_cs, 0, nchunks * sizeof(uint32_t), p.stream));  // later scans find it zeroed (k_chunk_counts)
-  GPU_LAUNCH(p.stream, k_chunk_sentinels, grid_for(n(), 256), 256, p.v, d_cs);
-  GPU_LAUNCH(p.stream, k_chunk_counts, ntiles, 256, p.v, d_cs, d_cc, tile, p.d_tiles);
-  GPU_LAUNCH(p.stream, k_scan_tilesums, 1, kTileSumThreads, p.d_tiles, ntiles, p.d_total, (ChainTable *)nullptr, (uint64_t)0, (uint64_t)0, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, 0u);
-  GPU_LAUNCH(p.stream, k_scan_write, ntiles, 256, p.v, (const uint32_t *)d_cc, tile, (const uint32_t *)p.d_tiles, d_rows, d_dst, cap,
-             d_values, d_contrib, d_triples, src_base);
+  int rc = part->ensure_tiles(ntiles);
+  if (rc != PPCSR_OK) return fail(rc, part->last_error());
+  if (fresh_state) GCHK(gpu::dset(d_cs, 0, nchunks * sizeof(uint32_t), st));  // later scans find it zeroed (k_chunk_counts)
+  GPU_LAUNCH(st, k_chunk_sentinels, grid_for(p.v.g.n, 256), 256, p.v, d_cs);
+  GPU_LAUNCH(st, k_chunk_counts, ntiles, 256, p.v, d_cs, d_cc, tile, p.d_tiles);
+  GPU_LAUNCH(st, k_scan_tilesums, 1, kTileSumThreads, p.d_tiles, ntiles, p.d_total, (ChainTable *)nullptr, (uint64_t)0, (uint64_t)0, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, 0u);
+  *tile_out = tile;
+  *ntiles_out = ntiles;
   return PPCSR_OK;
+}
+void Engine::scan_write(Engine *part, uint32_t tile, uint64_t ntiles, unsigned long long *d_rows, int *d_dst, uint64_t cap, const float *d_values,
+                        float *d_contrib, Op *d_triples, uint32_t src_base, uint32_t dest_bound) {
+  Impl &p = *part->p_;
+  const uint32_t *d_cc = reinterpret_cast<const uint32_t *>(p.d_scan_state) + p.scan_nchunks;
+  GPU_LAUNCH(p_->stream, k_scan_write, ntiles, 256, p.v, d_cc, tile, (const uint32_t *)p.d_tiles, d_rows, d_dst, cap, d_values, d_contrib,
+             d_triples, src_base, dest_bound);
 }
 
 // every edge as (src + src_base, dest, value) in array order (= ascending src, then ascending dest) into d_out (device memory,
@@ -2151,15 +2167,47 @@ int Engine::bulk_build_from(const Op *in_ops, bool on_device, uint64_t m, double
 }
 
 // ---- consumers ------------------------------------------------------------------------------------
-// bfs.h:15-36: level of every vertex from `start` (UINT32_MAX = unreachable); one launch per level over the gapped array
+// The consumers run over a table of gapped arrays (pma_scan.h: ConsumerPart) — a PPPCSR's partitions, or this engine alone —
+// on this engine's stream.  The partitions' own streams must be idle first: their last batch may still be in flight.
+// *slots = slots of all arrays; the table goes to the device (one copy, into *d_tab) unless d_tab is null.
+int Engine::consumer_table(const ConsumerRef *parts, uint32_t P, uint32_t total_n, void **d_tab, uint64_t *slots) {
+  Impl &p = *p_;
+  std::vector<ConsumerPart> tab(P + 1);
+  uint64_t chunks = 0, tot = 0;
+  for (uint32_t k = 0; k < P; k++) {
+    const Impl &q = *parts[k].e->p_;
+    if (parts[k].e != this) GCHK(gpu::sync(q.stream));
+    tab[k] = ConsumerPart{q.v.items, q.v.nodes, q.v.g.N, chunks, q.v.g.n, parts[k].first, {0, 0}};
+    chunks += (q.v.g.N + 63) / 64;
+    tot += q.v.g.N;
+  }
+  tab[P] = ConsumerPart{nullptr, nullptr, 0, chunks, 0, total_n, {0, 0}};
+  *slots = tot;
+  if (!d_tab) return PPCSR_OK;
+  GCHK(gpu::dmalloc(d_tab, (P + 1) * sizeof(ConsumerPart)));
+  GCHK(gpu::h2d(*d_tab, tab.data(), (P + 1) * sizeof(ConsumerPart), p.stream));
+  GCHK(gpu::sync(p.stream));
+  return PPCSR_OK;
+}
+
+// bfs.h:15-36: level of every vertex from `start` (UINT32_MAX = unreachable); one launch per level, whatever the number of arrays
 int Engine::bfs(uint32_t start, uint32_t *levels, double *device_ms) {
+  const ConsumerRef self{this, 0};
+  return bfs_over(&self, 1, n(), start, levels, device_ms);
+}
+int Engine::bfs_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t start, uint32_t *levels, double *device_ms) {
   Impl &p = *p_;
   GCHK(gpu::set_device(device_));
-  const uint32_t nn = n();
+  const uint32_t nn = total_n;
   if (start >= nn) return fail(PPCSR_EINVAL, "bfs: start vertex out of range");
   uint32_t *d_lv = nullptr, *d_f0 = nullptr, *d_f1 = nullptr, *d_cnt = nullptr, *d_fb = nullptr, *d_vb = nullptr;
+  ConsumerPart *d_tab = nullptr;
   DevGuard tmpg;
-  tmpg.add(&d_lv); tmpg.add(&d_f0); tmpg.add(&d_f1); tmpg.add(&d_cnt); tmpg.add(&d_fb); tmpg.add(&d_vb);
+  tmpg.add(&d_lv); tmpg.add(&d_f0); tmpg.add(&d_f1); tmpg.add(&d_cnt); tmpg.add(&d_fb); tmpg.add(&d_vb); tmpg.add(&d_tab);
+  uint64_t N = 0;  // slots of all arrays: what one streaming pass reads
+  int rc = consumer_table(parts, P, nn, (void **)&d_tab, &N);
+  if (rc != PPCSR_OK) return rc;
+  const ConsumerPart *tab = d_tab;
   const uint64_t bit_words = ((uint64_t)nn + 63) / 64 * 2;  // frontier / visited bitmaps of the streaming levels
   GCHK(gpu::dmalloc((void **)&d_fb, bit_words * sizeof(uint32_t)));
   GCHK(gpu::dmalloc((void **)&d_vb, bit_words * sizeof(uint32_t)));
@@ -2175,7 +2223,7 @@ int Engine::bfs(uint32_t start, uint32_t *levels, double *device_ms) {
   GCHK(gpu::h2d(d_lv + start, &zero, sizeof(uint32_t), p.stream));
   GCHK(gpu::h2d(d_f0, &start, sizeof(uint32_t), p.stream));
   // Hybrid: a small frontier is expanded one wave per vertex (k_bfs_level, builds the next frontier list); a frontier that
-  // is a sizeable share of the graph is expanded by one streaming pass over the whole gapped array (k_bfs_edges) — its cost
+  // is a sizeable share of the graph is expanded by one streaming pass over every gapped array (k_bfs_edges_bits) — its cost
   // does not depend on hub degrees — and the list is rebuilt only when the frontier becomes small again.
   uint32_t nfront = 1, level = 0;
   uint32_t *cur = d_f0, *nxt = d_f1;
@@ -2186,13 +2234,12 @@ int Engine::bfs(uint32_t start, uint32_t *levels, double *device_ms) {
     return sum;
   };
   bool have_list = true;
-  const uint64_t N = p.v.g.N;
   const uint32_t big = (uint32_t)std::max<uint64_t>(64, (uint64_t)nn / 256);  // frontier size from which the pass is cheaper
   while (nfront > 0) {
     GCHK(gpu::dset(d_cnt, 0, cnt_words * sizeof(uint32_t), p.stream));
     if (nfront >= big) {
       GPU_LAUNCH(p.stream, k_bfs_bits, grid_for(nn, 256, 4096), 256, (const uint32_t *)d_lv, nn, level, d_fb, d_vb);
-      GPU_LAUNCH(p.stream, k_bfs_edges_bits, grid_for((N + 255) / 256, 4, 8192), 256, p.v, level, (const uint32_t *)d_fb, (const uint32_t *)d_vb, d_lv, d_cnt + kBfsStripeWords);
+      GPU_LAUNCH(p.stream, k_bfs_edges_bits, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, level, (const uint32_t *)d_fb, (const uint32_t *)d_vb, d_lv, d_cnt + kBfsStripeWords);
       have_list = false;
     } else {
       if (!have_list) {  // (the pass only counted claims — an upper bound; the list gives the exact frontier)
@@ -2202,7 +2249,7 @@ int Engine::bfs(uint32_t start, uint32_t *levels, double *device_ms) {
         nfront = h_cnt[0];
         GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), p.stream));
       }
-      GPU_LAUNCH(p.stream, k_bfs_level, grid_for(nfront, 4, 16384), 256, p.v, (const uint32_t *)cur, nfront, level, d_lv, nxt, d_cnt);
+      GPU_LAUNCH(p.stream, k_bfs_level, grid_for(nfront, 4, 16384), 256, tab, P, nn, (const uint32_t *)cur, nfront, level, d_lv, nxt, d_cnt);
       have_list = true;
       std::swap(cur, nxt);
     }
@@ -2211,7 +2258,7 @@ int Engine::bfs(uint32_t start, uint32_t *levels, double *device_ms) {
     GCHK(gpu::last_error());
     if (h_cnt[1]) {  // hubs of this level were skipped by the per-vertex kernel: one pass finishes the level
       GPU_LAUNCH(p.stream, k_bfs_bits, grid_for(nn, 256, 4096), 256, (const uint32_t *)d_lv, nn, level, d_fb, d_vb);
-      GPU_LAUNCH(p.stream, k_bfs_edges_bits, grid_for((N + 255) / 256, 4, 8192), 256, p.v, level, (const uint32_t *)d_fb, (const uint32_t *)d_vb, d_lv, d_cnt + kBfsStripeWords);
+      GPU_LAUNCH(p.stream, k_bfs_edges_bits, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, level, (const uint32_t *)d_fb, (const uint32_t *)d_vb, d_lv, d_cnt + kBfsStripeWords);
       GCHK(gpu::d2h(h_cnt.data(), d_cnt, cnt_words * sizeof(uint32_t), p.stream));
       GCHK(gpu::sync(p.stream));
       GCHK(gpu::last_error());
@@ -2253,18 +2300,25 @@ static int sort_pairs_stable(gpu::stream_t st, uint32_t *kin, uint32_t *kout, fl
 }
 
 // pagerank.h:15-29: out[d] = sum over edges (s, d), in ascending s, of node_values[s] / num_neighbors(s).  The bulk scan
-// emits (dest, contribution) per edge in CSR order, a STABLE sort by dest keeps ascending source order inside every
+// emits (dest, contribution) per edge in CSR order — array after array, in partition order, which is ascending global source
+// order because the partitions hold ascending vertex ranges — a STABLE sort by dest keeps ascending source order inside every
 // destination, and one thread per destination adds its run sequentially: the reference's order of fp32 additions.
 int Engine::pagerank(const float *node_values, float *out, double *device_ms) {
+  const ConsumerRef self{this, 0};
+  return pagerank_over(&self, 1, n(), node_values, out, device_ms);
+}
+int Engine::pagerank_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const float *node_values, float *out, double *device_ms) {
   Impl &p = *p_;
   GCHK(gpu::set_device(device_));
-  const uint32_t nn = n();
-  const uint64_t N = p.v.g.N;
+  const uint32_t nn = total_n;
   float *d_val = nullptr, *d_c0 = nullptr, *d_c1 = nullptr, *d_out = nullptr;
   uint32_t *d_k0 = nullptr, *d_k1 = nullptr;
   uint32_t *d_long = nullptr;  // [0]: count, [1..]: destinations with long runs
   DevGuard tmpg;
   tmpg.add(&d_val); tmpg.add(&d_c0); tmpg.add(&d_c1); tmpg.add(&d_out); tmpg.add(&d_k0); tmpg.add(&d_k1); tmpg.add(&d_long);
+  uint64_t N = 0;  // slots of all arrays: room for every edge
+  int rc = consumer_table(parts, P, nn, nullptr, &N);
+  if (rc != PPCSR_OK) return rc;
   GCHK(gpu::dmalloc((void **)&d_val, (uint64_t)nn * sizeof(float)));
   GCHK(gpu::dmalloc((void **)&d_out, (uint64_t)nn * sizeof(float)));
   GCHK(gpu::dmalloc((void **)&d_k0, N * sizeof(uint32_t)));
@@ -2273,12 +2327,28 @@ int Engine::pagerank(const float *node_values, float *out, double *device_ms) {
   GCHK(gpu::dmalloc((void **)&d_c1, N * sizeof(float)));
   GCHK(gpu::h2d(d_val, node_values, (uint64_t)nn * sizeof(float), p.stream));
   p.timer.start(p.stream);
-  int rc = scan_launch(nullptr, reinterpret_cast<int *>(d_k0), N, d_val, d_c0);
-  if (rc != PPCSR_OK) return rc;
-  GCHK(gpu::d2h(p.h_total, p.d_total, sizeof(unsigned long long), p.stream));
+  // every array's edge count first (its place in the shared key / contribution arrays), then the contribution passes; the
+  // first array's pass needs no count (it starts at 0) and goes out with its counts, as the one-engine call always did
+  std::vector<uint32_t> tile(P);
+  std::vector<uint64_t> ntiles(P);
+  for (uint32_t k = 0; k < P; k++) {
+    rc = scan_count(parts[k].e, &tile[k], &ntiles[k]);
+    if (rc != PPCSR_OK) return rc;
+    const Impl &q = *parts[k].e->p_;
+    if (k == 0)
+      scan_write(parts[0].e, tile[0], ntiles[0], nullptr, reinterpret_cast<int *>(d_k0), q.v.g.N, d_val + parts[0].first, d_c0, nullptr, 0, nn);
+    GCHK(gpu::d2h(q.h_total, q.d_total, sizeof(unsigned long long), p.stream));
+  }
   GCHK(gpu::sync(p.stream));
   GCHK(gpu::last_error());
-  const uint64_t m = *p.h_total;
+  uint64_t m = 0;
+  for (uint32_t k = 0; k < P; k++) {
+    const uint64_t mk = *parts[k].e->p_->h_total;
+    if (k > 0)
+      scan_write(parts[k].e, tile[k], ntiles[k], nullptr, reinterpret_cast<int *>(d_k0 + m), mk, d_val + parts[k].first, d_c0 + m, nullptr,
+                 0, nn);
+    m += mk;
+  }
   if (m) {
     unsigned bits = 1;  // keys are clamped to [0, n]
     while (bits < 32 && ((uint64_t)nn >> bits) != 0) bits++;

@@ -13,6 +13,13 @@ namespace ppcsr {
 struct View;  // pma_device.h
 struct Edge;
 
+// one partition of a consumer call over several engines (bfs_over / pagerank_over): its engine and its first global vertex
+class Engine;
+struct ConsumerRef {
+  Engine *e;
+  uint32_t first;
+};
+
 struct EngineStats {
   uint64_t N, n;
   int logN, H;
@@ -59,6 +66,11 @@ class Engine {
   int bulk_build_device(const Op *d_adds, uint64_t m, double *device_ms);  // the same, adds already in HBM (pppcsr_repartition)
   int bfs(uint32_t start, uint32_t *levels, double *device_ms);
   int pagerank(const float *node_values, float *out, double *device_ms);
+  // the same over P engines that hold consecutive vertex ranges of one graph of total_n vertices (a PPPCSR's partitions, in
+  // partition order; edges stored with a local src and a global dest).  Runs on THIS engine's stream and device, which every
+  // partition must share; bfs / pagerank are the one-partition case.  Writes nothing to any partition's graph state.
+  int bfs_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t start, uint32_t *levels, double *device_ms);
+  int pagerank_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const float *node_values, float *out, double *device_ms);
   int export_state(Edge *items, Node *nodes);
   int check_invariants(uint64_t *bad);  // leafcnt == recount(items)
   int stats(EngineStats *out);
@@ -101,6 +113,12 @@ class Engine {
   int gather_prepare(const uint32_t *q, uint64_t kb, uint64_t *kt, uint64_t *C, uint64_t *T);
   int scan_launch(unsigned long long *d_rows, int *d_dst, uint64_t cap, const float *d_values = nullptr, float *d_contrib = nullptr,
                   Op *d_triples = nullptr, uint32_t src_base = 0);
+  // the bulk scan of `part`'s array in two halves, launched on THIS engine's stream with part's scratch: the chunk counts and
+  // tile sums (edge total in part's d_total), then the writing pass
+  int scan_count(Engine *part, uint32_t *tile, uint64_t *ntiles);
+  int consumer_table(const ConsumerRef *parts, uint32_t P, uint32_t total_n, void **d_tab, uint64_t *slots);
+  void scan_write(Engine *part, uint32_t tile, uint64_t ntiles, unsigned long long *d_rows, int *d_dst, uint64_t cap, const float *d_values,
+                  float *d_contrib, Op *d_triples, uint32_t src_base, uint32_t dest_bound);
 
  public:
   struct Impl;

@@ -114,11 +114,13 @@ PMA_KERNEL void k_chunk_counts(View v, uint32_t *chunk_sent, uint32_t *chunkcnt,
 // bulk neighbour scan (CSR export), final streaming pass: one workgroup per tile of chunks.  The tile's chunk counts are
 // scanned in LDS (offset = scanned tile sum + in-tile prefix), then every wave streams its chunks — four in flight —
 // writing dests in array order == CSR order and the row offsets at the sentinels.
-// (contrib != nullptr: also emit, per edge, node_values[src] / num_neighbors(src) — the PageRank push of pagerank.h:21;
+// (contrib != nullptr: also emit, per edge, node_values[src] / num_neighbors(src) — the PageRank push of pagerank.h:21 — with
+//  dests at or above dest_bound (the vertex count of the whole graph) written as dest_bound;
 //  triples != nullptr: emit (src + src_base, dest, value) per edge instead of / besides dests)
 PMA_KERNEL void k_scan_write(View v, const uint32_t *__restrict__ chunkcnt, uint32_t tile_chunks, const uint32_t *__restrict__ tile_excl,
                              unsigned long long *__restrict__ row_offsets, int *__restrict__ dests, uint64_t cap,
-                             const float *__restrict__ node_values, float *__restrict__ contrib, Op *__restrict__ triples, uint32_t src_base) {
+                             const float *__restrict__ node_values, float *__restrict__ contrib, Op *__restrict__ triples, uint32_t src_base,
+                             uint32_t dest_bound) {
   PMA_SHARED uint32_t pre[256];
   PMA_SHARED uint32_t wsum[4];
   const int lane = wv::lane(), w = wv::wave_in_block();
@@ -165,7 +167,7 @@ PMA_KERNEL void k_scan_write(View v, const uint32_t *__restrict__ chunkcnt, uint
       if (live && o < cap && dests != nullptr) {
         dests[o] = (int)e[q].dest;
         if (contrib != nullptr) {
-          if (e[q].dest >= v.g.n) dests[o] = (int)v.g.n;  // (the reference would write out of bounds; keeps the sort keys short)
+          if (e[q].dest >= dest_bound) dests[o] = (int)dest_bound;  // (the reference would write out of bounds; keeps the sort keys short)
           const uint32_t sv = e[q].src;
           contrib[o] = (sv < v.g.n) ? node_values[sv] / (float)v.nodes[sv].num_neighbors : 0.0f;
         }
@@ -270,18 +272,61 @@ PMA_KERNEL void k_bb_edges(View v, const unsigned long long *keys, const uint32_
 }
 
 // ---- graph-algorithm consumers over the gapped array (reference: src/utility/bfs.h, src/utility/pagerank.h) -----------
-// BFS, one level per launch: one wave per frontier vertex walks its slot range (beginning, end) 64 slots at a time, skips
-// nulls, claims unvisited neighbours with a compare-and-swap on their level and appends them to the next frontier (one
-// atomic per wave per 64 slots).  Levels are unique, so the result equals the reference's queue-based walk exactly.
+// The consumers run over a TABLE of gapped arrays: the partitions of a PPPCSR (vertex ranges [first, first + n), edges stored
+// with a partition-local src and a global dest), or one engine as a one-entry table.  Vertex ids in levels[], the frontier
+// lists and bitmaps are global.  The table has P + 1 entries: entry P only closes the two searchable columns (first = the
+// vertex count of the whole graph, chunk0 = the number of 64-slot chunks of all arrays).
+struct ConsumerPart {
+  const Edge *items;
+  const Node *nodes;
+  uint64_t N;       // slots
+  uint64_t chunk0;  // 64-slot chunks of the arrays before this one
+  uint32_t n;       // vertices
+  uint32_t first;   // global id of vertex 0
+  uint32_t pad[2];
+};
+static_assert(sizeof(ConsumerPart) == 48, "consumer table entry");
+// owner of global vertex u (wave-uniform): the last entry whose first vertex is <= u — an empty partition shares its first
+// vertex with the next one, which is the owner (the rule of PPPCSR.cpp:58-66)
+PMA_DEV uint32_t cp_owner(const ConsumerPart *tab, uint32_t P, uint32_t u) {
+  uint32_t lo = 0, hi = P - 1;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1) >> 1;
+    if (tab[mid].first <= u) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+// array that holds chunk ch of the concatenated chunk space (wave-uniform)
+PMA_DEV uint32_t cp_chunk_owner(const ConsumerPart *tab, uint32_t P, uint64_t ch) {
+  uint32_t lo = 0, hi = P - 1;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1) >> 1;
+    if (tab[mid].chunk0 <= ch) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+// BFS, one level per launch: one wave per frontier vertex finds the vertex's array, walks its slot range (beginning, end) 64
+// slots at a time, skips nulls, claims unvisited neighbours with a compare-and-swap on their level and appends them to the next
+// frontier (one atomic per wave per 64 slots).  Levels are unique, so the result equals the reference's queue-based walk exactly.
 constexpr uint64_t kBfsWaveSlots = 4096;  // longest slot range one wave walks on its own
-PMA_KERNEL void k_bfs_level(View v, const uint32_t *front, uint32_t nfront, uint32_t level, uint32_t *levels, uint32_t *next,
-                            uint32_t *next_count) {
+PMA_KERNEL void k_bfs_level(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, const uint32_t *front, uint32_t nfront,
+                            uint32_t level, uint32_t *levels, uint32_t *next, uint32_t *next_count) {
   const int lane = wv::lane();
   const uint64_t wstride = (uint64_t)wv::grid_dim() * (wv::block_dim() >> 6);
+  const Edge *const items0 = tab[0].items;  // (one array: no search, no table look-up inside the loop)
+  const Node *const nodes0 = tab[0].nodes;
   for (uint64_t f = (uint64_t)wv::block_idx() * (wv::block_dim() >> 6) + wv::wave_in_block(); f < nfront; f += wstride) {
-    const uint32_t u = front[f];
-    const Node nd = v.nodes[u];
-    if ((uint64_t)nd.end - (uint64_t)nd.beginning > kBfsWaveSlots) {  // a hub: leave it to one streaming pass (k_bfs_edges)
+    const uint32_t u = wv::uni(front[f]);
+    const Edge *items = items0;
+    Node nd;
+    if (P == 1) {
+      nd = nodes0[u];
+    } else {
+      const uint32_t k = cp_owner(tab, P, u);
+      items = tab[k].items;
+      nd = tab[k].nodes[u - tab[k].first];
+    }
+    if ((uint64_t)nd.end - (uint64_t)nd.beginning > kBfsWaveSlots) {  // a hub: leave it to one streaming pass (k_bfs_edges_bits)
       if (lane == 0) next_count[1] = 1u;
       continue;
     }
@@ -289,11 +334,11 @@ PMA_KERNEL void k_bfs_level(View v, const uint32_t *front, uint32_t nfront, uint
       const uint64_t s = base + (uint64_t)lane;
       uint32_t val = 0, dst = 0;
       if (s < (uint64_t)nd.end) {
-        val = v.items[s].value;
-        dst = v.items[s].dest;
+        val = items[s].value;
+        dst = items[s].dest;
       }
       bool won = false;
-      if (val != 0 && dst < v.g.n && levels[dst] == kMax) won = wv::atomic_cas_u32(&levels[dst], kMax, level + 1u) == kMax;
+      if (val != 0 && dst < n && levels[dst] == kMax) won = wv::atomic_cas_u32(&levels[dst], kMax, level + 1u) == kMax;
       const uint64_t m = wv::ballot(won);
       if (m) {
         uint32_t b = 0;
@@ -347,22 +392,40 @@ PMA_KERNEL void k_bfs_bits(const uint32_t *levels, uint32_t n, uint32_t level, u
     }
   }
 }
+// (The chunk space is the concatenation of the table's arrays: each chunk finds its array by a wave-uniform search of the chunk
+// prefix — with one array, a search of no steps — and its edges get global sources, src + first.)
 constexpr uint32_t kBfsStripes = 64, kBfsStripeWords = 32;
-PMA_KERNEL void k_bfs_edges_bits(View v, uint32_t level, const uint32_t *__restrict__ front_bits, const uint32_t *__restrict__ visited_bits,
-                                 uint32_t *levels, uint32_t *found) {
+PMA_KERNEL void k_bfs_edges_bits(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, uint32_t level,
+                                 const uint32_t *__restrict__ front_bits, const uint32_t *__restrict__ visited_bits, uint32_t *levels,
+                                 uint32_t *found) {
   const int lane = wv::lane();
-  const uint64_t N = v.g.N, nchunks = (N + 63) / 64;
+  const uint64_t nchunks = tab[P].chunk0;
   const uint64_t wstride = (uint64_t)wv::grid_dim() * (wv::block_dim() >> 6);
-  const uint32_t n = v.g.n;
+  const Edge *const items0 = tab[0].items;  // (one array: no search, no table look-up inside the loop)
+  const uint64_t N0 = tab[0].N;
+  const uint32_t n0 = tab[0].n;
   uint32_t mine = 0;
   constexpr int kB = 4;
-  for (uint64_t ch0 = ((uint64_t)wv::block_idx() * (wv::block_dim() >> 6) + wv::wave_in_block()) * kB; ch0 < nchunks; ch0 += wstride * kB) {
+  for (uint64_t ch0 = wv::uni(((uint64_t)wv::block_idx() * (wv::block_dim() >> 6) + wv::wave_in_block()) * kB); ch0 < nchunks;
+       ch0 += wstride * kB) {
     Edge e[kB];
+    uint32_t first[kB], pn[kB];
 #pragma unroll
     for (int b = 0; b < kB; b++) {
-      const uint64_t s = (ch0 + b) * 64 + (uint64_t)lane;
+      const Edge *items = items0;
+      uint64_t s = (ch0 + b) * 64 + (uint64_t)lane, N = N0;
+      first[b] = 0;
+      pn[b] = n0;
+      if (P > 1 && ch0 + b < nchunks) {
+        const uint32_t k = cp_chunk_owner(tab, P, ch0 + b);
+        items = tab[k].items;
+        s -= tab[k].chunk0 * 64;
+        N = tab[k].N;
+        first[b] = tab[k].first;
+        pn[b] = tab[k].n;
+      }
       e[b] = null_edge();
-      if (s + 1 < N) e[b] = v.items[s];  // (slot N-1 is never part of a neighbourhood)
+      if (ch0 + b < nchunks && s + 1 < N) e[b] = items[s];  // (slot N-1 is never part of a neighbourhood)
     }
     // Four phases, each over all kB chunks, so that the kB gathers of a phase are in flight TOGETHER (written one chunk after
     // the other, the levels[] load of chunk b+1 waits for the store of chunk b: they may alias).
@@ -370,8 +433,9 @@ PMA_KERNEL void k_bfs_edges_bits(View v, uint32_t level, const uint32_t *__restr
     uint32_t bit[kB], old[kB];
 #pragma unroll
     for (int b = 0; b < kB; b++) {
-      const bool live = e[b].value != 0 && !is_sentinel(e[b]) && e[b].src < n && e[b].dest < n;
-      hit[b] = live && ((front_bits[e[b].src >> 5] >> (e[b].src & 31u)) & 1u);
+      const bool live = e[b].value != 0 && !is_sentinel(e[b]) && e[b].src < pn[b] && e[b].dest < n;
+      const uint32_t src = e[b].src + first[b];
+      hit[b] = live && ((front_bits[src >> 5] >> (src & 31u)) & 1u);
       bit[b] = 1u << (e[b].dest & 31u);
     }
 #pragma unroll

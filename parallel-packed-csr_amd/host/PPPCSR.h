@@ -96,6 +96,31 @@ class PPPCSR {
     auto p = get_partiton(id);
     return partitions[p]->getNode(id - (int)distribution[p]);
   }
+  // the reference's consumers with T = PPPCSR (src/utility/bfs.h, pagerank.h) on the device over every partition's array
+  // (pppcsr_bfs / pppcsr_pagerank; global vertex ids).  false: the partitions sit on more than one device
+  // (PPCSR_STATUS_EUNSUPPORTED) — host/bfs.h and host/pagerank.h then run the generic host template
+  bool bfs(uint32_t start_node, std::vector<uint32_t> *levels) {
+    std::lock_guard<std::mutex> g(engine_mu_);
+    flush_locked();
+    uint64_t n = 0;
+    check(pppcsr_get_n(h_, &n));
+    levels->assign(n, 0);
+    const int rc = pppcsr_bfs(h_, start_node, levels->data(), nullptr);
+    if (rc == PPCSR_STATUS_EUNSUPPORTED) return false;
+    check(rc);
+    return true;
+  }
+  bool pagerank(const std::vector<float> &node_values, std::vector<float> *out) {
+    std::lock_guard<std::mutex> g(engine_mu_);
+    flush_locked();
+    uint64_t n = 0;
+    check(pppcsr_get_n(h_, &n));
+    out->assign(n, 0.0f);
+    const int rc = pppcsr_pagerank(h_, node_values.data(), out->data(), nullptr);
+    if (rc == PPCSR_STATUS_EUNSUPPORTED) return false;
+    check(rc);
+    return true;
+  }
   void registerThread(int par) { partitions[par]->edges.global_lock->registerThread(); }
   void unregisterThread(int par) { partitions[par]->edges.global_lock->unregisterThread(); }
 

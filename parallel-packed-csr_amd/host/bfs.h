@@ -1,12 +1,14 @@
 // Drop-in for the reference's src/utility/bfs.h (template bfs(graph, start_node), bfs.h:15-36).
-// For the engine-backed PCSR the walk runs on the GPU over the gapped array (ppcsr_bfs); any other graph type gets the
-// reference's host algorithm: a queue-based walk through get_neighbourhood().
+// For the engine-backed PCSR the walk runs on the GPU over the gapped array (ppcsr_bfs), for PPPCSR over every partition's
+// array (pppcsr_bfs; partitions on several devices take the template); any other graph type gets the reference's host
+// algorithm: a queue-based walk through get_neighbourhood().
 #ifndef PPCSR_HOST_BFS_H
 #define PPCSR_HOST_BFS_H
 #include <cstdint>
 #include <vector>
 
 #include "PCSR.h"
+#include "PPPCSR.h"
 
 inline std::vector<uint32_t> bfs(PCSR &graph, uint32_t start_node) { return graph.bfs(start_node); }
 
@@ -24,5 +26,11 @@ std::vector<uint32_t> bfs(T &graph, uint32_t start_node) {
       }
   }
   return level;
+}
+
+inline std::vector<uint32_t> bfs(PPPCSR &graph, uint32_t start_node) {
+  std::vector<uint32_t> level;
+  if (graph.bfs(start_node, &level)) return level;
+  return bfs<PPPCSR>(graph, start_node);
 }
 #endif
