@@ -124,6 +124,21 @@ int ppcsr_bulk_build(ppcsr_t h, const ppcsr_op *adds, uint64_t n, double *device
  *   reference template's (node_values, out: n entries).  device_ms (may be NULL): device time of the traversal. */
 int ppcsr_bfs(ppcsr_t h, uint32_t start, uint32_t *levels, double *device_ms);
 int ppcsr_pagerank(ppcsr_t h, const float *node_values, float *out, double *device_ms);
+/* Two consumers that use the edge values / the edges as undirected pairs, over the edge set ppcsr_bfs walks (live slots of
+ * every vertex's (beginning, end), slot N - 1 excluded, destinations >= n skipped).  The weight of an edge is its stored
+ * value (a duplicate add has overwritten it: the last add wins).
+ * sssp — dist[v] = the smallest sum of values over directed paths from `start` to v; dist[start] = 0; PPCSR_NO_PATH when
+ *   there is none (dist: n entries).  Distances are 64-bit and cannot overflow: a value lies in [1, 2^32 - 2] (0 is the null
+ *   slot, 0xFFFFFFFF the sentinel precondition) and a simple path has at most n - 1 <= 2^32 - 1 edges, so a distance is
+ *   below (2^32 - 1)(2^32 - 2) < 2^64 - 1 = PPCSR_NO_PATH.  Nothing saturates or is checked at run time.
+ * components — weakly connected components: labels[v] = the smallest vertex id of v's component, edges taken as
+ *   undirected; an isolated vertex labels itself (labels: n entries).  The number of components is the count of
+ *   labels[v] == v.
+ * Both results are unique.  Same contract as bfs: synchronous, write nothing to the graph, device_ms may be NULL.
+ * EINVAL: null handle or output, start >= n. */
+#define PPCSR_NO_PATH 0xFFFFFFFFFFFFFFFFull
+int ppcsr_sssp(ppcsr_t h, uint32_t start, uint64_t *dist, double *device_ms);
+int ppcsr_components(ppcsr_t h, uint32_t *labels, double *device_ms);
 /* raw state for parity checks: items[N], nodes[n] exactly as the reference holds them (PCSR.h:67,128) */
 int ppcsr_export_state(ppcsr_t h, ppcsr_edge *items, ppcsr_node *nodes);
 int ppcsr_stats(ppcsr_t h, ppcsr_stats_t *out);
@@ -205,6 +220,13 @@ int pppcsr_set_option(pppcsr_t h, const char *key, int64_t value);
  * EUNSUPPORTED: the partitions sit on more than one device (pppcsr_create with several devices) — run the host template. */
 int pppcsr_bfs(pppcsr_t h, uint32_t start, uint32_t *levels, double *device_ms);
 int pppcsr_pagerank(pppcsr_t h, const float *node_values, float *out, double *device_ms);
+/* ppcsr_sssp / ppcsr_components over the GLOBAL vertex ids (dist, labels: pppcsr_get_n entries), one device call over every
+ * partition's array: the results do not depend on the partitioning.  Same contract as pppcsr_bfs: synchronous; waits for
+ * every partition's stream, runs on the first partition's; writes nothing to any partition.  EINVAL: null handle or output,
+ * start >= pppcsr_get_n, or a partition not resident in this process.  EUNSUPPORTED: the partitions sit on more than one
+ * device — there is no host form of these two calls. */
+int pppcsr_sssp(pppcsr_t h, uint32_t start, uint64_t *dist, double *device_ms);
+int pppcsr_components(pppcsr_t h, uint32_t *labels, double *device_ms);
 /* bucket a host stream by owner (stable: per-partition order == stream order, src made partition-local as in
  * PPPCSR.cpp:46-52) and apply each bucket on its partition's GPU */
 int pppcsr_apply_batch(pppcsr_t h, const ppcsr_op *ops, uint64_t n);

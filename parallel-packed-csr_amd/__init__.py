@@ -52,9 +52,10 @@ EXPORTED = [
     "pppcsr_xchg_set_num_neighbors", "pppcsr_exchange_set_num_neighbors", "pppcsr_bulk_build_device", "pppcsr_xchg_bulk_build",
     "pppcsr_exchange_bulk_build", "ppcsr_lookup_edges", "ppcsr_lookup_edges_device", "ppcsr_gather_neighbourhoods",
     "ppcsr_gather_neighbourhoods_device", "pppcsr_lookup_edges", "pppcsr_gather_neighbourhoods", "pppcsr_set_option",
-    "pppcsr_bfs", "pppcsr_pagerank",
+    "pppcsr_bfs", "pppcsr_pagerank", "ppcsr_sssp", "ppcsr_components", "pppcsr_sssp", "pppcsr_components",
 ]
 
+NO_PATH = 0xFFFFFFFFFFFFFFFF  # PPCSR_NO_PATH: what sssp reports for a vertex no path reaches
 NO_EDGE = 0xFFFFFFFF  # PPCSR_NO_EDGE: what lookup_edges reports for a pair that is not an edge
 
 _LIBS = {}
@@ -116,6 +117,10 @@ def load_library(path=None):
     L.pppcsr_set_option.argtypes = [c_vp, ctypes.c_char_p, c_i64]
     L.pppcsr_bfs.argtypes = [c_vp, c_u32, c_vp, ctypes.POINTER(ctypes.c_double)]
     L.pppcsr_pagerank.argtypes = [c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_double)]
+    for name in ("ppcsr_sssp", "pppcsr_sssp"):
+        getattr(L, name).argtypes = [c_vp, c_u32, c_vp, ctypes.POINTER(ctypes.c_double)]
+    for name in ("ppcsr_components", "pppcsr_components"):
+        getattr(L, name).argtypes = [c_vp, c_vp, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_bulk_build.argtypes = [c_vp, c_vp, c_u64, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_bfs.argtypes = [c_vp, c_u32, c_vp, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_pagerank.argtypes = [c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_double)]
@@ -323,6 +328,20 @@ class PCSR:
         self._chk(self.L.ppcsr_pagerank(self.h, vals.ctypes.data, out.ctypes.data, ctypes.byref(ms)))
         return (out, ms.value) if with_ms else out
 
+    def sssp(self, start, with_ms=False):
+        """distances over the edge values from `start` (uint64, NO_PATH where no path leads)"""
+        out = np.empty(self.get_n(), np.uint64)
+        ms = ctypes.c_double(0.0)
+        self._chk(self.L.ppcsr_sssp(self.h, start, out.ctypes.data, ctypes.byref(ms)))
+        return (out, ms.value) if with_ms else out
+
+    def components(self, with_ms=False):
+        """weakly connected components: the smallest vertex id of every vertex's component (uint32)"""
+        out = np.empty(self.get_n(), np.uint32)
+        ms = ctypes.c_double(0.0)
+        self._chk(self.L.ppcsr_components(self.h, out.ctypes.data, ctypes.byref(ms)))
+        return (out, ms.value) if with_ms else out
+
     def geometry(self):
         N, lg, H = c_u64(), c_int(), c_int()
         self._chk(self.L.ppcsr_geometry(self.h, ctypes.byref(N), ctypes.byref(lg), ctypes.byref(H)))
@@ -492,6 +511,20 @@ class PPPCSR:
         out = np.empty(len(vals), np.float32)
         ms = ctypes.c_double(0.0)
         self._chk(self.L.pppcsr_pagerank(self.h, vals.ctypes.data, out.ctypes.data, ctypes.byref(ms)))
+        return (out, ms.value) if with_ms else out
+
+    def sssp(self, start, with_ms=False):
+        """distances over the edge values from `start` (uint64, NO_PATH where no path leads)"""
+        out = np.empty(self.get_n(), np.uint64)
+        ms = ctypes.c_double(0.0)
+        self._chk(self.L.pppcsr_sssp(self.h, start, out.ctypes.data, ctypes.byref(ms)))
+        return (out, ms.value) if with_ms else out
+
+    def components(self, with_ms=False):
+        """weakly connected components: the smallest vertex id of every vertex's component (uint32)"""
+        out = np.empty(self.get_n(), np.uint32)
+        ms = ctypes.c_double(0.0)
+        self._chk(self.L.pppcsr_components(self.h, out.ctypes.data, ctypes.byref(ms)))
         return (out, ms.value) if with_ms else out
 
     def set_option(self, key, value):

@@ -162,6 +162,16 @@ int ppcsr_pagerank(ppcsr_t h, const float *node_values, float *out, double *devi
   if (!node_values || !out) return bad("pagerank: null argument");
   return ret(h->e, h->e->pagerank(node_values, out, device_ms));
 }
+int ppcsr_sssp(ppcsr_t h, uint32_t start, uint64_t *dist, double *device_ms) {
+  H_CHECK();
+  if (!dist) return bad("sssp: null output");
+  return ret(h->e, h->e->sssp(start, dist, device_ms));
+}
+int ppcsr_components(ppcsr_t h, uint32_t *labels, double *device_ms) {
+  H_CHECK();
+  if (!labels) return bad("components: null output");
+  return ret(h->e, h->e->components(labels, device_ms));
+}
 int ppcsr_export_state(ppcsr_t h, ppcsr_edge *items, ppcsr_node *nodes) {
   H_CHECK();
   return ret(h->e, h->e->export_state(reinterpret_cast<ppcsr::Edge *>(items), reinterpret_cast<ppcsr::Node *>(nodes)));
@@ -649,6 +659,29 @@ int pppcsr_pagerank(pppcsr_t h, const float *node_values, float *out, double *de
   pppcsr_get_n(h, &n);
   Engine *e = refs[0].e;
   return ret(e, e->pagerank_over(refs.data(), (uint32_t)refs.size(), (uint32_t)n, node_values, out, device_ms));
+}
+int pppcsr_sssp(pppcsr_t h, uint32_t start, uint64_t *dist, double *device_ms) {
+  PP_CHECK();
+  if (!dist) return bad("sssp: null output");
+  std::vector<ppcsr::ConsumerRef> refs;
+  int rc = consumer_parts(h, &refs);
+  if (rc != 0) return rc;
+  uint64_t n = 0;
+  pppcsr_get_n(h, &n);
+  if (start >= n) return bad("sssp: start vertex out of range");
+  Engine *e = refs[0].e;
+  return ret(e, e->sssp_over(refs.data(), (uint32_t)refs.size(), (uint32_t)n, start, dist, device_ms));
+}
+int pppcsr_components(pppcsr_t h, uint32_t *labels, double *device_ms) {
+  PP_CHECK();
+  if (!labels) return bad("components: null output");
+  std::vector<ppcsr::ConsumerRef> refs;
+  int rc = consumer_parts(h, &refs);
+  if (rc != 0) return rc;
+  uint64_t n = 0;
+  pppcsr_get_n(h, &n);
+  Engine *e = refs[0].e;
+  return ret(e, e->components_over(refs.data(), (uint32_t)refs.size(), (uint32_t)n, labels, device_ms));
 }
 
 int pppcsr_apply_parts_device(pppcsr_t h, uint64_t first_part, uint64_t n_parts, const ppcsr_op *const *d_ops, const uint64_t *counts) {

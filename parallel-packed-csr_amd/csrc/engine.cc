@@ -2274,6 +2274,134 @@ int Engine::bfs_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uin
   return PPCSR_OK;
 }
 
+// Shortest paths over the edge values (pma_paths.h).  The hybrid of bfs_over, with rounds in place of levels: stamp[] holds
+// the round for which a vertex was last made active, so the round's bitmap and list come from k_bfs_bits / k_bfs_collect.
+// One host read per round; the call ends when a round lowers no distance.
+int Engine::sssp(uint32_t start, uint64_t *dist, double *device_ms) {
+  const ConsumerRef self{this, 0};
+  return sssp_over(&self, 1, n(), start, dist, device_ms);
+}
+int Engine::sssp_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t start, uint64_t *dist, double *device_ms) {
+  Impl &p = *p_;
+  GCHK(gpu::set_device(device_));
+  const uint32_t nn = total_n;
+  if (start >= nn) return fail(PPCSR_EINVAL, "sssp: start vertex out of range");
+  unsigned long long *d_dist = nullptr;
+  uint32_t *d_st = nullptr, *d_f0 = nullptr, *d_f1 = nullptr, *d_cnt = nullptr, *d_ab = nullptr, *d_vb = nullptr;
+  ConsumerPart *d_tab = nullptr;
+  DevGuard tmpg;
+  tmpg.add(&d_dist); tmpg.add(&d_st); tmpg.add(&d_f0); tmpg.add(&d_f1); tmpg.add(&d_cnt); tmpg.add(&d_ab); tmpg.add(&d_vb); tmpg.add(&d_tab);
+  uint64_t N = 0;  // slots of all arrays: what one streaming pass reads
+  int rc = consumer_table(parts, P, nn, (void **)&d_tab, &N);
+  if (rc != PPCSR_OK) return rc;
+  const ConsumerPart *tab = d_tab;
+  const uint64_t bit_words = ((uint64_t)nn + 63) / 64 * 2;  // active bitmap of the streaming rounds (d_vb: k_bfs_bits' second output, unused)
+  GCHK(gpu::dmalloc((void **)&d_ab, bit_words * sizeof(uint32_t)));
+  GCHK(gpu::dmalloc((void **)&d_vb, bit_words * sizeof(uint32_t)));
+  GCHK(gpu::dmalloc((void **)&d_dist, (uint64_t)nn * sizeof(unsigned long long)));
+  GCHK(gpu::dmalloc((void **)&d_st, (uint64_t)nn * sizeof(uint32_t)));
+  GCHK(gpu::dmalloc((void **)&d_f0, (uint64_t)nn * sizeof(uint32_t)));
+  GCHK(gpu::dmalloc((void **)&d_f1, (uint64_t)nn * sizeof(uint32_t)));
+  // [0] vertices made active, [1] a hub was left to the streaming pass, [kBfsStripeWords...] the streaming pass's striped count
+  constexpr uint32_t cnt_words = (kBfsStripes + 1) * kBfsStripeWords;
+  GCHK(gpu::dmalloc((void **)&d_cnt, cnt_words * sizeof(uint32_t)));
+  p.timer.start(p.stream);
+  GCHK(gpu::dset(d_dist, 0xFF, (uint64_t)nn * sizeof(unsigned long long), p.stream));
+  GCHK(gpu::dset(d_st, 0, (uint64_t)nn * sizeof(uint32_t), p.stream));
+  const unsigned long long zero = 0;
+  uint32_t round = 1;  // (stamp 0: never active)
+  GCHK(gpu::h2d(d_dist + start, &zero, sizeof(zero), p.stream));
+  GCHK(gpu::h2d(d_st + start, &round, sizeof(uint32_t), p.stream));
+  GCHK(gpu::h2d(d_f0, &start, sizeof(uint32_t), p.stream));
+  uint32_t nact = 1;
+  uint32_t *cur = d_f0, *nxt = d_f1;
+  std::vector<uint32_t> h_cnt(cnt_words, 0);
+  auto striped = [&]() {
+    uint32_t sum = 0;
+    for (uint32_t k = 1; k <= kBfsStripes; k++) sum += h_cnt[k * kBfsStripeWords];
+    return sum;
+  };
+  auto stream_round = [&]() {
+    GPU_LAUNCH(p.stream, k_bfs_bits, grid_for(nn, 256, 4096), 256, (const uint32_t *)d_st, nn, round, d_ab, d_vb);
+    GPU_LAUNCH(p.stream, k_sssp_edges, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, round, (const uint32_t *)d_ab, d_dist, d_st, d_cnt + kBfsStripeWords);
+  };
+  bool have_list = true;
+  const uint32_t big = (uint32_t)std::max<uint64_t>(64, (uint64_t)nn / 256);  // active-set size from which the pass is cheaper (as in bfs_over)
+  while (nact > 0) {
+    GCHK(gpu::dset(d_cnt, 0, cnt_words * sizeof(uint32_t), p.stream));
+    if (nact >= big) {
+      stream_round();
+      have_list = false;
+    } else {
+      if (!have_list) {  // (both passes count the vertices they activate exactly; the list itself comes from the stamps)
+        GPU_LAUNCH(p.stream, k_bfs_collect, grid_for(nn, 256), 256, (const uint32_t *)d_st, nn, round, cur, d_cnt);
+        GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), p.stream));
+      }
+      GPU_LAUNCH(p.stream, k_sssp_relax, grid_for(nact, 4, 16384), 256, tab, P, nn, (const uint32_t *)cur, nact, round, d_dist, d_st, nxt, d_cnt);
+      have_list = true;
+      std::swap(cur, nxt);
+    }
+    GCHK(gpu::d2h(h_cnt.data(), d_cnt, cnt_words * sizeof(uint32_t), p.stream));
+    GCHK(gpu::sync(p.stream));
+    GCHK(gpu::last_error());
+    if (h_cnt[1]) {  // hubs of this round were skipped by the per-vertex kernel: one pass relaxes their edges
+      stream_round();
+      GCHK(gpu::d2h(h_cnt.data(), d_cnt, cnt_words * sizeof(uint32_t), p.stream));
+      GCHK(gpu::sync(p.stream));
+      GCHK(gpu::last_error());
+      have_list = false;
+    }
+    nact = h_cnt[0] + striped();
+    round++;
+  }
+  p.timer.stop(p.stream);
+  GCHK(gpu::d2h(dist, d_dist, (uint64_t)nn * sizeof(unsigned long long), p.stream));
+  GCHK(gpu::sync(p.stream));
+  if (device_ms) *device_ms = p.timer.ms();
+  return PPCSR_OK;
+}
+
+// Weakly connected components (pma_paths.h): hook pass + pointer jumping until a hook pass finds no edge with two labels;
+// one host read per round.
+int Engine::components(uint32_t *labels, double *device_ms) {
+  const ConsumerRef self{this, 0};
+  return components_over(&self, 1, n(), labels, device_ms);
+}
+int Engine::components_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t *labels, double *device_ms) {
+  Impl &p = *p_;
+  GCHK(gpu::set_device(device_));
+  const uint32_t nn = total_n;
+  uint32_t *d_lab = nullptr, *d_cnt = nullptr;
+  ConsumerPart *d_tab = nullptr;
+  DevGuard tmpg;
+  tmpg.add(&d_lab); tmpg.add(&d_cnt); tmpg.add(&d_tab);
+  uint64_t N = 0;
+  int rc = consumer_table(parts, P, nn, (void **)&d_tab, &N);
+  if (rc != PPCSR_OK) return rc;
+  const ConsumerPart *tab = d_tab;
+  GCHK(gpu::dmalloc((void **)&d_lab, std::max<uint64_t>(nn, 1) * sizeof(uint32_t)));
+  constexpr uint32_t cnt_words = kBfsStripes * kBfsStripeWords;
+  GCHK(gpu::dmalloc((void **)&d_cnt, cnt_words * sizeof(uint32_t)));
+  std::vector<uint32_t> h_cnt(cnt_words, 0);
+  p.timer.start(p.stream);
+  if (nn) GPU_LAUNCH(p.stream, k_cc_init, grid_for(nn, 256, 4096), 256, d_lab, nn);
+  for (bool more = nn != 0; more;) {
+    GCHK(gpu::dset(d_cnt, 0, cnt_words * sizeof(uint32_t), p.stream));
+    GPU_LAUNCH(p.stream, k_cc_hook, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, d_lab, d_cnt);
+    GPU_LAUNCH(p.stream, k_cc_jump, grid_for(nn, 256, 4096), 256, d_lab, nn);
+    GCHK(gpu::d2h(h_cnt.data(), d_cnt, cnt_words * sizeof(uint32_t), p.stream));
+    GCHK(gpu::sync(p.stream));
+    GCHK(gpu::last_error());
+    more = false;
+    for (uint32_t k = 0; k < kBfsStripes; k++) more = more || h_cnt[k * kBfsStripeWords] != 0;
+  }
+  p.timer.stop(p.stream);
+  if (nn) GCHK(gpu::d2h(labels, d_lab, (uint64_t)nn * sizeof(uint32_t), p.stream));
+  GCHK(gpu::sync(p.stream));
+  if (device_ms) *device_ms = p.timer.ms();
+  return PPCSR_OK;
+}
+
 // stable sort of (key, value) pairs by key: rocPRIM's radix sort on the device, std::stable_sort in the CPU emulator
 static int sort_pairs_stable(gpu::stream_t st, uint32_t *kin, uint32_t *kout, float *vin, float *vout, uint64_t m, unsigned bits) {
 #if defined(PPCSR_SIM)

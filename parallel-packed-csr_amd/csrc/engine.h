@@ -71,6 +71,12 @@ class Engine {
   // partition must share; bfs / pagerank are the one-partition case.  Writes nothing to any partition's graph state.
   int bfs_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t start, uint32_t *levels, double *device_ms);
   int pagerank_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const float *node_values, float *out, double *device_ms);
+  // shortest paths over the edge values (dist: total_n entries, UINT64_MAX = no path) and weakly connected components
+  // (labels[v] = smallest vertex id of v's component), under the same contract (pma_paths.h)
+  int sssp(uint32_t start, uint64_t *dist, double *device_ms);
+  int components(uint32_t *labels, double *device_ms);
+  int sssp_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t start, uint64_t *dist, double *device_ms);
+  int components_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t *labels, double *device_ms);
   int export_state(Edge *items, Node *nodes);
   int check_invariants(uint64_t *bad);  // leafcnt == recount(items)
   int stats(EngineStats *out);

@@ -3,6 +3,7 @@
 //   pma_spec_rounds.h  speculative rounds (o_plan / o_check / o_apply / o_big / o_settle): the default scheduler
 //   pma_rebalance.h    whole-array / big-window rebalance, in-place window rebalance, snapshots, maintenance
 //   pma_scan.h         queries, bulk neighbour scan, bulk build, BFS / PageRank
+//   pma_paths.h        shortest paths over the edge values, weakly connected components
 //   pma_query.h        batched reads: edge lookups with values, neighbourhood gathers
 //   pma_exchange.h     owner bucketing for the multi-GPU exchange
 #pragma once
@@ -10,5 +11,6 @@
 #include "pma_spec_rounds.h"
 #include "pma_rebalance.h"
 #include "pma_scan.h"
+#include "pma_paths.h"
 #include "pma_query.h"
 #include "pma_exchange.h"

@@ -1,0 +1,252 @@
+// Consumers that use the edge VALUES and the edges as undirected pairs: single-source shortest paths and weakly connected
+// components over the table of gapped arrays (pma_scan.h: ConsumerPart, cp_owner, cp_chunk_owner).  The edge set is the one
+// the BFS kernels walk: live non-sentinel slots of (beginning, end), slot N-1 excluded, local src < n_p, global dests < n.
+#pragma once
+#include "pma_scan.h"
+
+namespace ppcsr {
+
+constexpr unsigned long long kNoPath = 0xFFFFFFFFFFFFFFFFull;
+
+// ---- SSSP: frontier relaxation to a fixpoint -------------------------------------------------------------------------------
+// dist[] only falls.  stamp[v] is the last round for which v was made active: a vertex whose distance falls in round r gets
+// stamp r + 1 (an atomic max: the first writer of the round sees an older stamp and is the one that appends / counts the
+// vertex, so a vertex enters a round's active set once).  The active set of round r is { v : stamp[v] == r } — stamp[] plays
+// the part levels[] plays in BFS, so k_bfs_bits and k_bfs_collect build the round's bitmap and list from it unchanged.
+// Every fall re-activates, so when a round lowers nothing every edge has dist[v] <= dist[u] + w: with dist[start] = 0 that
+// is the shortest-path condition.  Sums cannot overflow: an active source has a finite distance, the sum of at most n - 1
+// <= 2^32 - 1 values <= 2^32 - 2 (include/ppcsr.h).
+PMA_DEV bool sssp_relax_edge(unsigned long long nd, uint32_t dst, uint32_t round, unsigned long long *dist, uint32_t *stamp) {
+  // (the caller has had a plain look at dist[dst] — possibly stale, that is: too large — and found it above nd: the atomic
+  // decides, and is issued only for what looked like a fall)
+  if (wv::atomic_min_u64(&dist[dst], nd) <= nd) return false;
+  if (stamp[dst] == round + 1u) return false;  // (already active for the next round; stale means one more atomic)
+  return wv::atomic_max_u32(&stamp[dst], round + 1u) <= round;
+}
+// Small active set: one wave per active vertex walks its slot range 64 slots per step; a hub is left to the streaming pass
+// through the same flag word as in BFS (next_count[1]).  dist[u] is read when the wave starts: it may already be lower than
+// at the start of the round (another wave lowered it; u then is active again next round).  A newer, smaller dist[u] only
+// relaxes with a tighter bound — the fixpoint, which is unique, does not depend on it.
+PMA_KERNEL void k_sssp_relax(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, const uint32_t *front, uint32_t nfront,
+                             uint32_t round, unsigned long long *dist, uint32_t *stamp, uint32_t *next, uint32_t *next_count) {
+  const int lane = wv::lane();
+  const uint64_t wstride = (uint64_t)wv::grid_dim() * (wv::block_dim() >> 6);
+  const Edge *const items0 = tab[0].items;
+  const Node *const nodes0 = tab[0].nodes;
+  for (uint64_t f = (uint64_t)wv::block_idx() * (wv::block_dim() >> 6) + wv::wave_in_block(); f < nfront; f += wstride) {
+    const uint32_t u = wv::uni(front[f]);
+    const Edge *items = items0;
+    Node nd;
+    if (P == 1) {
+      nd = nodes0[u];
+    } else {
+      const uint32_t k = cp_owner(tab, P, u);
+      items = tab[k].items;
+      nd = tab[k].nodes[u - tab[k].first];
+    }
+    if ((uint64_t)nd.end - (uint64_t)nd.beginning > kBfsWaveSlots) {  // a hub: leave it to one streaming pass (k_sssp_edges)
+      if (lane == 0) next_count[1] = 1u;
+      continue;
+    }
+    const unsigned long long du = dist[u];
+    for (uint64_t base = (uint64_t)nd.beginning + 1; base < (uint64_t)nd.end; base += 64) {
+      const uint64_t s = base + (uint64_t)lane;
+      uint32_t val = 0, dst = 0;
+      if (s < (uint64_t)nd.end) {
+        val = items[s].value;
+        dst = items[s].dest;
+      }
+      bool won = false;
+      if (val != 0 && dst < n && du + val < dist[dst]) won = sssp_relax_edge(du + val, dst, round, dist, stamp);
+      const uint64_t m = wv::ballot(won);
+      if (m) {
+        uint32_t b = 0;
+        if (lane == 0) b = wv::atomic_add_u32(next_count, (uint32_t)wv::popc64(m));
+        b = wv::shfl(b, 0);
+        if (won) next[b + dev::lanemask_lt_count(m, lane)] = dst;
+      }
+    }
+  }
+}
+// Large active set (or hubs left over): one streaming pass over the concatenated chunk space, four 64-slot chunks in flight
+// per wave; the source is tested against the round's active bitmap (n / 8 bytes: L2-resident), dist[src] is gathered only
+// for edges that pass.  `found` (kBfsStripes counters on lines of their own, one add per workgroup) counts the vertices
+// this pass made active for the next round — exactly, since the stamp admits each vertex once.
+PMA_KERNEL void k_sssp_edges(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, uint32_t round,
+                             const uint32_t *__restrict__ active_bits, unsigned long long *dist, uint32_t *stamp, uint32_t *found) {
+  const int lane = wv::lane();
+  const uint64_t nchunks = tab[P].chunk0;
+  const uint64_t wstride = (uint64_t)wv::grid_dim() * (wv::block_dim() >> 6);
+  const Edge *const items0 = tab[0].items;  // (one array: no search, no table look-up inside the loop)
+  const uint64_t N0 = tab[0].N;
+  const uint32_t n0 = tab[0].n;
+  uint32_t mine = 0;
+  constexpr int kB = 4;
+  for (uint64_t ch0 = wv::uni(((uint64_t)wv::block_idx() * (wv::block_dim() >> 6) + wv::wave_in_block()) * kB); ch0 < nchunks;
+       ch0 += wstride * kB) {
+    Edge e[kB];
+    uint32_t first[kB], pn[kB];
+#pragma unroll
+    for (int b = 0; b < kB; b++) {
+      const Edge *items = items0;
+      uint64_t s = (ch0 + b) * 64 + (uint64_t)lane, N = N0;
+      first[b] = 0;
+      pn[b] = n0;
+      if (P > 1 && ch0 + b < nchunks) {
+        const uint32_t k = cp_chunk_owner(tab, P, ch0 + b);
+        items = tab[k].items;
+        s -= tab[k].chunk0 * 64;
+        N = tab[k].N;
+        first[b] = tab[k].first;
+        pn[b] = tab[k].n;
+      }
+      e[b] = null_edge();
+      if (ch0 + b < nchunks && s + 1 < N) e[b] = items[s];  // (slot N-1 is never part of a neighbourhood)
+    }
+    // phases over all kB chunks, so that the kB gathers of a phase are in flight together
+    bool hit[kB];
+    unsigned long long nd[kB], dd[kB];
+#pragma unroll
+    for (int b = 0; b < kB; b++) {
+      const bool live = e[b].value != 0 && !is_sentinel(e[b]) && e[b].src < pn[b] && e[b].dest < n;
+      const uint32_t src = e[b].src + first[b];
+      hit[b] = live && ((active_bits[src >> 5] >> (src & 31u)) & 1u);
+      first[b] = src;
+    }
+#pragma unroll
+    for (int b = 0; b < kB; b++) {
+      nd[b] = hit[b] ? dist[first[b]] + e[b].value : kNoPath;
+      dd[b] = hit[b] ? dist[e[b].dest] : 0ull;
+    }
+#pragma unroll
+    for (int b = 0; b < kB; b++)
+      if (nd[b] < dd[b] && sssp_relax_edge(nd[b], e[b].dest, round, dist, stamp)) mine++;
+  }
+  PMA_SHARED uint32_t red[4];
+  mine = wv::reduce_add(mine);
+  if (lane == 0) red[wv::wave_in_block()] = mine;
+  wv::block_sync();
+  if (wv::thread_idx() == 0) {
+    const uint32_t all = red[0] + red[1] + red[2] + red[3];
+    if (all) wv::atomic_add_u32(found + (uint64_t)(wv::block_idx() % kBfsStripes) * kBfsStripeWords, all);
+  }
+}
+
+// ---- weakly connected components: min-label propagation with pointer jumping ---------------------------------------------
+// Invariants: labels only fall; labels[x] <= x; labels[x] is a vertex of x's component.  A hook pass that finds no edge
+// with two labels leaves labels constant on every component; the constant c is a vertex of the component and the
+// component's smallest vertex m has labels[m] <= m, so c = m.
+PMA_KERNEL void k_cc_init(uint32_t *labels, uint32_t n) {
+  const uint64_t stride = (uint64_t)wv::grid_dim() * wv::block_dim();
+  for (uint64_t v = (uint64_t)wv::block_idx() * wv::block_dim() + wv::thread_idx(); v < n; v += stride) labels[v] = (uint32_t)v;
+}
+// One streaming pass: an edge whose ends carry different labels lowers the end with the larger label, and the entry of that
+// larger label itself (the vertex it pointed to — this is what merges whole trees instead of single vertices, so a long chain
+// finishes in few rounds).  Loads may be stale (too large): the atomic min decides.  `found` counts the edges that differed.
+constexpr int kCcRunLanes = 8;  // lanes of a wave on one source from which its run is reduced before the atomic
+PMA_KERNEL void k_cc_hook(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, uint32_t *labels, uint32_t *found) {
+  const int lane = wv::lane();
+  const uint64_t nchunks = tab[P].chunk0;
+  const uint64_t wstride = (uint64_t)wv::grid_dim() * (wv::block_dim() >> 6);
+  const Edge *const items0 = tab[0].items;
+  const uint64_t N0 = tab[0].N;
+  const uint32_t n0 = tab[0].n;
+  uint32_t mine = 0;
+  constexpr int kB = 4;
+  for (uint64_t ch0 = wv::uni(((uint64_t)wv::block_idx() * (wv::block_dim() >> 6) + wv::wave_in_block()) * kB); ch0 < nchunks;
+       ch0 += wstride * kB) {
+    Edge e[kB];
+    uint32_t first[kB], pn[kB];
+#pragma unroll
+    for (int b = 0; b < kB; b++) {
+      const Edge *items = items0;
+      uint64_t s = (ch0 + b) * 64 + (uint64_t)lane, N = N0;
+      first[b] = 0;
+      pn[b] = n0;
+      if (P > 1 && ch0 + b < nchunks) {
+        const uint32_t k = cp_chunk_owner(tab, P, ch0 + b);
+        items = tab[k].items;
+        s -= tab[k].chunk0 * 64;
+        N = tab[k].N;
+        first[b] = tab[k].first;
+        pn[b] = tab[k].n;
+      }
+      e[b] = null_edge();
+      if (ch0 + b < nchunks && s + 1 < N) e[b] = items[s];  // (slot N-1 is never part of a neighbourhood)
+    }
+    bool live[kB];
+    uint32_t lu[kB], lv[kB];
+#pragma unroll
+    for (int b = 0; b < kB; b++) {
+      live[b] = e[b].value != 0 && !is_sentinel(e[b]) && e[b].src < pn[b] && e[b].dest < n;
+      first[b] += e[b].src;  // global source
+      live[b] = live[b] && first[b] != e[b].dest;
+    }
+#pragma unroll
+    for (int b = 0; b < kB; b++) {
+      lu[b] = live[b] ? labels[first[b]] : 0u;
+      lv[b] = live[b] ? labels[e[b].dest] : 0u;
+    }
+#pragma unroll
+    for (int b = 0; b < kB; b++) {
+      const bool diff = lu[b] != lv[b];
+      uint32_t lo = lu[b] < lv[b] ? lu[b] : lv[b];
+      const uint32_t hi = lu[b] < lv[b] ? lv[b] : lu[b];
+      const uint32_t x = lu[b] < lv[b] ? e[b].dest : first[b];
+      // Lanes that lower THEIR SOURCE share the target with their neighbours (a vertex's slots are contiguous): 64 atomics on
+      // one word are served one after the other, and a hub's run fills whole waves.  The runs at the two ends of the wave's
+      // pending lanes — a run that fills the wave is both — are reduced to their smallest label and one lane issues it
+      // (the others' edges still count as differing; whatever they would have stored is not below that minimum).
+      bool issue = diff;
+      const bool own = diff && x == first[b];
+      const uint64_t pend = wv::ballot(own);
+      if (pend) {
+        const int ends[2] = {wv::ctz64(pend), 63 - wv::clz64(pend)};
+        for (int t = 0; t < 2; t++) {
+          const uint32_t key = wv::bcast(x, ends[t]);
+          const bool in = own && issue && x == key;
+          const uint64_t grp = wv::ballot(in);
+          if (wv::popc64(grp) < kCcRunLanes) continue;
+          uint32_t m = in ? lo : 0xFFFFFFFFu;
+          for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t o = wv::shfl(m, lane ^ d);
+            m = o < m ? o : m;
+          }
+          if (in) {
+            lo = m;
+            issue = lane == wv::ctz64(grp);
+          }
+        }
+      }
+      if (issue) {
+        wv::atomic_min_u32(&labels[x], lo);
+        if (hi != x) wv::atomic_min_u32(&labels[hi], lo);
+      }
+      if (diff) mine++;
+    }
+  }
+  PMA_SHARED uint32_t red[4];
+  mine = wv::reduce_add(mine);
+  if (lane == 0) red[wv::wave_in_block()] = mine;
+  wv::block_sync();
+  if (wv::thread_idx() == 0) {
+    const uint32_t all = red[0] + red[1] + red[2] + red[3];
+    if (all) wv::atomic_add_u32(found + (uint64_t)(wv::block_idx() % kBfsStripes) * kBfsStripeWords, all);
+  }
+}
+// labels[v] = the end of v's label chain.  labels[x] <= x, so a chain falls strictly until it meets a fixed point; only
+// thread v stores to labels[v], and what it stores is not above what it read there.
+PMA_KERNEL void k_cc_jump(uint32_t *labels, uint32_t n) {
+  const uint64_t stride = (uint64_t)wv::grid_dim() * wv::block_dim();
+  for (uint64_t v = (uint64_t)wv::block_idx() * wv::block_dim() + wv::thread_idx(); v < n; v += stride) {
+    const uint32_t l0 = labels[v];
+    uint32_t l = l0, next = labels[l];
+    while (next != l) {
+      l = next;
+      next = labels[l];
+    }
+    if (l != l0) labels[v] = l;
+  }
+}
+
+}  // namespace ppcsr
