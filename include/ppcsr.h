@@ -169,6 +169,39 @@ int ppcsr_restore(ppcsr_t h);
 int ppcsr_check_invariants(ppcsr_t h, uint64_t *bad_leaves);
 int ppcsr_bench_scan_all(ppcsr_t h, double *ms, uint64_t *total);
 int ppcsr_bench_rebalance(ppcsr_t h, uint64_t window_slots, int iters, double *ms_per_call);
+/* Debugging probe of the rebalance position chain: the functions every rebalance places its elements with, run ON THE DEVICE on
+ * a batch of cases, in buffers of the call's own (the engine's state is neither read nor written).  No reference equivalent.
+ *   mode  cases (words per case)              what runs                                              comes back
+ *   0 table      (index, len, j)              one thread builds the table, a grid expands it         pos, info, segs, samples
+ *   1 published  (index, len, j)              the table built INSIDE the expanding launch and handed pos, info, segs, samples, wg
+ *                                             from workgroup 0 to the others segment by segment, over a POISONED buffer
+ *   2 single     (index, len, j)              the one-segment closed form of the in-wave rebalance   pos (where accepted), info, segs
+ *   3 linear     (index, len, j)              linear runs of <= 64 ranks at stride 37 vs the table   info
+ *   4 segment    (bits of x, bits of step,    one segment from raw operands, then the device's own   segs (6 words per case), info,
+ *                 mantissa S, exponent es)    fp64 subtractions walked along it                      pos (4096 words per case: bits)
+ *   5 div        (a, b), both < 2^53, b > 0   the table build's floor division                       pos: (quotient, raw estimate)
+ * pos: case c writes pos[pos_off[c] ...]: for j <= 2^22 the j positions, above that one order-independent 64-bit digest per block of
+ * 2^20 consecutive ranks (wrapping sum of splitmix64(pos_k + k * 0x9E3779B97F4A7C15)).  sample_*: optional ranks whose literal
+ * positions are wanted as well (sample_off: ncases + 1 offsets into sample_k / sample_pos).  info: 4 ints per case — segments,
+ * overflow flag, verdict of mode 2 / differing positions of mode 3, runs mode 3 accepted.  segs: optional, 128 segments of 6 words
+ * per case (t0, count, M0, Dfirst, Drest, shift).  wg: optional, mode 1, 4 words per case — workgroups, those (other than the
+ * builder) that went ahead with a PART of the table, those that gave up waiting and built it themselves, fewest segments copied.
+ * grid: mode 1, number of workgroups (0: one per 4096 ranks) */
+typedef struct ppcsr_chain_probe_io {
+  int32_t mode;
+  uint32_t grid;
+  uint64_t ncases;
+  const uint64_t *cases;
+  const uint64_t *pos_off;
+  uint64_t *pos;
+  const uint64_t *sample_off;
+  const uint64_t *sample_k;
+  uint64_t *sample_pos;
+  int32_t *info;
+  uint64_t *segs;
+  uint32_t *wg;
+} ppcsr_chain_probe_io;
+int ppcsr_debug_chain_probe(ppcsr_t h, const ppcsr_chain_probe_io *io);
 /* PCSR::double_list / half_list (PCSR.cpp:251-282, 284-320) alone: the array is doubled and halved back `iters` times; device time
  * per call of each (measurement helper: the array ends at its original size, evenly spread) */
 int ppcsr_bench_resize(ppcsr_t h, int iters, double *double_ms, double *half_ms);

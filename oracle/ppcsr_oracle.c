@@ -77,6 +77,56 @@ void po_redistribute_positions(uint64_t index, uint64_t len, uint64_t j, uint64_
   out[0] = index;
 }
 
+/* The same loop (pcsr/PCSR.cpp:237-247) for windows too large to keep every position: one order-independent digest per block of
+ * 2^block_log2 consecutive ranks — the wrapping sum of splitmix64(pos_k + k * 0x9E3779B97F4A7C15) — and whether the chain is a
+ * PLACEMENT at all.  Return value: 0 = the positions rise strictly (pos_1 > pos_0 = index included) and stay below index + len;
+ * bit 0 = two ranks share a slot or fall out of order; bit 1 = a position at or beyond index + len; bit 2 = the running value went
+ * negative, where the reference's (size_t) cast is undefined (such a position is taken as 0 here).  digests may be NULL.
+ * Literal positions as well for the ranks of `nranges` ranges [range_lo[r], range_hi[r]) — ascending, disjoint, inside [0, j) —
+ * written one range after the other into range_pos */
+static inline uint64_t po_mix_rank_pos(uint64_t k, uint64_t pos) {
+  uint64_t z = pos + k * 0x9E3779B97F4A7C15ull;
+  z ^= z >> 30;
+  z *= 0xBF58476D1CE4E5B9ull;
+  z ^= z >> 27;
+  z *= 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return z;
+}
+int po_redistribute_positions_digest(uint64_t index, uint64_t len, uint64_t j, int block_log2, uint64_t *digests, uint64_t nranges,
+                                     const uint64_t *range_lo, const uint64_t *range_hi, uint64_t *range_pos) {
+  if (j == 0) return 0;
+  int status = 0;
+  uint64_t r = nranges, r_base = 0; /* r - 1: the range the descending loop meets next; r_base: where its positions start */
+  for (uint64_t q = 0; q < nranges; q++) r_base += range_hi[q] - range_lo[q];
+  if (r) r_base -= range_hi[r - 1] - range_lo[r - 1];
+  const double step = (double)len / (double)j;
+  double index_d = (double)index + (double)(j - 1) * step;
+  uint64_t above = index + len; /* the position of the rank above the current one (the window's end for the top rank) */
+  for (uint64_t i = j - 1; i > 0; i--) {
+    uint64_t in;
+    if (index_d < 0) {
+      status |= 4;
+      in = 0;
+    } else {
+      in = (uint64_t)index_d;
+    }
+    if (in >= above) status |= (i == j - 1) ? 2 : 1;
+    above = in;
+    if (digests) digests[i >> block_log2] += po_mix_rank_pos(i, in);
+    while (r && i < range_lo[r - 1]) {
+      r--;
+      if (r) r_base -= range_hi[r - 1] - range_lo[r - 1];
+    }
+    if (r && i < range_hi[r - 1]) range_pos[r_base + (i - range_lo[r - 1])] = in;
+    index_d -= step;
+  }
+  if (above <= index) status |= 1; /* pos_1 <= pos_0 (j == 1: above is still index + len) */
+  if (digests) digests[0] += po_mix_rank_pos(0, index);
+  if (nranges && range_lo[0] == 0 && range_hi[0] > 0) range_pos[0] = index;
+  return status;
+}
+
 /* pcsr/PCSR.cpp:222-249 */
 static void po_redistribute(po_pcsr *p, int64_t index, int64_t len) {
   p->st.redistribute_calls++;

@@ -59,6 +59,11 @@ void po_get_stats(const po_pcsr *p, po_stats *out);
 void po_reset_stats(po_pcsr *p);
 /* exact redistribute target positions (PCSR.cpp:237-247) for a window; out[k] = slot of element k */
 void po_redistribute_positions(uint64_t index, uint64_t len, uint64_t j, uint64_t *out);
+/* the same chain as digests (one per 2^block_log2 ranks; caller zeroes them) + whether it is a strictly rising placement inside the
+ * window: 0 yes; bit 0 collision / disorder, bit 1 beyond the window's end, bit 2 negative running value; optionally the literal
+ * positions of the ranks in a few ascending, disjoint ranges */
+int po_redistribute_positions_digest(uint64_t index, uint64_t len, uint64_t j, int block_log2, uint64_t *digests, uint64_t nranges,
+                                     const uint64_t *range_lo, const uint64_t *range_hi, uint64_t *range_pos);
 
 /* PPPCSR: vertex-range partitioning (PPPCSR.cpp:13-34, 58-66) */
 typedef struct po_pppcsr po_pppcsr;

@@ -36,6 +36,18 @@ class Stats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ChainProbeIO(ctypes.Structure):
+    """ppcsr_chain_probe_io (include/ppcsr.h)"""
+    _fields_ = [("mode", ctypes.c_int32), ("grid", c_u32), ("ncases", c_u64), ("cases", c_vp), ("pos_off", c_vp), ("pos", c_vp),
+                ("sample_off", c_vp), ("sample_k", c_vp), ("sample_pos", c_vp), ("info", c_vp), ("segs", c_vp), ("wg", c_vp)]
+
+
+CHAIN_PROBE_MODES = {"table": 0, "published": 1, "single": 2, "linear": 3, "segment": 4, "div": 5}
+CHAIN_PROBE_LITERAL_MAX = 1 << 22  # windows with more elements come back as one digest per 2^20 ranks
+CHAIN_PROBE_DIGEST_LOG = 20
+CHAIN_PROBE_WALK = 4096
+CHAIN_MAX_SEG = 128
+
 EXPORTED = [
     "ppcsr_create", "ppcsr_destroy", "ppcsr_add_edge", "ppcsr_remove_edge", "ppcsr_add_node", "ppcsr_apply_batch",
     "ppcsr_apply_batch_device", "ppcsr_edge_exists", "ppcsr_get_n", "ppcsr_get_node", "ppcsr_geometry",
@@ -53,6 +65,7 @@ EXPORTED = [
     "pppcsr_exchange_bulk_build", "ppcsr_lookup_edges", "ppcsr_lookup_edges_device", "ppcsr_gather_neighbourhoods",
     "ppcsr_gather_neighbourhoods_device", "pppcsr_lookup_edges", "pppcsr_gather_neighbourhoods", "pppcsr_set_option",
     "pppcsr_bfs", "pppcsr_pagerank", "ppcsr_sssp", "ppcsr_components", "pppcsr_sssp", "pppcsr_components",
+    "ppcsr_debug_chain_probe",
 ]
 
 NO_PATH = 0xFFFFFFFFFFFFFFFF  # PPCSR_NO_PATH: what sssp reports for a vertex no path reaches
@@ -132,6 +145,7 @@ def load_library(path=None):
     L.ppcsr_check_invariants.argtypes = [c_vp, ctypes.POINTER(c_u64)]
     L.ppcsr_bench_scan_all.argtypes = [c_vp, ctypes.POINTER(c_dbl), ctypes.POINTER(c_u64)]
     L.ppcsr_bench_rebalance.argtypes = [c_vp, c_u64, c_int, ctypes.POINTER(c_dbl)]
+    L.ppcsr_debug_chain_probe.argtypes = [c_vp, ctypes.POINTER(ChainProbeIO)]
     L.ppcsr_bench_resize.argtypes = [c_vp, c_int, ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl)]
     L.ppcsr_strerror.restype = ctypes.c_char_p
     L.ppcsr_strerror.argtypes = [c_int]
@@ -396,6 +410,71 @@ class PCSR:
         ms = c_dbl()
         self._chk(self.L.ppcsr_bench_rebalance(self.h, window_slots, iters, ctypes.byref(ms)))
         return ms.value
+
+    def debug_chain_probe(self, mode, cases, samples=None, grid=0, want_segs=True):
+        """Debugging: the rebalance's position-chain functions run on the device (ppcsr_debug_chain_probe); engine state untouched.
+        mode "table" / "published" / "single" / "linear": cases = (index, len, j) rows -> dict with `pos` (list: per case the j
+        positions, or one digest per 2^20 ranks when j > 2^22; None where "single" declined), `nseg`, `overflow`, `verdict`
+        (single) / `mismatches`, `runs` (linear), `segs` (ncases x 128 x 6), `samples` (list, positions of the ranks asked for
+        in `samples`), `wg` (published: ncases x 4 = workgroups, partial-table consumers, fallbacks, fewest segments copied).
+        mode "segment": cases = (bits of x, bits of step, S, es) rows -> `segs` (ncases x 6), `steps`, `walk` (list of bit arrays).
+        mode "div": cases = (a, b) rows -> `q`, `est`."""
+        m = CHAIN_PROBE_MODES[mode]
+        width = {4: 4, 5: 2}.get(m, 3)
+        cs = np.ascontiguousarray(np.asarray(cases, np.uint64).reshape(-1, width))
+        n = len(cs)
+        io = ChainProbeIO(mode=m, grid=grid, ncases=n, cases=cs.ctypes.data)
+        keep = [cs]
+        if m == 5:
+            out = np.zeros((n, 2), np.uint64)
+            io.pos = out.ctypes.data
+            self._chk(self.L.ppcsr_debug_chain_probe(self.h, ctypes.byref(io)))
+            return {"q": out[:, 0].copy(), "est": out[:, 1].copy()}
+        info = np.zeros((n, 4), np.int32)
+        io.info = info.ctypes.data
+        if m == 4:
+            cnt = np.full(n, CHAIN_PROBE_WALK, np.uint64)
+            segs = np.zeros((n, 6), np.uint64)
+        else:
+            j = cs[:, 2]
+            cnt = np.where(j <= CHAIN_PROBE_LITERAL_MAX, j, (j + np.uint64((1 << CHAIN_PROBE_DIGEST_LOG) - 1)) >> np.uint64(CHAIN_PROBE_DIGEST_LOG))
+            segs = np.zeros((n, CHAIN_MAX_SEG, 6), np.uint64) if want_segs else None
+        off = np.zeros(n + 1, np.uint64)
+        np.cumsum(cnt, out=off[1:])
+        pos = np.zeros(int(off[-1]) if m != 3 else 1, np.uint64)
+        io.pos_off, io.pos = off.ctypes.data, pos.ctypes.data
+        if segs is not None:
+            io.segs = segs.ctypes.data
+        wg = np.zeros((n, 4), np.uint32)
+        io.wg = wg.ctypes.data
+        soff = spos = None
+        if samples is not None and m in (0, 1):
+            ks = [np.ascontiguousarray(np.asarray(k, np.uint64)) for k in samples]
+            soff = np.zeros(n + 1, np.uint64)
+            np.cumsum([len(k) for k in ks], out=soff[1:])
+            sk = np.concatenate(ks) if n else np.zeros(0, np.uint64)
+            if len(sk) == 0:
+                sk = np.zeros(1, np.uint64)
+            spos = np.zeros(max(int(soff[-1]), 1), np.uint64)
+            io.sample_off, io.sample_k, io.sample_pos = soff.ctypes.data, sk.ctypes.data, spos.ctypes.data
+            keep += [sk]
+        self._chk(self.L.ppcsr_debug_chain_probe(self.h, ctypes.byref(io)))
+        if m == 4:
+            return {"segs": segs, "steps": info[:, 0].copy(),
+                    "walk": [pos[int(off[c]):int(off[c]) + int(info[c, 0])].copy() for c in range(n)]}
+        res = {"nseg": info[:, 0].copy(), "overflow": info[:, 1].copy(), "segs": segs}
+        if m == 3:
+            res["mismatches"], res["runs"] = info[:, 2].copy(), info[:, 3].copy()
+            return res
+        res["pos"] = [pos[int(off[c]):int(off[c + 1])] for c in range(n)]
+        if m == 2:
+            res["verdict"] = info[:, 2].copy()
+            res["pos"] = [p if v else None for p, v in zip(res["pos"], res["verdict"])]
+        if m == 1:
+            res["wg"] = wg
+        if soff is not None:
+            res["samples"] = [spos[int(soff[c]):int(soff[c + 1])] for c in range(n)]
+        return res
 
 
 class PPPCSR:

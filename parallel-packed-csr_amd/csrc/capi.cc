@@ -198,6 +198,11 @@ int ppcsr_stats(ppcsr_t h, ppcsr_stats_t *out) {
 int ppcsr_set_option(ppcsr_t h, const char *key, int64_t value) { H_CHECK(); return ret(h->e, h->e->set_option(key, value)); }
 int ppcsr_check_invariants(ppcsr_t h, uint64_t *bad_leaves) { H_CHECK(); return ret(h->e, h->e->check_invariants(bad_leaves)); }
 int ppcsr_bench_scan_all(ppcsr_t h, double *ms, uint64_t *total) { H_CHECK(); return ret(h->e, h->e->scan_all_device(ms, total)); }
+static_assert(sizeof(ppcsr_chain_probe_io) == sizeof(ppcsr::ChainProbeIO), "layout");
+int ppcsr_debug_chain_probe(ppcsr_t h, const ppcsr_chain_probe_io *io) {
+  H_CHECK();
+  return ret(h->e, h->e->chain_probe(reinterpret_cast<const ppcsr::ChainProbeIO *>(io)));
+}
 int ppcsr_bench_rebalance(ppcsr_t h, uint64_t w, int iters, double *ms) { H_CHECK(); return ret(h->e, h->e->rebalance_bench(w, iters, ms)); }
 int ppcsr_bench_resize(ppcsr_t h, int iters, double *double_ms, double *half_ms) {
   H_CHECK();

@@ -2760,6 +2760,210 @@ int Engine::rebalance_bench(uint64_t wlen, int iters, double *ms_per_call) {
   return inplace_fault_check();
 }
 
+// Debugging probe of the position chain (pma_probe.h): every case runs the production functions on the device, in the probe's
+// own buffers (not p.d_table: a later rebalance expects it as it left it), on the engine's stream.  Engine state is not read.
+int Engine::chain_probe(const ChainProbeIO *io) {
+  Impl &p = *p_;
+  if (!io || (io->ncases && !io->cases)) return fail(PPCSR_EINVAL, "chain probe: no cases");
+  GCHK(gpu::set_device(device_));
+  const uint64_t n = io->ncases;
+  DevGuard guard;
+  if (io->mode == 5) {  // div: (a, b) -> (quotient, estimate)
+    if (!io->pos) return fail(PPCSR_EINVAL, "chain probe: no output");
+    for (uint64_t c = 0; c < n; c++)
+      if (io->cases[2 * c + 1] == 0 || (io->cases[2 * c] >> 53) || (io->cases[2 * c + 1] >> 53)) return fail(PPCSR_EINVAL, "chain probe: div operands must be below 2^53, b > 0");
+    uint64_t *d_ops = nullptr, *d_out = nullptr;
+    guard.add(&d_ops);
+    guard.add(&d_out);
+    const uint64_t chunk = 1ull << 20;
+    GCHK(gpu::dmalloc((void **)&d_ops, std::min(n, chunk) * 16));
+    GCHK(gpu::dmalloc((void **)&d_out, std::min(n, chunk) * 16));
+    for (uint64_t lo = 0; lo < n; lo += chunk) {
+      const uint64_t m = std::min(chunk, n - lo);
+      GCHK(gpu::h2d(d_ops, io->cases + 2 * lo, m * 16, p.stream));
+      GPU_LAUNCH(p.stream, k_probe_div, (m + kProbeThreads - 1) / kProbeThreads, kProbeThreads, (const uint64_t *)d_ops, m, d_out);
+      GCHK(gpu::d2h(io->pos + 2 * lo, d_out, m * 16, p.stream));
+      GCHK(gpu::sync(p.stream));
+    }
+    GCHK(gpu::last_error());
+    return PPCSR_OK;
+  }
+  if (io->mode == 4) {  // segment: (bits x, bits step, S, es) -> segment words, walked values
+    if (!io->pos || !io->pos_off || !io->info || !io->segs) return fail(PPCSR_EINVAL, "chain probe: no output");
+    for (uint64_t c = 0; c < n; c++) {
+      const double x = bits_dbl(io->cases[4 * c]), st = bits_dbl(io->cases[4 * c + 1]);
+      if (!(x > 0 && x < 1.0e300 && st > 0 && st < 1.0e300)) return fail(PPCSR_EINVAL, "chain probe: segment operands must be positive and finite");
+      if (io->pos_off[c + 1] - io->pos_off[c] < kProbeWalk) return fail(PPCSR_EINVAL, "chain probe: segment cases take 4096 output words each");
+    }
+    const uint64_t chunk = 256;
+    uint64_t *d_ops = nullptr, *d_walk = nullptr;
+    ChainSeg *d_segs = nullptr;
+    uint32_t *d_nw = nullptr;
+    guard.add(&d_ops);
+    guard.add(&d_walk);
+    guard.add(&d_segs);
+    guard.add(&d_nw);
+    GCHK(gpu::dmalloc((void **)&d_ops, chunk * 32));
+    GCHK(gpu::dmalloc((void **)&d_walk, chunk * kProbeWalk * 8));
+    GCHK(gpu::dmalloc((void **)&d_segs, chunk * sizeof(ChainSeg)));
+    GCHK(gpu::dmalloc((void **)&d_nw, chunk * 4));
+    std::vector<uint32_t> nw(chunk);
+    std::vector<ChainSeg> sg(chunk);
+    std::vector<uint64_t> walk(chunk * kProbeWalk);
+    for (uint64_t lo = 0; lo < n; lo += chunk) {
+      const uint64_t m = std::min(chunk, n - lo);
+      GCHK(gpu::h2d(d_ops, io->cases + 4 * lo, m * 32, p.stream));
+      GCHK(gpu::dset(d_walk, 0xFF, m * kProbeWalk * 8, p.stream));
+      GPU_LAUNCH(p.stream, k_probe_segment, (m + 63) / 64, 64, (const uint64_t *)d_ops, m, d_segs, d_nw, d_walk);
+      GCHK(gpu::d2h(nw.data(), d_nw, m * 4, p.stream));
+      GCHK(gpu::d2h(sg.data(), d_segs, m * sizeof(ChainSeg), p.stream));
+      GCHK(gpu::d2h(walk.data(), d_walk, m * kProbeWalk * 8, p.stream));
+      GCHK(gpu::sync(p.stream));
+      for (uint64_t c = 0; c < m; c++) {
+        memcpy(io->segs + 6 * (lo + c), &sg[c], sizeof(ChainSeg));
+        io->info[4 * (lo + c)] = (int32_t)nw[c];
+        memcpy(io->pos + io->pos_off[lo + c], &walk[c * kProbeWalk], (size_t)kProbeWalk * 8);
+      }
+    }
+    GCHK(gpu::last_error());
+    return PPCSR_OK;
+  }
+  if (io->mode < 0 || io->mode > 3) return fail(PPCSR_EINVAL, "chain probe: unknown mode");
+  if (!io->info || (io->mode != 3 && (!io->pos || !io->pos_off))) return fail(PPCSR_EINVAL, "chain probe: no output");
+  // window modes: (index, len, j), one case at a time through one set of buffers sized for the largest
+  const uint64_t lit_max = 1ull << 22, dig = 1ull << kProbeDigestLog;
+  uint64_t max_lit = 1, max_dig = 1, max_smp = 1, max_grid = 1;
+  for (uint64_t c = 0; c < n; c++) {
+    const uint64_t index = io->cases[3 * c], len = io->cases[3 * c + 1], j = io->cases[3 * c + 2];
+    if (len == 0 || j == 0 || j > len || j > 0xFFFFFFFEull || index > (1ull << 40) || len > (1ull << 40)) return fail(PPCSR_EINVAL, "chain probe: 1 <= j <= len wanted");
+    const uint64_t want = j <= lit_max ? j : (j + dig - 1) / dig;
+    if (io->mode != 3 && io->pos_off[c + 1] - io->pos_off[c] < want) return fail(PPCSR_EINVAL, "chain probe: output too small for a case");
+    if (j <= lit_max) max_lit = std::max(max_lit, j); else max_dig = std::max(max_dig, want);
+    if (io->sample_off) {
+      if (!io->sample_k || !io->sample_pos || io->sample_off[c + 1] < io->sample_off[c]) return fail(PPCSR_EINVAL, "chain probe: bad sample list");
+      for (uint64_t i = io->sample_off[c]; i < io->sample_off[c + 1]; i++)
+        if (io->sample_k[i] >= j) return fail(PPCSR_EINVAL, "chain probe: sample rank beyond j");
+      max_smp = std::max(max_smp, io->sample_off[c + 1] - io->sample_off[c]);
+    }
+    if (io->mode == 1) {
+      uint64_t g = io->grid ? io->grid : (j + kProbeTile - 1) / kProbeTile;
+      if (g > (1ull << 20)) return fail(PPCSR_EINVAL, "chain probe: more than 2^20 workgroups");
+      max_grid = std::max(max_grid, g);
+    }
+  }
+  ChainTable *d_tb = nullptr;
+  uint64_t *d_pos = nullptr, *d_sk = nullptr, *d_so = nullptr;
+  unsigned long long *d_dig = nullptr, *d_lin = nullptr;
+  uint32_t *d_wg = nullptr;
+  guard.add(&d_tb);
+  guard.add(&d_pos);
+  guard.add(&d_sk);
+  guard.add(&d_so);
+  guard.add(&d_dig);
+  guard.add(&d_lin);
+  guard.add(&d_wg);
+  GCHK(gpu::dmalloc((void **)&d_tb, sizeof(ChainTable)));
+  GCHK(gpu::dmalloc((void **)&d_pos, max_lit * 8));
+  GCHK(gpu::dmalloc((void **)&d_dig, max_dig * 8));
+  GCHK(gpu::dmalloc((void **)&d_sk, max_smp * 8));
+  GCHK(gpu::dmalloc((void **)&d_so, max_smp * 8));
+  GCHK(gpu::dmalloc((void **)&d_lin, 16));
+  GCHK(gpu::dmalloc((void **)&d_wg, max_grid * 4));
+  std::unique_ptr<ChainTable> htb(new ChainTable);
+  std::vector<uint32_t> hwg(max_grid);
+  for (uint64_t c = 0; c < n; c++) {
+    const uint64_t index = io->cases[3 * c], len = io->cases[3 * c + 1], j = io->cases[3 * c + 2];
+    const bool literal = j <= lit_max;
+    const uint64_t ndig = (j + dig - 1) / dig;
+    uint64_t *pos_out = literal ? d_pos : (uint64_t *)nullptr;
+    unsigned long long *dig_out = literal ? (unsigned long long *)nullptr : d_dig;
+    const uint32_t xgrid = grid_for(j, kProbeTile);
+    int32_t *info = io->info + 4 * c;
+    info[0] = info[1] = info[2] = info[3] = 0;
+    GCHK(gpu::dset(d_tb, 0xFF, sizeof(ChainTable), p.stream));  // poison: nothing of an earlier case (an equal table!) can be read
+    if (io->mode != 3) {
+      if (literal) GCHK(gpu::dset(d_pos, 0xFF, j * 8, p.stream));
+      else GCHK(gpu::dset(d_dig, 0, ndig * 8, p.stream));
+    }
+    uint64_t pgrid = 0;
+    if (io->mode == 0) {
+      GPU_LAUNCH(p.stream, k_probe_table, 1, 64, d_tb, index, len, j);
+      GPU_LAUNCH(p.stream, k_probe_expand, xgrid, kProbeThreads, (const ChainTable *)d_tb, pos_out, dig_out);
+    } else if (io->mode == 1) {
+      pgrid = io->grid ? io->grid : (j + kProbeTile - 1) / kProbeTile;
+      uint64_t tile_ranks = (j + pgrid - 1) / pgrid;
+      tile_ranks = (tile_ranks + kProbeTile - 1) / kProbeTile * kProbeTile;
+      GCHK(gpu::dset(d_wg, 0, pgrid * 4, p.stream));
+      GPU_LAUNCH(p.stream, k_probe_header, 1, 64, d_tb, index, len, j);
+      GPU_LAUNCH(p.stream, k_probe_published, pgrid, kProbeThreads, d_tb, tile_ranks, pos_out, dig_out, d_wg);
+    } else if (io->mode == 2) {
+      GPU_LAUNCH(p.stream, k_probe_single, 1, 64, d_tb, index, len, j);
+      GPU_LAUNCH(p.stream, k_probe_single_expand, xgrid, kProbeThreads, (const ChainTable *)d_tb, pos_out, dig_out);
+    } else {
+      GCHK(gpu::dset(d_lin, 0, 16, p.stream));
+      GPU_LAUNCH(p.stream, k_probe_table, 1, 64, d_tb, index, len, j);
+      GPU_LAUNCH(p.stream, k_probe_linear, grid_for((j + 36) / 37, kProbeThreads), kProbeThreads, (const ChainTable *)d_tb, d_lin);
+    }
+    GCHK(gpu::d2h(htb.get(), d_tb, sizeof(ChainTable), p.stream));
+    GCHK(gpu::sync(p.stream));
+    GCHK(gpu::last_error());
+    int nseg = htb->nseg;
+    if (io->mode == 1) {  // (the builder publishes its count in pub_nseg; the header's nseg stays 0)
+      nseg = (int)(htb->pub_nseg & ~kTbDone);
+      info[1] = !(htb->pub_nseg & kTbDone) ? 2 : ((nseg >= kMaxSeg && j >= 2 && (uint64_t)htb->pub_t < j - 1) ? 1 : 0);
+      if (nseg < 0 || nseg > kMaxSeg) return fail(PPCSR_EINTERNAL, "chain probe: published segment count out of range");
+      GCHK(gpu::d2h(hwg.data(), d_wg, pgrid * 4, p.stream));
+      GCHK(gpu::h2d(&d_tb->nseg, &nseg, sizeof(int), p.stream));  // (so that the sample kernel below can read the finished table)
+      GCHK(gpu::sync(p.stream));
+      uint32_t partial = 0, fallback = 0, fewest = 0xFFFFFFFFu;
+      for (uint64_t b = 0; b < pgrid; b++) {
+        if (hwg[b] == kProbeFallback) {
+          fallback++;
+          continue;
+        }
+        if (b != 0 && hwg[b] < (uint32_t)nseg) partial++;
+        fewest = std::min(fewest, hwg[b]);
+      }
+      if (io->wg) {
+        io->wg[4 * c] = (uint32_t)pgrid;
+        io->wg[4 * c + 1] = partial;
+        io->wg[4 * c + 2] = fallback;
+        io->wg[4 * c + 3] = fewest;
+      }
+    } else {
+      info[1] = htb->overflow;
+    }
+    info[0] = nseg;
+    if (io->segs) {
+      static_assert(sizeof(ChainSeg) == 48, "six words per segment");
+      memset(io->segs + (size_t)6 * kMaxSeg * c, 0, sizeof(ChainSeg) * kMaxSeg);
+      if (nseg > 0 && nseg <= kMaxSeg) memcpy(io->segs + (size_t)6 * kMaxSeg * c, htb->seg, sizeof(ChainSeg) * (size_t)nseg);
+    }
+    if (io->mode == 3) {
+      unsigned long long lin[2];
+      GCHK(gpu::d2h(lin, d_lin, 16, p.stream));
+      GCHK(gpu::sync(p.stream));
+      info[2] = (int32_t)std::min<unsigned long long>(lin[0], 0x7FFFFFFF);
+      info[3] = (int32_t)std::min<unsigned long long>(lin[1], 0x7FFFFFFF);
+      continue;
+    }
+    if (io->mode == 2) info[2] = nseg;
+    if (io->mode != 2 || nseg == 1) {
+      if (literal) GCHK(gpu::d2h(io->pos + io->pos_off[c], d_pos, j * 8, p.stream));
+      else GCHK(gpu::d2h(io->pos + io->pos_off[c], d_dig, ndig * 8, p.stream));
+    }
+    const uint64_t ns = io->sample_off ? io->sample_off[c + 1] - io->sample_off[c] : 0;
+    if (ns && io->mode != 2 && info[1] == 0) {
+      GCHK(gpu::h2d(d_sk, io->sample_k + io->sample_off[c], ns * 8, p.stream));
+      GPU_LAUNCH(p.stream, k_probe_sample, grid_for(ns, kProbeThreads), kProbeThreads, (const ChainTable *)d_tb, (const uint64_t *)d_sk, ns, d_so);
+      GCHK(gpu::d2h(io->sample_pos + io->sample_off[c], d_so, ns * 8, p.stream));
+    }
+    GCHK(gpu::sync(p.stream));
+    GCHK(gpu::last_error());
+  }
+  return PPCSR_OK;
+}
+
 // double_list / half_list alone (PCSR.cpp:251-320): the array is doubled and halved back `iters` times; device time of the
 // passes (tile sums, position table, fused scatter into the fresh array), allocations and the final synchronisation outside.
 // The array ends at its original size, evenly spread.

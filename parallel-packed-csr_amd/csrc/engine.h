@@ -38,6 +38,22 @@ struct EngineStats {
   uint64_t narrow;         // 1: sorted, disjoint vertex ranges (64-ary search narrowing + parallel rounds); 0: sequential regime
 };
 
+// ppcsr_debug_chain_probe (include/ppcsr.h: ppcsr_chain_probe_io, same layout)
+struct ChainProbeIO {
+  int32_t mode;
+  uint32_t grid;
+  uint64_t ncases;
+  const uint64_t *cases;
+  const uint64_t *pos_off;
+  uint64_t *pos;
+  const uint64_t *sample_off;
+  const uint64_t *sample_k;
+  uint64_t *sample_pos;
+  int32_t *info;
+  uint64_t *segs;
+  uint32_t *wg;
+};
+
 class Engine {
  public:
   static int create(uint32_t init_n, uint32_t src_n, int lock_search, int device, Engine **out, std::string *errmsg = nullptr);
@@ -83,6 +99,7 @@ class Engine {
   int set_option(const char *key, int64_t value);
   int rebalance_bench(uint64_t wlen, int iters, double *ms_per_call);
   int resize_bench(int iters, double *double_ms, double *half_ms);
+  int chain_probe(const ChainProbeIO *io);  // the position-chain functions run on the device, engine state untouched
   int snapshot();  // device-side copy of the whole state (items, nodes, leaf counts, geometry)
   int restore();   // back to the last snapshot (device-to-device)  // whole-window rebalance kernel timing
 

@@ -2,6 +2,7 @@
 //   pma_rounds.h       strict prefix rounds (k_plan / k_check / k_apply) and the exclusive executor (k_exclusive)
 //   pma_spec_rounds.h  speculative rounds (o_plan / o_check / o_apply / o_big / o_settle): the default scheduler
 //   pma_rebalance.h    whole-array / big-window rebalance, in-place window rebalance, snapshots, maintenance
+//   pma_probe.h        debugging probe of the position chain (ppcsr_debug_chain_probe)
 //   pma_scan.h         queries, bulk neighbour scan, bulk build, BFS / PageRank
 //   pma_paths.h        shortest paths over the edge values, weakly connected components
 //   pma_query.h        batched reads: edge lookups with values, neighbourhood gathers
@@ -10,6 +11,7 @@
 #include "pma_rounds.h"
 #include "pma_spec_rounds.h"
 #include "pma_rebalance.h"
+#include "pma_probe.h"
 #include "pma_scan.h"
 #include "pma_paths.h"
 #include "pma_query.h"

@@ -505,7 +505,7 @@ PMA_KERNEL void k_rb_tilesums(uint32_t *cnt, uint64_t nleaves, uint32_t tile_lea
 // the window crosses, 23 for 2^24 slots: ~10 us on one lane, which the whole-array rebalance used to spend in front of its
 // scatter launch.  Its first segment covers the top HALF of the positions, the second the next quarter ...: with the tiles taken
 // from the top of the window down, a builder thread inside the scatter launch (workgroup 0) stays ahead of them.  Every
-// finished segment is published — its six words and then the count, at agent scope, word by word: plain stores may sit in the
+// finished segment is published — its six words, a wait until they are acknowledged, then the count, at agent scope, word by word: plain stores may sit in the
 // builder's XCD L2 — and a workgroup copies the table to its LDS once the published part covers the chain steps its tile needs.
 // A workgroup that waits too long (it never does: workgroup 0 is dispatched first) builds the table itself: no hang, no error path.
 PMA_DEV void build_chain_table_publish(ChainTable *tb) {  // one thread; index / len / j are in the header already
@@ -526,12 +526,16 @@ PMA_DEV void build_chain_table_publish(ChainTable *tb) {  // one thread; index /
     if (c > T - t) c = T - t;
     sg.count = c;
     unsigned long long *out = reinterpret_cast<unsigned long long *>(&tb->seg[nseg]);
-    const unsigned long long *in = reinterpret_cast<const unsigned long long *>(&sg);
+    unsigned long long in[sizeof(ChainSeg) / 8];  // (copied, not aliased: read through a pointer of another type, the compiler
+    __builtin_memcpy(in, &sg, sizeof(ChainSeg));  //  may take the words before sg.count is set — the emulator build did)
 #pragma unroll
     for (int q = 0; q < (int)(sizeof(ChainSeg) / 8); q++) wv::store_agent_u64(out + q, in[q]);
     nseg++;
     t += c;
     const bool done = t >= T || nseg >= kMaxSeg;
+    // (the segment's words have LANDED before the count that announces them is stored — stores to different addresses may
+    //  otherwise become visible in any order, and a reader that sees the count copies the words)
+    wv::wait_loads();
     wv::store_agent_u64(reinterpret_cast<unsigned long long *>(&tb->pub_nseg),
                         (unsigned long long)((uint32_t)nseg | (done ? kTbDone : 0u)) | ((unsigned long long)(uint32_t)(t + 1) << 32));
     if (done) return;

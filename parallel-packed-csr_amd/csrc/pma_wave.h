@@ -79,7 +79,9 @@ PMA_DEV uint32_t atomic_cas_u32(uint32_t *p, uint32_t expect, uint32_t v) { retu
 // agent-scope loads (a plain load may be served from a stale line of this XCD's L2 for ever).  No data travels with the
 // flag (the poller only WRITES afterwards), so neither side needs a release / acquire: at agent scope those are an L2
 // write-back and a cache invalidate per workgroup, which made the kernel 4x slower than the copy it replaces.
-// every global load this wave has issued has returned (a workgroup barrier alone does not wait for vmcnt)
+// every global load this wave has issued has returned (a workgroup barrier alone does not wait for vmcnt) — and, vmcnt counting
+// stores as well on gfx9, every store it has issued has been acknowledged: the drain in front of a word that PUBLISHES data
+// stored before it (build_chain_table_publish); the "memory" clobber keeps the compiler from moving a store across it
 PMA_DEV void wait_loads() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 PMA_DEV void flag_publish(uint32_t *p, uint32_t v) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -67,3 +67,15 @@ extern "C" int ppcsr_sim_chain_positions(uint64_t index, uint64_t len, uint64_t 
   if (linear_ok) *linear_ok = ok;
   return 0;
 }
+
+// test hook (emulator build only): the integer fix-up of the table build's division fed with estimates that are off by `err` in
+// either direction (the emulator's own division takes the exact branch, so the fix-up loops never run otherwise).  The estimate is
+// clamped at 0 and at the largest quotient whose product with b stays below 2^63 (the fix-up's precondition)
+extern "C" void ppcsr_sim_div_fixup(const uint64_t *ab, uint64_t n, uint64_t err, int above, uint64_t *out) {
+  for (uint64_t i = 0; i < n; i++) {
+    const uint64_t a = ab[2 * i], b = ab[2 * i + 1], q = a / b, top = ((1ull << 63) - 1) / b;
+    uint64_t est = above ? q + err : (q > err ? q - err : 0);
+    if (est > top) est = top;
+    out[i] = ppcsr::div_floor_fixup(a, b, est);
+  }
+}

@@ -53,6 +53,7 @@ def _load_oracle():
     L.po_import_state.restype = c_vp
     L.po_import_state.argtypes = [c_u64, c_vp, c_u32, c_vp, c_int]
     L.po_redistribute_positions.argtypes = [c_u64, c_u64, c_u64, c_vp]
+    L.po_redistribute_positions_digest.argtypes = [c_u64, c_u64, c_u64, c_int, c_vp, c_u64, c_vp, c_vp, c_vp]
     L.pop_create.restype = c_vp
     L.pop_create.argtypes = [c_u32, c_u32, c_int, c_int, c_int]
     L.pop_destroy.argtypes = [c_vp]

@@ -437,7 +437,8 @@ def test_sim_consumers_bfs_pagerank(sim, streams):
 
 def test_chain_table_matches_serial_fp64_chain():
     """the piecewise-linear position table (built with the fp64-reciprocal division) == the oracle's serial `x -= step`
-    chain (PCSR.cpp:237-247), for windows up to 2^31 slots and densities across the PMA's range"""
+    chain (PCSR.cpp:237-247), for windows of up to 2^24 slots at densities across the PMA's range and sparse ones of 2^30 and
+    2^31 slots (tests/chain_cases.py; where the reference's chain stops being a placement: DESIGN.md, Exact positions)"""
     import ctypes
     from oracle_lib import oracle_lib
     build_sim()
@@ -445,25 +446,9 @@ def test_chain_table_matches_serial_fp64_chain():
     c_u64 = ctypes.c_uint64
     lib.ppcsr_sim_chain_positions.argtypes = [c_u64, c_u64, c_u64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
                                               ctypes.POINTER(ctypes.c_int)]
+    from chain_cases import legacy_cases
     L = oracle_lib()
-    rng = np.random.default_rng(5)
-    cases = [(0, 1 << 24, 10_000_000), (0, 1 << 24, 4_194_305), (1 << 30, 1 << 30, 3_000_001), (0, 1 << 31, 2_500_000),
-             (4096, 4096, 4095), (0, 8, 1), (0, 8, 2), (64, 64, 64), (12288, 8192, 3), (16384, 8192, 3), (8192, 8192, 7000)]
-    for _ in range(60):
-        lg = int(rng.integers(3, 25))
-        ln = 1 << lg
-        idx = int(rng.integers(0, 1 << (30 - lg))) * ln
-        j = int(rng.integers(1, ln + 1))
-        cases.append((idx, ln, j))
-    # the windows ONE wave / one workgroup rebalances (closed form without the division): small windows at every kind of
-    # start — slot 0, powers of two (the window fills its binade from the bottom), other multiples — and every fill
-    for _ in range(2500):
-        lg = int(rng.integers(3, 11))
-        ln = 1 << lg
-        kind = int(rng.integers(0, 4))
-        idx = 0 if kind == 0 else ((1 << int(rng.integers(lg, 31))) if kind == 1 else int(rng.integers(1, 1 << (31 - lg))) * ln)
-        j = int(rng.integers(1, ln + 1)) if rng.integers(0, 4) else int(rng.choice([1, 2, 3, 4, ln - 1, ln]))
-        cases.append((idx, ln, max(j, 1)))
+    cases = legacy_cases()  # (tests/chain_cases.py: the list this test has always run, shared with the device probe's tests)
     for idx, ln, j in cases:
         ref = np.zeros(j, np.uint64)
         got = np.zeros(j, np.uint64)
