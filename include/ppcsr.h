@@ -139,6 +139,26 @@ int ppcsr_pagerank(ppcsr_t h, const float *node_values, float *out, double *devi
 #define PPCSR_NO_PATH 0xFFFFFFFFFFFFFFFFull
 int ppcsr_sssp(ppcsr_t h, uint32_t start, uint64_t *dist, double *device_ms);
 int ppcsr_components(ppcsr_t h, uint32_t *labels, double *device_ms);
+/* Two consumers that intersect two neighbourhoods, over the same edge set (live slots of every vertex's (beginning, end), slot
+ * N - 1 excluded, destinations >= n skipped; a (src, dst) pair is stored at most once).  A vertex's live slots lie in
+ * ascending destination order, so the neighbourhoods are intersected in place: no export, no sort.
+ * triangles — counted in the upper orientation: the undirected graph G has the edge {a, b}, a < b, exactly when the pair
+ *   (a, b) is stored; stored pairs with src > dst and self-loops play no part.  A triangle is a triple a < b < c with (a, b),
+ *   (a, c) and (b, c) all stored.  tri[v] = triangles that contain v (n entries, 64-bit: a hub's count can pass 2^32; may be
+ *   NULL), *total = triangles = sum(tri) / 3 (may be NULL, not both).  This is the exact triangle count of a graph stored
+ *   symmetrically (both directions inserted) and of a graph stored as its upper triangle; for any other state it is still
+ *   one well-defined number.
+ * common_neighbours — counts[i] = |{c < n : (a[i], c) stored and (b[i], c) stored}| for k pairs: directed out-neighbourhoods,
+ *   no orientation filter, a self-loop is an ordinary stored edge.  a[i] >= n or b[i] >= n gives 0 (not EINVAL); a[i] == b[i]
+ *   gives the number of stored destinations < n; repeats are allowed.  The host form stages the pairs through bounded buffers
+ *   ("query_lookup_stage" pairs per round trip); the _device form takes every array in this GPU's HBM.
+ * Both results are unique.  Same contract as bfs: synchronous, write nothing to the graph, device_ms may be NULL.
+ * EINVAL: null handle, tri and total both NULL, a / b / counts NULL with k > 0.  EUNSUPPORTED: the structure is in the
+ * sequential regime (stats.narrow == 0: add_node after a doubling, vertex ranges may be unsorted or overlapping until the
+ * next range re-check) — sorted ranges cannot be intersected then, and no number is returned; ppcsr_last_error says so. */
+int ppcsr_triangles(ppcsr_t h, uint64_t *tri, uint64_t *total, double *device_ms);
+int ppcsr_common_neighbours(ppcsr_t h, const uint32_t *a, const uint32_t *b, uint64_t k, uint32_t *counts, double *device_ms);
+int ppcsr_common_neighbours_device(ppcsr_t h, const uint32_t *d_a, const uint32_t *d_b, uint64_t k, uint32_t *d_counts, double *device_ms);
 /* raw state for parity checks: items[N], nodes[n] exactly as the reference holds them (PCSR.h:67,128) */
 int ppcsr_export_state(ppcsr_t h, ppcsr_edge *items, ppcsr_node *nodes);
 int ppcsr_stats(ppcsr_t h, ppcsr_stats_t *out);
@@ -156,7 +176,7 @@ int ppcsr_stats(ppcsr_t h, ppcsr_stats_t *out);
  *   measuring  "profile" (1: HIP events around every round kernel, reported through ppcsr_stats), "diag" (1: why updates
  *              did not commit, per epoch, on stderr; 2: also a per-update dependency trace, PPCSR_DIAG_DUMP = file), "marker" (marker kernels for profile cuts), "test_block_rebalance"
  *   reads      test hooks that move the seams of the batched reads (defaults = the shipped sizes; values in [1, 2^32]):
- *              "query_lookup_stage" (host lookups per H2D / D2H round trip; 2^22), "query_gather_rows" (queried vertices
+ *              "query_lookup_stage" (host lookups — and host common-neighbour pairs — per H2D / D2H round trip; 2^22), "query_gather_rows" (queried vertices
  *              per gather block; 2^20), "query_gather_chunks" (64-slot chunks per gather block; 2^22), "query_gather_stage"
  *              (edges per D2H window of a host gather; 2^22) */
 int ppcsr_set_option(ppcsr_t h, const char *key, int64_t value);
@@ -260,6 +280,12 @@ int pppcsr_pagerank(pppcsr_t h, const float *node_values, float *out, double *de
  * device — there is no host form of these two calls. */
 int pppcsr_sssp(pppcsr_t h, uint32_t start, uint64_t *dist, double *device_ms);
 int pppcsr_components(pppcsr_t h, uint32_t *labels, double *device_ms);
+/* ppcsr_triangles / ppcsr_common_neighbours over the GLOBAL vertex ids (tri: pppcsr_get_n entries), one device call over every
+ * partition's array: a pair may have its two vertices in different partitions, and the results do not depend on the
+ * partitioning.  Same contract as pppcsr_bfs.  EINVAL: as the single calls, or a partition not resident in this process.
+ * EUNSUPPORTED: the partitions sit on more than one device, or any partition is in the sequential regime. */
+int pppcsr_triangles(pppcsr_t h, uint64_t *tri, uint64_t *total, double *device_ms);
+int pppcsr_common_neighbours(pppcsr_t h, const uint32_t *a, const uint32_t *b, uint64_t k, uint32_t *counts, double *device_ms);
 /* bucket a host stream by owner (stable: per-partition order == stream order, src made partition-local as in
  * PPPCSR.cpp:46-52) and apply each bucket on its partition's GPU */
 int pppcsr_apply_batch(pppcsr_t h, const ppcsr_op *ops, uint64_t n);

@@ -66,6 +66,7 @@ EXPORTED = [
     "ppcsr_gather_neighbourhoods_device", "pppcsr_lookup_edges", "pppcsr_gather_neighbourhoods", "pppcsr_set_option",
     "pppcsr_bfs", "pppcsr_pagerank", "ppcsr_sssp", "ppcsr_components", "pppcsr_sssp", "pppcsr_components",
     "ppcsr_debug_chain_probe",
+    "ppcsr_triangles", "pppcsr_triangles", "ppcsr_common_neighbours", "ppcsr_common_neighbours_device", "pppcsr_common_neighbours",
 ]
 
 NO_PATH = 0xFFFFFFFFFFFFFFFF  # PPCSR_NO_PATH: what sssp reports for a vertex no path reaches
@@ -134,6 +135,10 @@ def load_library(path=None):
         getattr(L, name).argtypes = [c_vp, c_u32, c_vp, ctypes.POINTER(ctypes.c_double)]
     for name in ("ppcsr_components", "pppcsr_components"):
         getattr(L, name).argtypes = [c_vp, c_vp, ctypes.POINTER(ctypes.c_double)]
+    for name in ("ppcsr_triangles", "pppcsr_triangles"):
+        getattr(L, name).argtypes = [c_vp, c_vp, ctypes.POINTER(c_u64), ctypes.POINTER(ctypes.c_double)]
+    for name in ("ppcsr_common_neighbours", "ppcsr_common_neighbours_device", "pppcsr_common_neighbours"):
+        getattr(L, name).argtypes = [c_vp, c_vp, c_vp, c_u64, c_vp, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_bulk_build.argtypes = [c_vp, c_vp, c_u64, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_bfs.argtypes = [c_vp, c_u32, c_vp, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_pagerank.argtypes = [c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_double)]
@@ -206,6 +211,23 @@ def _lookup(fn, h, src, dst):
     assert s.size == d.size, "src and dst must have the same length"
     out = np.empty(s.size, np.uint32)
     return fn(h, s.ctypes.data, d.ctypes.data, s.size, out.ctypes.data), out
+
+
+def _triangles(obj, fn, per_vertex, with_ms):
+    """(tri, total[, ms]): tri is None unless per_vertex"""
+    tri = np.empty(obj.get_n(), np.uint64) if per_vertex else None
+    total, ms = c_u64(), ctypes.c_double(0.0)
+    obj._chk(fn(obj.h, tri.ctypes.data if per_vertex else None, ctypes.byref(total), ctypes.byref(ms)))
+    return (tri, total.value, ms.value) if with_ms else (tri, total.value)
+
+
+def _common(obj, fn, a, b, with_ms):
+    a, b = _u32(a), _u32(b)
+    assert a.size == b.size, "a and b must have the same length"
+    out = np.empty(a.size, np.uint32)
+    ms = ctypes.c_double(0.0)
+    obj._chk(fn(obj.h, a.ctypes.data, b.ctypes.data, a.size, out.ctypes.data, ctypes.byref(ms)))
+    return (out, ms.value) if with_ms else out
 
 
 def _gather(fn, h, vertices, with_values):
@@ -355,6 +377,21 @@ class PCSR:
         ms = ctypes.c_double(0.0)
         self._chk(self.L.ppcsr_components(self.h, out.ctypes.data, ctypes.byref(ms)))
         return (out, ms.value) if with_ms else out
+
+    def triangles(self, per_vertex=True, with_ms=False):
+        """(tri, total): triangles through every vertex (uint64; None unless per_vertex) and their number, counted in the
+        upper orientation ({a, b}, a < b, is an edge exactly when (a, b) is stored: include/ppcsr.h)"""
+        return _triangles(self, self.L.ppcsr_triangles, per_vertex, with_ms)
+
+    def common_neighbours(self, a, b, with_ms=False):
+        """counts[i] = stored destinations < n that a[i] and b[i] share (uint32; vertices >= n give 0)"""
+        return _common(self, self.L.ppcsr_common_neighbours, a, b, with_ms)
+
+    def common_neighbours_device(self, a_ptr, b_ptr, k, out_ptr, with_ms=False):
+        """the same, pairs and counts in this GPU's memory (e.g. tensor.data_ptr())"""
+        ms = ctypes.c_double(0.0)
+        self._chk(self.L.ppcsr_common_neighbours_device(self.h, a_ptr, b_ptr, k, out_ptr, ctypes.byref(ms)))
+        return ms.value if with_ms else None
 
     def geometry(self):
         N, lg, H = c_u64(), c_int(), c_int()
@@ -605,6 +642,15 @@ class PPPCSR:
         ms = ctypes.c_double(0.0)
         self._chk(self.L.pppcsr_components(self.h, out.ctypes.data, ctypes.byref(ms)))
         return (out, ms.value) if with_ms else out
+
+    def triangles(self, per_vertex=True, with_ms=False):
+        """(tri, total): triangles through every vertex (uint64; None unless per_vertex) and their number, counted in the
+        upper orientation ({a, b}, a < b, is an edge exactly when (a, b) is stored: include/ppcsr.h)"""
+        return _triangles(self, self.L.pppcsr_triangles, per_vertex, with_ms)
+
+    def common_neighbours(self, a, b, with_ms=False):
+        """counts[i] = stored destinations < n that a[i] and b[i] share (uint32; vertices >= n give 0)"""
+        return _common(self, self.L.pppcsr_common_neighbours, a, b, with_ms)
 
     def set_option(self, key, value):
         """sizes of the batched reads: "query_block", "gather_stage" (include/ppcsr.h: pppcsr_set_option)"""

@@ -172,6 +172,21 @@ int ppcsr_components(ppcsr_t h, uint32_t *labels, double *device_ms) {
   if (!labels) return bad("components: null output");
   return ret(h->e, h->e->components(labels, device_ms));
 }
+int ppcsr_triangles(ppcsr_t h, uint64_t *tri, uint64_t *total, double *device_ms) {
+  H_CHECK();
+  if (!tri && !total) return bad("triangles: null outputs");
+  return ret(h->e, h->e->triangles(tri, total, device_ms));
+}
+int ppcsr_common_neighbours(ppcsr_t h, const uint32_t *a, const uint32_t *b, uint64_t k, uint32_t *counts, double *device_ms) {
+  H_CHECK();
+  if (k && (!a || !b || !counts)) return bad("common_neighbours: null argument");
+  return ret(h->e, h->e->common_neighbours(a, b, k, counts, false, device_ms));
+}
+int ppcsr_common_neighbours_device(ppcsr_t h, const uint32_t *d_a, const uint32_t *d_b, uint64_t k, uint32_t *d_counts, double *device_ms) {
+  H_CHECK();
+  if (k && (!d_a || !d_b || !d_counts)) return bad("common_neighbours: null argument");
+  return ret(h->e, h->e->common_neighbours(d_a, d_b, k, d_counts, true, device_ms));
+}
 int ppcsr_export_state(ppcsr_t h, ppcsr_edge *items, ppcsr_node *nodes) {
   H_CHECK();
   return ret(h->e, h->e->export_state(reinterpret_cast<ppcsr::Edge *>(items), reinterpret_cast<ppcsr::Node *>(nodes)));
@@ -687,6 +702,28 @@ int pppcsr_components(pppcsr_t h, uint32_t *labels, double *device_ms) {
   pppcsr_get_n(h, &n);
   Engine *e = refs[0].e;
   return ret(e, e->components_over(refs.data(), (uint32_t)refs.size(), (uint32_t)n, labels, device_ms));
+}
+int pppcsr_triangles(pppcsr_t h, uint64_t *tri, uint64_t *total, double *device_ms) {
+  PP_CHECK();
+  if (!tri && !total) return bad("triangles: null outputs");
+  std::vector<ppcsr::ConsumerRef> refs;
+  int rc = consumer_parts(h, &refs);
+  if (rc != 0) return rc;
+  uint64_t n = 0;
+  pppcsr_get_n(h, &n);
+  Engine *e = refs[0].e;
+  return ret(e, e->triangles_over(refs.data(), (uint32_t)refs.size(), (uint32_t)n, tri, total, device_ms));
+}
+int pppcsr_common_neighbours(pppcsr_t h, const uint32_t *a, const uint32_t *b, uint64_t k, uint32_t *counts, double *device_ms) {
+  PP_CHECK();
+  if (k && (!a || !b || !counts)) return bad("common_neighbours: null argument");
+  std::vector<ppcsr::ConsumerRef> refs;
+  int rc = consumer_parts(h, &refs);
+  if (rc != 0) return rc;
+  uint64_t n = 0;
+  pppcsr_get_n(h, &n);
+  Engine *e = refs[0].e;
+  return ret(e, e->common_neighbours_over(refs.data(), (uint32_t)refs.size(), (uint32_t)n, a, b, k, counts, false, device_ms));
 }
 
 int pppcsr_apply_parts_device(pppcsr_t h, uint64_t first_part, uint64_t n_parts, const ppcsr_op *const *d_ops, const uint64_t *counts) {

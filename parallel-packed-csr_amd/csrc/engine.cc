@@ -2402,6 +2402,123 @@ int Engine::components_over(const ConsumerRef *parts, uint32_t P, uint32_t total
   return PPCSR_OK;
 }
 
+// Triangle counts and common-neighbour counts (pma_intersect.h).  Both intersect vertex ranges as sorted lists, which holds
+// in the regular regime only: a partition in the sequential regime (narrow == 0: ranges may be unsorted or overlapping until
+// the next re-check) is refused rather than answered on a wrong assumption.
+int Engine::intersect_regime(const ConsumerRef *parts, uint32_t P, const char *what, std::string *msg) {
+  for (uint32_t k = 0; k < P; k++)
+    if (parts[k].e->p_->v.g.narrow == 0u) {
+      *msg = std::string(what) + ": the structure is in the sequential regime (add_node after a doubling: vertex ranges may be unsorted "
+             "or overlapping, stats.narrow == 0) and sorted ranges cannot be intersected; it ends at the next range re-check";
+      return PPCSR_EUNSUPPORTED;
+    }
+  return PPCSR_OK;
+}
+int Engine::triangles(uint64_t *tri, uint64_t *total, double *device_ms) {
+  const ConsumerRef self{this, 0};
+  return triangles_over(&self, 1, n(), tri, total, device_ms);
+}
+int Engine::triangles_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint64_t *tri, uint64_t *total, double *device_ms) {
+  Impl &p = *p_;
+  GCHK(gpu::set_device(device_));
+  const uint32_t nn = total_n;
+  std::string msg;
+  if (intersect_regime(parts, P, "triangles", &msg) != PPCSR_OK) return fail(PPCSR_EUNSUPPORTED, msg);
+  unsigned long long *d_tri = nullptr, *d_tot = nullptr;
+  uint32_t *d_list = nullptr, *d_cnt = nullptr;
+  ConsumerPart *d_tab = nullptr;
+  DevGuard tmpg;
+  tmpg.add(&d_tri); tmpg.add(&d_tot); tmpg.add(&d_list); tmpg.add(&d_cnt); tmpg.add(&d_tab);
+  uint64_t N = 0;
+  int rc = consumer_table(parts, P, nn, (void **)&d_tab, &N);
+  if (rc != PPCSR_OK) return rc;
+  const ConsumerPart *tab = d_tab;
+  uint64_t chunks = 0;
+  for (uint32_t k = 0; k < P; k++) chunks += (parts[k].e->N() + 63) / 64;
+  if (chunks >= (1ull << 32)) return fail(PPCSR_EUNSUPPORTED, "triangles: more than 2^32 chunks");
+  constexpr uint32_t tot_words = kBfsStripes * kTriStripeWords;
+  if (tri) GCHK(gpu::dmalloc((void **)&d_tri, std::max<uint64_t>(nn, 1) * sizeof(unsigned long long)));
+  GCHK(gpu::dmalloc((void **)&d_tot, tot_words * sizeof(unsigned long long)));
+  GCHK(gpu::dmalloc((void **)&d_list, std::max<uint64_t>(chunks, 1) * sizeof(uint32_t)));  // chunks that hold an edge with a long range
+  GCHK(gpu::dmalloc((void **)&d_cnt, 32 * sizeof(uint32_t)));
+  p.timer.start(p.stream);
+  if (tri) GCHK(gpu::dset(d_tri, 0, std::max<uint64_t>(nn, 1) * sizeof(unsigned long long), p.stream));
+  GCHK(gpu::dset(d_tot, 0, tot_words * sizeof(unsigned long long), p.stream));
+  GCHK(gpu::dset(d_cnt, 0, 32 * sizeof(uint32_t), p.stream));
+  GPU_LAUNCH(p.stream, k_tri_edges, grid_for(chunks, 4, 8192), 256, tab, P, nn, d_tri, d_tot, d_list, d_cnt);
+  uint32_t ndefer = 0;
+  GCHK(gpu::d2h(&ndefer, d_cnt, sizeof(uint32_t), p.stream));
+  GCHK(gpu::sync(p.stream));
+  GCHK(gpu::last_error());
+  if (ndefer) GPU_LAUNCH(p.stream, k_tri_long, grid_for((uint64_t)ndefer * 4, 1, 16384), 256, tab, P, nn, d_tri, d_tot, (const uint32_t *)d_list, ndefer);
+  p.timer.stop(p.stream);
+  std::vector<unsigned long long> h_tot(tot_words, 0);
+  GCHK(gpu::d2h(h_tot.data(), d_tot, tot_words * sizeof(unsigned long long), p.stream));
+  if (tri && nn) GCHK(gpu::d2h(tri, d_tri, (uint64_t)nn * sizeof(unsigned long long), p.stream));
+  GCHK(gpu::sync(p.stream));
+  GCHK(gpu::last_error());
+  if (total) {
+    *total = 0;
+    for (uint32_t k = 0; k < kBfsStripes; k++) *total += h_tot[(uint64_t)k * kTriStripeWords];
+  }
+  if (device_ms) *device_ms = p.timer.ms();
+  return PPCSR_OK;
+}
+
+// pairs and counts: host memory (staged through the buffers of lookup_edges, lookup_stage pairs at a time), or this GPU's
+int Engine::common_neighbours(const uint32_t *a, const uint32_t *b, uint64_t k, uint32_t *counts, bool on_device, double *device_ms) {
+  const ConsumerRef self{this, 0};
+  return common_neighbours_over(&self, 1, n(), a, b, k, counts, on_device, device_ms);
+}
+int Engine::common_neighbours_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const uint32_t *a, const uint32_t *b, uint64_t nq,
+                                   uint32_t *counts, bool on_device, double *device_ms) {
+  Impl &p = *p_;
+  GCHK(gpu::set_device(device_));
+  std::string msg;
+  if (intersect_regime(parts, P, "common_neighbours", &msg) != PPCSR_OK) return fail(PPCSR_EUNSUPPORTED, msg);
+  if (device_ms) *device_ms = 0.0;
+  ConsumerPart *d_tab = nullptr;
+  DevGuard tmpg;
+  tmpg.add(&d_tab);
+  uint64_t N = 0;
+  int rc = consumer_table(parts, P, total_n, (void **)&d_tab, &N);
+  if (rc != PPCSR_OK) return rc;
+  if (nq == 0) return PPCSR_OK;
+  const ConsumerPart *tab = d_tab;
+  if (on_device) {
+    p.timer.start(p.stream);
+    GPU_LAUNCH(p.stream, k_common_neighbours, query_blocks(p, (nq + 63) / 64), 256, tab, P, total_n, a, b, nq, counts);
+    p.timer.stop(p.stream);
+    GCHK(gpu::sync(p.stream));
+    if (device_ms) *device_ms = p.timer.ms();
+  } else {
+    const uint64_t stage = std::min(nq, p.q.lookup_stage);
+    if (stage > p.q.lookup_cap) {
+      uint64_t c0 = p.q.lookup_cap, c1 = p.q.lookup_cap, c2 = p.q.lookup_cap;
+      if (grow_buf(&p.q.src, &c0, stage) || grow_buf(&p.q.dst, &c1, stage) || grow_buf(&p.q.val, &c2, stage)) {
+        p.q.lookup_cap = 0;
+        return fail(PPCSR_ENOMEM, "common_neighbours: staging");
+      }
+      p.q.lookup_cap = stage;
+    }
+    for (uint64_t i0 = 0; i0 < nq; i0 += stage) {
+      const uint64_t m = std::min(stage, nq - i0);
+      GCHK(gpu::h2d(p.q.src, a + i0, m * sizeof(uint32_t), p.stream));
+      GCHK(gpu::h2d(p.q.dst, b + i0, m * sizeof(uint32_t), p.stream));
+      p.timer.start(p.stream);
+      GPU_LAUNCH(p.stream, k_common_neighbours, query_blocks(p, (m + 63) / 64), 256, tab, P, total_n, (const uint32_t *)p.q.src,
+                 (const uint32_t *)p.q.dst, m, p.q.val);
+      p.timer.stop(p.stream);
+      GCHK(gpu::d2h(counts + i0, p.q.val, m * sizeof(uint32_t), p.stream));
+      GCHK(gpu::sync(p.stream));
+      if (device_ms) *device_ms += p.timer.ms();
+    }
+  }
+  GCHK(gpu::sync(p.stream));
+  GCHK(gpu::last_error());
+  return PPCSR_OK;
+}
+
 // stable sort of (key, value) pairs by key: rocPRIM's radix sort on the device, std::stable_sort in the CPU emulator
 static int sort_pairs_stable(gpu::stream_t st, uint32_t *kin, uint32_t *kout, float *vin, float *vout, uint64_t m, unsigned bits) {
 #if defined(PPCSR_SIM)

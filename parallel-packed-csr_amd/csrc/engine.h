@@ -93,6 +93,16 @@ class Engine {
   int components(uint32_t *labels, double *device_ms);
   int sssp_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t start, uint64_t *dist, double *device_ms);
   int components_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t *labels, double *device_ms);
+  // consumers that intersect two neighbourhoods (pma_intersect.h), under the same contract.  triangles: upper orientation —
+  // {a, b}, a < b, is an edge exactly when (a, b) is stored; tri (total_n entries, may be null): triangles through every
+  // vertex; *total (may be null): triangles.  common_neighbours: counts[i] = stored dests < total_n shared by a[i] and b[i]
+  // (vertices >= total_n: 0); a, b, counts are host memory, or this GPU's when on_device.  Both fail with PPCSR_EUNSUPPORTED
+  // while a partition is in the sequential regime (narrow == 0).
+  int triangles(uint64_t *tri, uint64_t *total, double *device_ms);
+  int triangles_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint64_t *tri, uint64_t *total, double *device_ms);
+  int common_neighbours(const uint32_t *a, const uint32_t *b, uint64_t k, uint32_t *counts, bool on_device, double *device_ms);
+  int common_neighbours_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const uint32_t *a, const uint32_t *b, uint64_t k,
+                             uint32_t *counts, bool on_device, double *device_ms);
   int export_state(Edge *items, Node *nodes);
   int check_invariants(uint64_t *bad);  // leafcnt == recount(items)
   int stats(EngineStats *out);
@@ -139,6 +149,7 @@ class Engine {
   // the bulk scan of `part`'s array in two halves, launched on THIS engine's stream with part's scratch: the chunk counts and
   // tile sums (edge total in part's d_total), then the writing pass
   int scan_count(Engine *part, uint32_t *tile, uint64_t *ntiles);
+  int intersect_regime(const ConsumerRef *parts, uint32_t P, const char *what, std::string *msg);
   int consumer_table(const ConsumerRef *parts, uint32_t P, uint32_t total_n, void **d_tab, uint64_t *slots);
   void scan_write(Engine *part, uint32_t tile, uint64_t ntiles, unsigned long long *d_rows, int *d_dst, uint64_t cap, const float *d_values,
                   float *d_contrib, Op *d_triples, uint32_t src_base, uint32_t dest_bound);

@@ -5,6 +5,7 @@
 //   pma_probe.h        debugging probe of the position chain (ppcsr_debug_chain_probe)
 //   pma_scan.h         queries, bulk neighbour scan, bulk build, BFS / PageRank
 //   pma_paths.h        shortest paths over the edge values, weakly connected components
+//   pma_intersect.h    triangle counts and common-neighbour counts: sorted intersection of two gapped vertex ranges
 //   pma_query.h        batched reads: edge lookups with values, neighbourhood gathers
 //   pma_exchange.h     owner bucketing for the multi-GPU exchange
 #pragma once
@@ -14,5 +15,6 @@
 #include "pma_probe.h"
 #include "pma_scan.h"
 #include "pma_paths.h"
+#include "pma_intersect.h"
 #include "pma_query.h"
 #include "pma_exchange.h"
