@@ -222,6 +222,37 @@ typedef struct ppcsr_chain_probe_io {
   uint32_t *wg;
 } ppcsr_chain_probe_io;
 int ppcsr_debug_chain_probe(ppcsr_t h, const ppcsr_chain_probe_io *io);
+/* Debugging probe of the neighbourhood intersections (what ppcsr_triangles / ppcsr_common_neighbours stand on): the routines run ON
+ * THE DEVICE, alone, on slot ranges of one or two edge buffers of the call's own (the engine's state is neither read nor written).
+ * No reference equivalent.  cases: 6 words per case — (alo, ahi, blo, bhi, from_or_key, n): slot ranges [alo, ahi) of items_a and
+ * [blo, bhi) of items_b; items_b == NULL, or == items_a with len_b == len_a: both ranges lie in items_a (two vertices of one partition).
+ *   mode  what runs                                 launch shape                                       out[case]
+ *   0 lane         the one-lane intersection        one case per lane: 64 cases diverge in a wave      |{from <= c < n} in both ranges|
+ *   1 wave         the one-wave intersection        one wave per case, four per workgroup, one LDS     the same
+ *                  (merge and probe forms)          tile each (the triangle kernel's shape)
+ *   2 block        the one-workgroup intersection   one 256-thread workgroup per case                  the same (the four waves' shares added)
+ *                  (streamed and probed tiles)
+ *   3 lower_bound  the 64-sample search of [blo, bhi) for key, one wave per case                       first slot of [blo, bhi] behind which no
+ *                                                                                                      live slot holds a dest < key
+ *   4 probe        one lane's gap-aware binary search of [blo, bhi) for key, one case per lane         1: a live slot holds key, else 0
+ * A slot is live when its value is not 0; the live dests of every range must ascend (the caller's duty: nothing checks it here).
+ * tri: optional, modes 0-2: tri_n 64-bit words, zeroed by the call, tri[c] += 1 for every c counted by any case.
+ * EINVAL: a range that leaves its buffer, lo > hi, a case with n > tri_n while tri is asked for, tri with tri_n == 0, more than
+ * 2^20 cases, an unknown mode. */
+typedef struct ppcsr_isect_probe_io {
+  int32_t mode;
+  uint32_t reserved;
+  uint64_t ncases;
+  const uint32_t *cases;
+  const ppcsr_edge *items_a;
+  uint64_t len_a;
+  const ppcsr_edge *items_b;
+  uint64_t len_b;
+  uint32_t *out;
+  uint64_t *tri;
+  uint64_t tri_n;
+} ppcsr_isect_probe_io;
+int ppcsr_debug_isect_probe(ppcsr_t h, const ppcsr_isect_probe_io *io);
 /* PCSR::double_list / half_list (PCSR.cpp:251-282, 284-320) alone: the array is doubled and halved back `iters` times; device time
  * per call of each (measurement helper: the array ends at its original size, evenly spread) */
 int ppcsr_bench_resize(ppcsr_t h, int iters, double *double_ms, double *half_ms);

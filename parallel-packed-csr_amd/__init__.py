@@ -42,6 +42,13 @@ class ChainProbeIO(ctypes.Structure):
                 ("sample_off", c_vp), ("sample_k", c_vp), ("sample_pos", c_vp), ("info", c_vp), ("segs", c_vp), ("wg", c_vp)]
 
 
+class IsectProbeIO(ctypes.Structure):
+    """ppcsr_isect_probe_io (include/ppcsr.h)"""
+    _fields_ = [("mode", ctypes.c_int32), ("reserved", c_u32), ("ncases", c_u64), ("cases", c_vp), ("items_a", c_vp), ("len_a", c_u64),
+                ("items_b", c_vp), ("len_b", c_u64), ("out", c_vp), ("tri", c_vp), ("tri_n", c_u64)]
+
+
+ISECT_PROBE_MODES = {"lane": 0, "wave": 1, "block": 2, "lower_bound": 3, "probe": 4}
 CHAIN_PROBE_MODES = {"table": 0, "published": 1, "single": 2, "linear": 3, "segment": 4, "div": 5}
 CHAIN_PROBE_LITERAL_MAX = 1 << 22  # windows with more elements come back as one digest per 2^20 ranks
 CHAIN_PROBE_DIGEST_LOG = 20
@@ -65,7 +72,7 @@ EXPORTED = [
     "pppcsr_exchange_bulk_build", "ppcsr_lookup_edges", "ppcsr_lookup_edges_device", "ppcsr_gather_neighbourhoods",
     "ppcsr_gather_neighbourhoods_device", "pppcsr_lookup_edges", "pppcsr_gather_neighbourhoods", "pppcsr_set_option",
     "pppcsr_bfs", "pppcsr_pagerank", "ppcsr_sssp", "ppcsr_components", "pppcsr_sssp", "pppcsr_components",
-    "ppcsr_debug_chain_probe",
+    "ppcsr_debug_chain_probe", "ppcsr_debug_isect_probe",
     "ppcsr_triangles", "pppcsr_triangles", "ppcsr_common_neighbours", "ppcsr_common_neighbours_device", "pppcsr_common_neighbours",
 ]
 
@@ -151,6 +158,7 @@ def load_library(path=None):
     L.ppcsr_bench_scan_all.argtypes = [c_vp, ctypes.POINTER(c_dbl), ctypes.POINTER(c_u64)]
     L.ppcsr_bench_rebalance.argtypes = [c_vp, c_u64, c_int, ctypes.POINTER(c_dbl)]
     L.ppcsr_debug_chain_probe.argtypes = [c_vp, ctypes.POINTER(ChainProbeIO)]
+    L.ppcsr_debug_isect_probe.argtypes = [c_vp, ctypes.POINTER(IsectProbeIO)]
     L.ppcsr_bench_resize.argtypes = [c_vp, c_int, ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl)]
     L.ppcsr_strerror.restype = ctypes.c_char_p
     L.ppcsr_strerror.argtypes = [c_int]
@@ -512,6 +520,32 @@ class PCSR:
         if soff is not None:
             res["samples"] = [spos[int(soff[c]):int(soff[c + 1])] for c in range(n)]
         return res
+
+    def debug_isect_probe(self, mode, cases, items_a, items_b=None, tri_n=None):
+        """Debugging: the intersection routines of triangles / common_neighbours run alone on the device (ppcsr_debug_isect_probe);
+        engine state untouched.  mode "lane" / "wave" / "block": count of {from <= c < n} in both ranges; "lower_bound": the slot;
+        "probe": 0 or 1.  cases = (alo, ahi, blo, bhi, from_or_key, n) rows over items_a / items_b ((slots, 3) uint32 arrays of
+        (src, dest, value), value 0 = a null; items_b None: both ranges in items_a).  The live dests of every range must ascend:
+        asserted here.  tri_n: also return the uint64[tri_n] credits of all cases (intersecting modes) -> (out, tri)."""
+        m = ISECT_PROBE_MODES[mode]
+        cs = np.ascontiguousarray(np.asarray(cases, np.uint32).reshape(-1, 6))
+        ia = np.ascontiguousarray(items_a, np.uint32).reshape(-1, 3)
+        ib = ia if items_b is None else np.ascontiguousarray(items_b, np.uint32).reshape(-1, 3)
+        for buf, lo, hi in ((ia, cs[:, 0], cs[:, 1]), (ib, cs[:, 2], cs[:, 3])):
+            if len(cs) and np.all(lo <= hi) and int(hi.max()) <= len(buf):  # (anything else is the library's to refuse)
+                # a descent between two consecutive live slots, by index of the second one; no range may contain one
+                live = np.nonzero(buf[:, 2] != 0)[0]
+                desc = live[1:][buf[live[1:], 1].astype(np.int64) < buf[live[:-1], 1].astype(np.int64)]
+                prev = live[np.searchsorted(live, desc) - 1]
+                for q, pq in zip(desc.tolist(), prev.tolist()):
+                    assert not np.any((lo <= pq) & (q < hi)), f"live dests of a range descend at slot {q}"
+        out = np.zeros(len(cs), np.uint32)
+        tri = np.zeros(max(tri_n, 1), np.uint64) if tri_n is not None else None  # (tri_n == 0: the library refuses it)
+        io = IsectProbeIO(mode=m, ncases=len(cs), cases=cs.ctypes.data, items_a=ia.ctypes.data, len_a=len(ia),
+                          items_b=None if items_b is None else ib.ctypes.data, len_b=0 if items_b is None else len(ib),
+                          out=out.ctypes.data, tri=None if tri is None else tri.ctypes.data, tri_n=tri_n or 0)
+        self._chk(self.L.ppcsr_debug_isect_probe(self.h, ctypes.byref(io)))
+        return (out, tri[:tri_n]) if tri_n is not None else out
 
 
 class PPPCSR:

@@ -1,4 +1,5 @@
 // C ABI (include/ppcsr.h) over ppcsr::Engine.  No torch types, plain pointers and sizes.
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -217,6 +218,11 @@ static_assert(sizeof(ppcsr_chain_probe_io) == sizeof(ppcsr::ChainProbeIO), "layo
 int ppcsr_debug_chain_probe(ppcsr_t h, const ppcsr_chain_probe_io *io) {
   H_CHECK();
   return ret(h->e, h->e->chain_probe(reinterpret_cast<const ppcsr::ChainProbeIO *>(io)));
+}
+static_assert(sizeof(ppcsr_isect_probe_io) == sizeof(ppcsr::IsectProbeIO) && offsetof(ppcsr_isect_probe_io, tri_n) == offsetof(ppcsr::IsectProbeIO, tri_n), "layout");
+int ppcsr_debug_isect_probe(ppcsr_t h, const ppcsr_isect_probe_io *io) {
+  H_CHECK();
+  return ret(h->e, h->e->isect_probe(reinterpret_cast<const ppcsr::IsectProbeIO *>(io)));
 }
 int ppcsr_bench_rebalance(ppcsr_t h, uint64_t w, int iters, double *ms) { H_CHECK(); return ret(h->e, h->e->rebalance_bench(w, iters, ms)); }
 int ppcsr_bench_resize(ppcsr_t h, int iters, double *double_ms, double *half_ms) {

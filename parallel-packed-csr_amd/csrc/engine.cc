@@ -3081,6 +3081,70 @@ int Engine::chain_probe(const ChainProbeIO *io) {
   return PPCSR_OK;
 }
 
+// Debugging probe of the intersection routines (pma_isect_probe.h): the caller's edge buffers and case rows are copied into
+// buffers of the call's own and every case runs the production routine of its mode there, on the engine's stream.  Engine
+// state is not read.  Every range is checked against its buffer here, so that a bad case is an EINVAL and not a device fault.
+int Engine::isect_probe(const IsectProbeIO *io) {
+  Impl &p = *p_;
+  if (!io) return fail(PPCSR_EINVAL, "isect probe: no request");
+  if (io->mode < 0 || io->mode > 4) return fail(PPCSR_EINVAL, "isect probe: unknown mode");
+  const uint64_t nc = io->ncases;
+  if (nc > (1ull << 20)) return fail(PPCSR_EINVAL, "isect probe: more than 2^20 cases");
+  if (nc && (!io->cases || !io->out)) return fail(PPCSR_EINVAL, "isect probe: no cases or no output");
+  if (io->len_a >= kMax || io->len_b >= kMax) return fail(PPCSR_EINVAL, "isect probe: a buffer of 2^32 - 1 slots or more");
+  if ((io->len_a && !io->items_a) || (io->len_b && !io->items_b)) return fail(PPCSR_EINVAL, "isect probe: a buffer length without a buffer");
+  const bool same = !io->items_b || (io->items_b == io->items_a && io->len_b == io->len_a);  // both ranges in one buffer
+  const uint64_t len_a = io->len_a, len_b = same ? io->len_a : io->len_b;
+  const bool want_tri = io->tri != nullptr;
+  if (want_tri && io->mode > 2) return fail(PPCSR_EINVAL, "isect probe: tri is credited by the intersecting modes only");
+  if (want_tri && io->tri_n == 0) return fail(PPCSR_EINVAL, "isect probe: tri asked for with n == 0");
+  static_assert(sizeof(IsectCase) == 24, "six words per case");
+  const IsectCase *cs = reinterpret_cast<const IsectCase *>(io->cases);
+  for (uint64_t c = 0; c < nc; c++) {
+    if (cs[c].alo > cs[c].ahi || cs[c].blo > cs[c].bhi) return fail(PPCSR_EINVAL, "isect probe: a case with lo > hi");
+    if (cs[c].ahi > len_a || cs[c].bhi > len_b) return fail(PPCSR_EINVAL, "isect probe: a range leaves its buffer");
+    if (want_tri && cs[c].n > io->tri_n) return fail(PPCSR_EINVAL, "isect probe: a case's n beyond tri");
+  }
+  if (nc == 0) {
+    if (want_tri) memset(io->tri, 0, io->tri_n * sizeof(uint64_t));
+    return PPCSR_OK;
+  }
+  GCHK(gpu::set_device(device_));
+  Edge *d_a = nullptr, *d_b = nullptr;
+  IsectCase *d_cs = nullptr;
+  uint32_t *d_out = nullptr;
+  unsigned long long *d_tri = nullptr;
+  DevGuard guard;
+  guard.add(&d_a);
+  guard.add(&d_b);
+  guard.add(&d_cs);
+  guard.add(&d_out);
+  guard.add(&d_tri);
+  GCHK(gpu::dmalloc((void **)&d_a, std::max<uint64_t>(len_a, 1) * sizeof(Edge)));
+  if (!same) GCHK(gpu::dmalloc((void **)&d_b, std::max<uint64_t>(len_b, 1) * sizeof(Edge)));
+  GCHK(gpu::dmalloc((void **)&d_cs, nc * sizeof(IsectCase)));
+  GCHK(gpu::dmalloc((void **)&d_out, nc * sizeof(uint32_t)));
+  if (want_tri) GCHK(gpu::dmalloc((void **)&d_tri, io->tri_n * sizeof(unsigned long long)));
+  if (len_a) GCHK(gpu::h2d(d_a, io->items_a, len_a * sizeof(Edge), p.stream));
+  if (!same && len_b) GCHK(gpu::h2d(d_b, io->items_b, len_b * sizeof(Edge), p.stream));
+  GCHK(gpu::h2d(d_cs, cs, nc * sizeof(IsectCase), p.stream));
+  GCHK(gpu::dset(d_out, 0, nc * sizeof(uint32_t), p.stream));
+  if (want_tri) GCHK(gpu::dset(d_tri, 0, io->tri_n * sizeof(unsigned long long), p.stream));
+  const Edge *ia = d_a, *ib = same ? d_a : d_b;
+  const IsectCase *dcs = d_cs;
+  const uint32_t per_lane = (uint32_t)((nc + kIsectProbeThreads - 1) / kIsectProbeThreads), per_wave = (uint32_t)((nc + 3) / 4);
+  if (io->mode == 0) GPU_LAUNCH(p.stream, k_probe_isect_lane, per_lane, kIsectProbeThreads, ia, ib, dcs, nc, d_out, d_tri);
+  else if (io->mode == 1) GPU_LAUNCH(p.stream, k_probe_isect_wave, per_wave, kIsectProbeThreads, ia, ib, dcs, nc, d_out, d_tri);
+  else if (io->mode == 2) GPU_LAUNCH(p.stream, k_probe_isect_block, (uint32_t)nc, kIsectProbeThreads, ia, ib, dcs, d_out, d_tri);
+  else if (io->mode == 3) GPU_LAUNCH(p.stream, k_probe_isect_lower_bound, per_wave, kIsectProbeThreads, ib, dcs, nc, d_out);
+  else GPU_LAUNCH(p.stream, k_probe_isect_probe, per_lane, kIsectProbeThreads, ib, dcs, nc, d_out);
+  GCHK(gpu::d2h(io->out, d_out, nc * sizeof(uint32_t), p.stream));
+  if (want_tri) GCHK(gpu::d2h(io->tri, d_tri, io->tri_n * sizeof(unsigned long long), p.stream));
+  GCHK(gpu::sync(p.stream));
+  GCHK(gpu::last_error());
+  return PPCSR_OK;
+}
+
 // double_list / half_list alone (PCSR.cpp:251-320): the array is doubled and halved back `iters` times; device time of the
 // passes (tile sums, position table, fused scatter into the fresh array), allocations and the final synchronisation outside.
 // The array ends at its original size, evenly spread.

@@ -53,6 +53,20 @@ struct ChainProbeIO {
   uint64_t *segs;
   uint32_t *wg;
 };
+// ppcsr_debug_isect_probe (include/ppcsr.h: ppcsr_isect_probe_io, same layout)
+struct IsectProbeIO {
+  int32_t mode;
+  uint32_t reserved;
+  uint64_t ncases;
+  const uint32_t *cases;
+  const Edge *items_a;
+  uint64_t len_a;
+  const Edge *items_b;
+  uint64_t len_b;
+  uint32_t *out;
+  uint64_t *tri;
+  uint64_t tri_n;
+};
 
 class Engine {
  public:
@@ -110,6 +124,7 @@ class Engine {
   int rebalance_bench(uint64_t wlen, int iters, double *ms_per_call);
   int resize_bench(int iters, double *double_ms, double *half_ms);
   int chain_probe(const ChainProbeIO *io);  // the position-chain functions run on the device, engine state untouched
+  int isect_probe(const IsectProbeIO *io);  // the intersection routines of pma_intersect.h likewise
   int snapshot();  // device-side copy of the whole state (items, nodes, leaf counts, geometry)
   int restore();   // back to the last snapshot (device-to-device)  // whole-window rebalance kernel timing
 

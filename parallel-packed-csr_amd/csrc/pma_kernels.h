@@ -6,6 +6,7 @@
 //   pma_scan.h         queries, bulk neighbour scan, bulk build, BFS / PageRank
 //   pma_paths.h        shortest paths over the edge values, weakly connected components
 //   pma_intersect.h    triangle counts and common-neighbour counts: sorted intersection of two gapped vertex ranges
+//   pma_isect_probe.h  debugging probe of the intersection routines (ppcsr_debug_isect_probe)
 //   pma_query.h        batched reads: edge lookups with values, neighbourhood gathers
 //   pma_exchange.h     owner bucketing for the multi-GPU exchange
 #pragma once
@@ -16,5 +17,6 @@
 #include "pma_scan.h"
 #include "pma_paths.h"
 #include "pma_intersect.h"
+#include "pma_isect_probe.h"
 #include "pma_query.h"
 #include "pma_exchange.h"

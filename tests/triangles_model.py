@@ -111,3 +111,99 @@ def assert_hard(h, label="", want_long=False):
     assert h["gapped"] >= 1, (label, h)
     if want_long:
         assert h["long"] >= 1, (label, h)
+
+
+# ---- which routine of pma_intersect.h answers what -------------------------------------------------------------------------------------
+LANE_SLOTS, LOPSIDED = 32, 8  # kIsectLaneSlots, kIsectLopsided
+
+
+def edge_counts(src, dst, n):
+    """{(a, b): triangles (a, b, c), c > b} of the upper edges with a count above 0 (the wedge enumeration of model_triangles)"""
+    a, b = upper_edges(src, dst, n)
+    keys = a * n + b
+    rows = np.searchsorted(a, np.arange(n + 1))
+    lens = (rows[1:] - rows[:-1])[b]
+    eidx = np.repeat(np.arange(len(a)), lens)
+    off = np.arange(int(lens.sum())) - np.repeat(np.cumsum(lens) - lens, lens)
+    c = b[rows[b[eidx]] + off]
+    q = a[eidx] * n + c
+    hit = keys[np.minimum(np.searchsorted(keys, q), len(keys) - 1)] == q
+    cnt = np.bincount(eidx[hit], minlength=len(a))
+    return {(int(x), int(y)): int(k) for x, y, k in zip(a[cnt > 0], b[cnt > 0], cnt[cnt > 0])}
+
+
+def wave_route(la, lb):
+    """the form of isect_wave for operands of la and lb slots"""
+    s, l = min(la, lb), max(la, lb)
+    return "wave_probe" if s and l // LOPSIDED > s else "wave_merge"
+
+
+def routes(states, n):
+    """Every counted edge (a, b) — a live non-sentinel slot s with a < b < n — classified by the slot lengths k_tri_edges and
+    k_tri_long decide on: `aend - s` (one more than the slots of a's suffix behind the edge) and b's range (beginning, end) for
+    lane / deferred; a's suffix and b's range from the first dest above b for the form of isect_wave.  From the exported states
+    alone.  -> dict: route -> [edges, edges with a count above 0], and the counters of the glue code."""
+    src, dst = global_edges(states)
+    tri_of = edge_counts(src, dst, n)
+    firsts = np.array([f for f, _, _ in states], np.int64)
+    r = {k: [0, 0] for k in ("lane", "wave_merge", "wave_probe", "block")}
+    c = dict(a_suffix={32: 0, 33: 0, WAVE_SLOTS: 0, WAVE_SLOTS + 1: 0}, mixed_chunks=0, full_quarter_chunks=0, credit_run_chunks=0, cross_partition=0,
+             b_range_short=0, b_range_mid=0, b_range_long=0)
+    for k, (first, items, nodes) in enumerate(states):
+        if not len(nodes):
+            continue
+        live = (items[:, 2] != 0) & (items[:, 1] != 0xFFFFFFFF) & (items[:, 2] != 0xFFFFFFFF)
+        live[-1] = False
+        live &= items[:, 0] < len(nodes)
+        slot = np.nonzero(live)[0]
+        la_, b_ = items[slot, 0].astype(np.int64), items[slot, 1].astype(np.int64)
+        ok = (la_ + first < b_) & (b_ < n)
+        slot, la_, b_ = slot[ok], la_[ok], b_[ok]
+        aend = np.maximum(nodes[la_, 1].astype(np.int64), slot + 1)
+        kb = np.searchsorted(firsts, b_, side="right") - 1
+        lng = np.zeros(len(slot), bool)
+        has = np.zeros(len(slot), bool)
+        for i in range(len(slot)):
+            s, a, b = int(slot[i]), int(la_[i]) + first, int(b_[i])
+            _, bitems, bnodes = states[kb[i]]
+            nb = bnodes[b - int(firsts[kb[i]])]
+            bbeg = int(nb[0]) + 1
+            bend = max(int(nb[1]), bbeg)
+            suffix = int(aend[i]) - s
+            if suffix in c["a_suffix"]:
+                c["a_suffix"][suffix] += 1
+            c["cross_partition"] += int(kb[i] != k)
+            c["b_range_short" if bend - bbeg <= LANE_SLOTS else "b_range_mid" if bend - bbeg <= WAVE_SLOTS else "b_range_long"] += 1
+            cnt = tri_of.get((a, b), 0)
+            has[i] = cnt > 0
+            if suffix > WAVE_SLOTS or bend - bbeg > WAVE_SLOTS:
+                route, lng[i] = "block", True
+            elif suffix <= LANE_SLOTS and bend - bbeg <= LANE_SLOTS:
+                route = "lane"
+            else:
+                br = bitems[bbeg:bend]
+                above = np.nonzero((br[:, 2] != 0) & (br[:, 1] > b))[0]
+                blo = bbeg + int(above[0]) if len(above) else bend
+                route = wave_route(suffix - 1, bend - blo)
+            r[route][0] += 1
+            r[route][1] += int(cnt > 0)
+        chunk = slot // 64
+        for ch in np.unique(chunk):
+            m = chunk == ch
+            if lng[m].any():
+                c["mixed_chunks"] += int((~lng[m]).any())
+                c["full_quarter_chunks"] += int(len(np.unique((slot[m][lng[m]] % 64) // 16)) == 4)
+            c["credit_run_chunks"] += int(len(np.unique(la_[m][has[m]])) >= 3)
+    return dict(routes=r, counters=c)
+
+
+def assert_routes(rt, label="", partitions=1):
+    """every route answers an edge that has triangles, and every seam of the glue code is met"""
+    for name, (edges, with_tri) in rt["routes"].items():
+        assert with_tri >= 1, (label, name, rt)
+    c = rt["counters"]
+    assert all(v >= 1 for v in c["a_suffix"].values()), (label, c)
+    for key in ("mixed_chunks", "full_quarter_chunks", "credit_run_chunks", "b_range_short", "b_range_mid", "b_range_long"):
+        assert c[key] >= 1, (label, key, c)
+    if partitions > 1:  # (one partition has no such edge)
+        assert c["cross_partition"] >= 1, (label, c)
