@@ -139,6 +139,19 @@ int ppcsr_pagerank(ppcsr_t h, const float *node_values, float *out, double *devi
 #define PPCSR_NO_PATH 0xFFFFFFFFFFFFFFFFull
 int ppcsr_sssp(ppcsr_t h, uint32_t start, uint64_t *dist, double *device_ms);
 int ppcsr_components(ppcsr_t h, uint32_t *labels, double *device_ms);
+/* Core numbers (the k-core decomposition), over the edge set ppcsr_components hooks (live non-sentinel slots, slot N - 1
+ * excluded, destinations >= n skipped) and in the undirected graph G ppcsr_triangles counts in, the upper orientation: {a, b},
+ * a < b < n, is an edge exactly when the pair (a, b) is stored; stored pairs with src > dst and self-loops play no part — so
+ * tri[] and core[] speak about the same graph.  This is the exact answer for a graph stored symmetrically and for one stored
+ * as its upper triangle; for any other state it is still one well-defined result.
+ * kcore — core[v] = the largest k such that v lies in a subgraph of G whose every vertex has at least k neighbours inside it
+ *   (n entries, may be NULL); an isolated vertex has core 0.  *kmax = the largest core number, the degeneracy of G; 0 for
+ *   n = 0 or no edges (may be NULL, not both).
+ * Both results are unique.  Same contract as components: synchronous on the engine's stream, sees every batch applied before
+ * it, writes nothing to the graph (state, stats, dirty tags and snapshot unchanged), device_ms may be NULL.  The call does not
+ * intersect sorted ranges, so — as components, and unlike triangles — it also answers in the sequential regime
+ * (stats.narrow == 0).  EINVAL: null handle, core and kmax both NULL. */
+int ppcsr_kcore(ppcsr_t h, uint32_t *core, uint32_t *kmax, double *device_ms);
 /* Two consumers that intersect two neighbourhoods, over the same edge set (live slots of every vertex's (beginning, end), slot
  * N - 1 excluded, destinations >= n skipped; a (src, dst) pair is stored at most once).  A vertex's live slots lie in
  * ascending destination order, so the neighbourhoods are intersected in place: no export, no sort.
@@ -311,6 +324,11 @@ int pppcsr_pagerank(pppcsr_t h, const float *node_values, float *out, double *de
  * device — there is no host form of these two calls. */
 int pppcsr_sssp(pppcsr_t h, uint32_t start, uint64_t *dist, double *device_ms);
 int pppcsr_components(pppcsr_t h, uint32_t *labels, double *device_ms);
+/* ppcsr_kcore over the GLOBAL vertex ids (core: pppcsr_get_n entries), one device call over every partition's array: an edge
+ * may have its two vertices in different partitions, and the result does not depend on the partitioning.  Same contract as
+ * pppcsr_components; a partition in the sequential regime is answered.  EINVAL: null handle, core and kmax both NULL, or a
+ * partition not resident in this process.  EUNSUPPORTED: the partitions sit on more than one device. */
+int pppcsr_kcore(pppcsr_t h, uint32_t *core, uint32_t *kmax, double *device_ms);
 /* ppcsr_triangles / ppcsr_common_neighbours over the GLOBAL vertex ids (tri: pppcsr_get_n entries), one device call over every
  * partition's array: a pair may have its two vertices in different partitions, and the results do not depend on the
  * partitioning.  Same contract as pppcsr_bfs.  EINVAL: as the single calls, or a partition not resident in this process.

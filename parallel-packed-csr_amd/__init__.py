@@ -72,7 +72,7 @@ EXPORTED = [
     "pppcsr_exchange_bulk_build", "ppcsr_lookup_edges", "ppcsr_lookup_edges_device", "ppcsr_gather_neighbourhoods",
     "ppcsr_gather_neighbourhoods_device", "pppcsr_lookup_edges", "pppcsr_gather_neighbourhoods", "pppcsr_set_option",
     "pppcsr_bfs", "pppcsr_pagerank", "ppcsr_sssp", "ppcsr_components", "pppcsr_sssp", "pppcsr_components",
-    "ppcsr_debug_chain_probe", "ppcsr_debug_isect_probe",
+    "ppcsr_debug_chain_probe", "ppcsr_debug_isect_probe", "ppcsr_kcore", "pppcsr_kcore",
     "ppcsr_triangles", "pppcsr_triangles", "ppcsr_common_neighbours", "ppcsr_common_neighbours_device", "pppcsr_common_neighbours",
 ]
 
@@ -142,6 +142,8 @@ def load_library(path=None):
         getattr(L, name).argtypes = [c_vp, c_u32, c_vp, ctypes.POINTER(ctypes.c_double)]
     for name in ("ppcsr_components", "pppcsr_components"):
         getattr(L, name).argtypes = [c_vp, c_vp, ctypes.POINTER(ctypes.c_double)]
+    for name in ("ppcsr_kcore", "pppcsr_kcore"):
+        getattr(L, name).argtypes = [c_vp, c_vp, ctypes.POINTER(c_u32), ctypes.POINTER(ctypes.c_double)]
     for name in ("ppcsr_triangles", "pppcsr_triangles"):
         getattr(L, name).argtypes = [c_vp, c_vp, ctypes.POINTER(c_u64), ctypes.POINTER(ctypes.c_double)]
     for name in ("ppcsr_common_neighbours", "ppcsr_common_neighbours_device", "pppcsr_common_neighbours"):
@@ -227,6 +229,14 @@ def _triangles(obj, fn, per_vertex, with_ms):
     total, ms = c_u64(), ctypes.c_double(0.0)
     obj._chk(fn(obj.h, tri.ctypes.data if per_vertex else None, ctypes.byref(total), ctypes.byref(ms)))
     return (tri, total.value, ms.value) if with_ms else (tri, total.value)
+
+
+def _kcore(obj, fn, with_ms):
+    """(core, kmax[, ms])"""
+    core = np.empty(obj.get_n(), np.uint32)
+    kmax, ms = c_u32(), ctypes.c_double(0.0)
+    obj._chk(fn(obj.h, core.ctypes.data, ctypes.byref(kmax), ctypes.byref(ms)))
+    return (core, kmax.value, ms.value) if with_ms else (core, kmax.value)
 
 
 def _common(obj, fn, a, b, with_ms):
@@ -390,6 +400,11 @@ class PCSR:
         """(tri, total): triangles through every vertex (uint64; None unless per_vertex) and their number, counted in the
         upper orientation ({a, b}, a < b, is an edge exactly when (a, b) is stored: include/ppcsr.h)"""
         return _triangles(self, self.L.ppcsr_triangles, per_vertex, with_ms)
+
+    def kcore(self, with_ms=False):
+        """(core, kmax): the core number of every vertex (uint32) and the largest of them, in the upper orientation that
+        triangles() counts in"""
+        return _kcore(self, self.L.ppcsr_kcore, with_ms)
 
     def common_neighbours(self, a, b, with_ms=False):
         """counts[i] = stored destinations < n that a[i] and b[i] share (uint32; vertices >= n give 0)"""
@@ -681,6 +696,11 @@ class PPPCSR:
         """(tri, total): triangles through every vertex (uint64; None unless per_vertex) and their number, counted in the
         upper orientation ({a, b}, a < b, is an edge exactly when (a, b) is stored: include/ppcsr.h)"""
         return _triangles(self, self.L.pppcsr_triangles, per_vertex, with_ms)
+
+    def kcore(self, with_ms=False):
+        """(core, kmax): the core number of every vertex (uint32, global ids) and the largest of them, in the upper
+        orientation that triangles() counts in"""
+        return _kcore(self, self.L.pppcsr_kcore, with_ms)
 
     def common_neighbours(self, a, b, with_ms=False):
         """counts[i] = stored destinations < n that a[i] and b[i] share (uint32; vertices >= n give 0)"""

@@ -173,6 +173,11 @@ int ppcsr_components(ppcsr_t h, uint32_t *labels, double *device_ms) {
   if (!labels) return bad("components: null output");
   return ret(h->e, h->e->components(labels, device_ms));
 }
+int ppcsr_kcore(ppcsr_t h, uint32_t *core, uint32_t *kmax, double *device_ms) {
+  H_CHECK();
+  if (!core && !kmax) return bad("kcore: null outputs");
+  return ret(h->e, h->e->kcore(core, kmax, device_ms));
+}
 int ppcsr_triangles(ppcsr_t h, uint64_t *tri, uint64_t *total, double *device_ms) {
   H_CHECK();
   if (!tri && !total) return bad("triangles: null outputs");
@@ -708,6 +713,17 @@ int pppcsr_components(pppcsr_t h, uint32_t *labels, double *device_ms) {
   pppcsr_get_n(h, &n);
   Engine *e = refs[0].e;
   return ret(e, e->components_over(refs.data(), (uint32_t)refs.size(), (uint32_t)n, labels, device_ms));
+}
+int pppcsr_kcore(pppcsr_t h, uint32_t *core, uint32_t *kmax, double *device_ms) {
+  PP_CHECK();
+  if (!core && !kmax) return bad("kcore: null outputs");
+  std::vector<ppcsr::ConsumerRef> refs;
+  int rc = consumer_parts(h, &refs);
+  if (rc != 0) return rc;
+  uint64_t n = 0;
+  pppcsr_get_n(h, &n);
+  Engine *e = refs[0].e;
+  return ret(e, e->kcore_over(refs.data(), (uint32_t)refs.size(), (uint32_t)n, core, kmax, device_ms));
 }
 int pppcsr_triangles(pppcsr_t h, uint64_t *tri, uint64_t *total, double *device_ms) {
   PP_CHECK();

@@ -2402,6 +2402,99 @@ int Engine::components_over(const ConsumerRef *parts, uint32_t P, uint32_t total
   return PPCSR_OK;
 }
 
+// Core numbers (pma_cores.h).  Stage 1 exports the upper-orientation graph as a compact symmetric adjacency (degree pass,
+// scan, fill pass); stage 2 peels it level by level in sub-rounds.  One host read of the small counter block per level (the
+// level and its first frontier) and per sub-round (the next frontier, the deferred long lists).  device_ms covers the whole
+// call: besides the kernels it holds the host read of the edge total and the allocation of the lists between the scan and
+// the fill pass, and every round trip of the peel.
+int Engine::kcore(uint32_t *core, uint32_t *kmax, double *device_ms) {
+  const ConsumerRef self{this, 0};
+  return kcore_over(&self, 1, n(), core, kmax, device_ms);
+}
+int Engine::kcore_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t *core, uint32_t *kmax, double *device_ms) {
+  Impl &p = *p_;
+  GCHK(gpu::set_device(device_));
+  const uint32_t nn = total_n;
+  uint32_t *d_deg = nullptr, *d_core = nullptr, *d_fill = nullptr, *d_adj = nullptr, *d_f0 = nullptr, *d_f1 = nullptr, *d_long = nullptr, *d_cnt = nullptr;
+  unsigned long long *d_off = nullptr, *d_tiles = nullptr;
+  ConsumerPart *d_tab = nullptr;
+  DevGuard tmpg;
+  tmpg.add(&d_deg); tmpg.add(&d_core); tmpg.add(&d_fill); tmpg.add(&d_adj); tmpg.add(&d_f0); tmpg.add(&d_f1); tmpg.add(&d_long); tmpg.add(&d_cnt);
+  tmpg.add(&d_off); tmpg.add(&d_tiles); tmpg.add(&d_tab);
+  uint64_t N = 0;  // slots of all arrays: what one streaming pass reads
+  int rc = consumer_table(parts, P, nn, (void **)&d_tab, &N);
+  if (rc != PPCSR_OK) return rc;
+  const ConsumerPart *tab = d_tab;
+  const uint64_t words = std::max<uint64_t>(nn, 1);
+  const uint32_t ntiles = (uint32_t)(((uint64_t)nn + kKcTile - 1) / kKcTile);
+  GCHK(gpu::dmalloc((void **)&d_deg, words * sizeof(uint32_t)));
+  GCHK(gpu::dmalloc((void **)&d_core, words * sizeof(uint32_t)));
+  GCHK(gpu::dmalloc((void **)&d_fill, words * sizeof(uint32_t)));
+  GCHK(gpu::dmalloc((void **)&d_f0, words * sizeof(uint32_t)));  // (a vertex enters one frontier once: no list exceeds n)
+  GCHK(gpu::dmalloc((void **)&d_f1, words * sizeof(uint32_t)));
+  GCHK(gpu::dmalloc((void **)&d_long, words * sizeof(uint32_t)));
+  GCHK(gpu::dmalloc((void **)&d_off, (words + 1) * sizeof(unsigned long long)));
+  GCHK(gpu::dmalloc((void **)&d_tiles, std::max<uint64_t>(ntiles, 1) * sizeof(unsigned long long)));
+  GCHK(gpu::dmalloc((void **)&d_cnt, kKcCntWords * sizeof(uint32_t)));
+  uint32_t top = 0;
+  p.timer.start(p.stream);
+  if (nn) {
+    // stage 1: deg[], off[] (off[nn] = 2 |E(G)|), adj[]
+    GCHK(gpu::dset(d_deg, 0, words * sizeof(uint32_t), p.stream));
+    GCHK(gpu::dset(d_fill, 0, words * sizeof(uint32_t), p.stream));
+    GPU_LAUNCH(p.stream, k_kc_init, grid_for(nn, 256, 4096), 256, d_core, nn);
+    GPU_LAUNCH(p.stream, k_kc_degree, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, d_deg);
+    GPU_LAUNCH(p.stream, k_kc_tile_sums, grid_for(ntiles, 1, 65536), 256, (const uint32_t *)d_deg, nn, ntiles, d_tiles);
+    GPU_LAUNCH(p.stream, k_kc_scan_tiles, 1, 64, d_tiles, ntiles, d_off + nn);
+    GPU_LAUNCH(p.stream, k_kc_scan_write, grid_for(ntiles, 1, 65536), 256, (const uint32_t *)d_deg, nn, ntiles, (const unsigned long long *)d_tiles, d_off);
+    unsigned long long entries = 0;
+    GCHK(gpu::d2h(&entries, d_off + nn, sizeof(entries), p.stream));
+    GCHK(gpu::sync(p.stream));
+    GCHK(gpu::last_error());
+    GCHK(gpu::dmalloc((void **)&d_adj, std::max<uint64_t>(entries, 1) * sizeof(uint32_t)));
+    GPU_LAUNCH(p.stream, k_kc_fill, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, (const unsigned long long *)d_off, d_fill, d_adj);
+    // stage 2
+    uint32_t h_cnt[4] = {0, 0, 0, 0};  // (host copy of the three words of the counter block that are in use, padded to 16 bytes)
+    uint32_t *cur = d_f0, *nxt = d_f1;
+    for (;;) {
+      GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), p.stream));
+      GCHK(gpu::dset(d_cnt + 2, 0xFF, sizeof(uint32_t), p.stream));
+      GPU_LAUNCH(p.stream, k_kc_min, grid_for(nn, 256, 1024), 256, (const uint32_t *)d_deg, (const uint32_t *)d_core, nn, d_cnt);
+      GPU_LAUNCH(p.stream, k_kc_collect, grid_for(nn, 256), 256, (const uint32_t *)d_deg, d_core, nn, cur, d_cnt);
+      GCHK(gpu::d2h(h_cnt, d_cnt, 3 * sizeof(uint32_t), p.stream));
+      GCHK(gpu::sync(p.stream));
+      GCHK(gpu::last_error());
+      uint32_t nfront = h_cnt[0];
+      const uint32_t k = h_cnt[2];
+      if (nfront == 0) break;  // (k == kMax: every vertex is assigned)
+      top = k;
+      while (nfront > 0) {
+        GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), p.stream));
+        GPU_LAUNCH(p.stream, k_kc_peel, grid_for(nfront, 4, 16384), 256, (const unsigned long long *)d_off, (const uint32_t *)d_adj, (const uint32_t *)cur,
+                   nfront, k, d_deg, d_core, nxt, d_long, d_cnt);
+        GCHK(gpu::d2h(h_cnt, d_cnt, 2 * sizeof(uint32_t), p.stream));
+        GCHK(gpu::sync(p.stream));
+        GCHK(gpu::last_error());
+        if (h_cnt[1]) {  // lists beyond one wave's reach: a second launch splits them over waves and appends to the same frontier
+          GPU_LAUNCH(p.stream, k_kc_peel_long, grid_for((uint64_t)h_cnt[1] * 16, 4, 4096), 256, (const unsigned long long *)d_off, (const uint32_t *)d_adj,
+                     (const uint32_t *)d_long, h_cnt[1], k, d_deg, d_core, nxt, d_cnt);
+          GCHK(gpu::d2h(h_cnt, d_cnt, sizeof(uint32_t), p.stream));
+          GCHK(gpu::sync(p.stream));
+          GCHK(gpu::last_error());
+        }
+        nfront = h_cnt[0];
+        std::swap(cur, nxt);
+      }
+    }
+  }
+  p.timer.stop(p.stream);
+  if (core && nn) GCHK(gpu::d2h(core, d_core, (uint64_t)nn * sizeof(uint32_t), p.stream));
+  GCHK(gpu::sync(p.stream));
+  if (kmax) *kmax = top;
+  if (device_ms) *device_ms = p.timer.ms();
+  return PPCSR_OK;
+}
+
 // Triangle counts and common-neighbour counts (pma_intersect.h).  Both intersect vertex ranges as sorted lists, which holds
 // in the regular regime only: a partition in the sequential regime (narrow == 0: ranges may be unsorted or overlapping until
 // the next re-check) is refused rather than answered on a wrong assumption.

@@ -107,6 +107,10 @@ class Engine {
   int components(uint32_t *labels, double *device_ms);
   int sssp_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t start, uint64_t *dist, double *device_ms);
   int components_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t *labels, double *device_ms);
+  // core numbers of the upper-orientation graph triangles counts in (pma_cores.h), under the same contract and in either
+  // regime: core (total_n entries, may be null), *kmax (may be null): the largest core number
+  int kcore(uint32_t *core, uint32_t *kmax, double *device_ms);
+  int kcore_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t *core, uint32_t *kmax, double *device_ms);
   // consumers that intersect two neighbourhoods (pma_intersect.h), under the same contract.  triangles: upper orientation —
   // {a, b}, a < b, is an edge exactly when (a, b) is stored; tri (total_n entries, may be null): triangles through every
   // vertex; *total (may be null): triangles.  common_neighbours: counts[i] = stored dests < total_n shared by a[i] and b[i]

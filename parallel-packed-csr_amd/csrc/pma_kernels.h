@@ -5,6 +5,7 @@
 //   pma_probe.h        debugging probe of the position chain (ppcsr_debug_chain_probe)
 //   pma_scan.h         queries, bulk neighbour scan, bulk build, BFS / PageRank
 //   pma_paths.h        shortest paths over the edge values, weakly connected components
+//   pma_cores.h        core numbers (k-core decomposition): symmetric adjacency export, peeling in sub-rounds
 //   pma_intersect.h    triangle counts and common-neighbour counts: sorted intersection of two gapped vertex ranges
 //   pma_isect_probe.h  debugging probe of the intersection routines (ppcsr_debug_isect_probe)
 //   pma_query.h        batched reads: edge lookups with values, neighbourhood gathers
@@ -16,6 +17,7 @@
 #include "pma_probe.h"
 #include "pma_scan.h"
 #include "pma_paths.h"
+#include "pma_cores.h"
 #include "pma_intersect.h"
 #include "pma_isect_probe.h"
 #include "pma_query.h"
