@@ -223,31 +223,6 @@ def _lookup(fn, h, src, dst):
     return fn(h, s.ctypes.data, d.ctypes.data, s.size, out.ctypes.data), out
 
 
-def _triangles(obj, fn, per_vertex, with_ms):
-    """(tri, total[, ms]): tri is None unless per_vertex"""
-    tri = np.empty(obj.get_n(), np.uint64) if per_vertex else None
-    total, ms = c_u64(), ctypes.c_double(0.0)
-    obj._chk(fn(obj.h, tri.ctypes.data if per_vertex else None, ctypes.byref(total), ctypes.byref(ms)))
-    return (tri, total.value, ms.value) if with_ms else (tri, total.value)
-
-
-def _kcore(obj, fn, with_ms):
-    """(core, kmax[, ms])"""
-    core = np.empty(obj.get_n(), np.uint32)
-    kmax, ms = c_u32(), ctypes.c_double(0.0)
-    obj._chk(fn(obj.h, core.ctypes.data, ctypes.byref(kmax), ctypes.byref(ms)))
-    return (core, kmax.value, ms.value) if with_ms else (core, kmax.value)
-
-
-def _common(obj, fn, a, b, with_ms):
-    a, b = _u32(a), _u32(b)
-    assert a.size == b.size, "a and b must have the same length"
-    out = np.empty(a.size, np.uint32)
-    ms = ctypes.c_double(0.0)
-    obj._chk(fn(obj.h, a.ctypes.data, b.ctypes.data, a.size, out.ctypes.data, ctypes.byref(ms)))
-    return (out, ms.value) if with_ms else out
-
-
 def _gather(fn, h, vertices, with_values):
     """(rc, row_offsets, dests, values|None): the size query, then the gather into arrays of that size"""
     q = _u32(vertices)
@@ -264,8 +239,68 @@ def _gather(fn, h, vertices, with_values):
     return rc, rows, dests, vals
 
 
-class PCSR:
+class _Consumers:
+    """The device consumers (reference: src/utility/bfs.h, src/utility/pagerank.h; include/ppcsr.h): PCSR calls ppcsr_<name>,
+    PPPCSR calls pppcsr_<name> over every partition, with global vertex ids."""
+    _prefix = None
+
+    def _consumer(self, name, *args):
+        ms = ctypes.c_double(0.0)
+        self._chk(getattr(self.L, self._prefix + name)(self.h, *args, ctypes.byref(ms)))
+        return ms.value
+
+    def bfs(self, start, with_ms=False):
+        out = np.empty(self.get_n(), np.uint32)
+        ms = self._consumer("bfs", start, out.ctypes.data)
+        return (out, ms) if with_ms else out
+
+    def pagerank(self, node_values, with_ms=False):
+        vals = np.ascontiguousarray(node_values, np.float32)
+        assert len(vals) == self.get_n()
+        out = np.empty(len(vals), np.float32)
+        ms = self._consumer("pagerank", vals.ctypes.data, out.ctypes.data)
+        return (out, ms) if with_ms else out
+
+    def sssp(self, start, with_ms=False):
+        """distances over the edge values from `start` (uint64, NO_PATH where no path leads)"""
+        out = np.empty(self.get_n(), np.uint64)
+        ms = self._consumer("sssp", start, out.ctypes.data)
+        return (out, ms) if with_ms else out
+
+    def components(self, with_ms=False):
+        """weakly connected components: the smallest vertex id of every vertex's component (uint32)"""
+        out = np.empty(self.get_n(), np.uint32)
+        ms = self._consumer("components", out.ctypes.data)
+        return (out, ms) if with_ms else out
+
+    def triangles(self, per_vertex=True, with_ms=False):
+        """(tri, total[, ms]): triangles through every vertex (uint64; None unless per_vertex) and their number, counted in the
+        upper orientation ({a, b}, a < b, is an edge exactly when (a, b) is stored: include/ppcsr.h)"""
+        tri = np.empty(self.get_n(), np.uint64) if per_vertex else None
+        total = c_u64()
+        ms = self._consumer("triangles", tri.ctypes.data if per_vertex else None, ctypes.byref(total))
+        return (tri, total.value, ms) if with_ms else (tri, total.value)
+
+    def kcore(self, with_ms=False):
+        """(core, kmax[, ms]): the core number of every vertex (uint32, global ids) and the largest of them, in the upper
+        orientation that triangles() counts in"""
+        core = np.empty(self.get_n(), np.uint32)
+        kmax = c_u32()
+        ms = self._consumer("kcore", core.ctypes.data, ctypes.byref(kmax))
+        return (core, kmax.value, ms) if with_ms else (core, kmax.value)
+
+    def common_neighbours(self, a, b, with_ms=False):
+        """counts[i] = stored destinations < n that a[i] and b[i] share (uint32; vertices >= n give 0)"""
+        a, b = _u32(a), _u32(b)
+        assert a.size == b.size, "a and b must have the same length"
+        out = np.empty(a.size, np.uint32)
+        ms = self._consumer("common_neighbours", a.ctypes.data, b.ctypes.data, a.size, out.ctypes.data)
+        return (out, ms) if with_ms else out
+
+
+class PCSR(_Consumers):
     """Mirror of the reference class PCSR (PCSR.h:64-124) on one GPU."""
+    _prefix = "ppcsr_"
 
     def __init__(self, init_n, src_n=None, lock_search=True, device=0, lib=None, _handle=None):
         self.L = lib or load_library()
@@ -367,51 +402,9 @@ class PCSR:
         self._chk(self.L.ppcsr_bulk_build(self.h, a.ctypes.data, len(a), ctypes.byref(ms)))
         return ms.value if with_ms else None
 
-    # consumers on the device (reference: src/utility/bfs.h, src/utility/pagerank.h)
-    def bfs(self, start, with_ms=False):
-        out = np.empty(self.get_n(), np.uint32)
-        ms = ctypes.c_double(0.0)
-        self._chk(self.L.ppcsr_bfs(self.h, start, out.ctypes.data, ctypes.byref(ms)))
-        return (out, ms.value) if with_ms else out
-
-    def pagerank(self, node_values, with_ms=False):
-        vals = np.ascontiguousarray(node_values, np.float32)
-        assert len(vals) == self.get_n()
-        out = np.empty(len(vals), np.float32)
-        ms = ctypes.c_double(0.0)
-        self._chk(self.L.ppcsr_pagerank(self.h, vals.ctypes.data, out.ctypes.data, ctypes.byref(ms)))
-        return (out, ms.value) if with_ms else out
-
-    def sssp(self, start, with_ms=False):
-        """distances over the edge values from `start` (uint64, NO_PATH where no path leads)"""
-        out = np.empty(self.get_n(), np.uint64)
-        ms = ctypes.c_double(0.0)
-        self._chk(self.L.ppcsr_sssp(self.h, start, out.ctypes.data, ctypes.byref(ms)))
-        return (out, ms.value) if with_ms else out
-
-    def components(self, with_ms=False):
-        """weakly connected components: the smallest vertex id of every vertex's component (uint32)"""
-        out = np.empty(self.get_n(), np.uint32)
-        ms = ctypes.c_double(0.0)
-        self._chk(self.L.ppcsr_components(self.h, out.ctypes.data, ctypes.byref(ms)))
-        return (out, ms.value) if with_ms else out
-
-    def triangles(self, per_vertex=True, with_ms=False):
-        """(tri, total): triangles through every vertex (uint64; None unless per_vertex) and their number, counted in the
-        upper orientation ({a, b}, a < b, is an edge exactly when (a, b) is stored: include/ppcsr.h)"""
-        return _triangles(self, self.L.ppcsr_triangles, per_vertex, with_ms)
-
-    def kcore(self, with_ms=False):
-        """(core, kmax): the core number of every vertex (uint32) and the largest of them, in the upper orientation that
-        triangles() counts in"""
-        return _kcore(self, self.L.ppcsr_kcore, with_ms)
-
-    def common_neighbours(self, a, b, with_ms=False):
-        """counts[i] = stored destinations < n that a[i] and b[i] share (uint32; vertices >= n give 0)"""
-        return _common(self, self.L.ppcsr_common_neighbours, a, b, with_ms)
-
+    # consumers on the device: _Consumers
     def common_neighbours_device(self, a_ptr, b_ptr, k, out_ptr, with_ms=False):
-        """the same, pairs and counts in this GPU's memory (e.g. tensor.data_ptr())"""
+        """common_neighbours with pairs and counts in this GPU's memory (e.g. tensor.data_ptr())"""
         ms = ctypes.c_double(0.0)
         self._chk(self.L.ppcsr_common_neighbours_device(self.h, a_ptr, b_ptr, k, out_ptr, ctypes.byref(ms)))
         return ms.value if with_ms else None
@@ -563,8 +556,9 @@ class PCSR:
         return (out, tri[:tri_n]) if tri_n is not None else out
 
 
-class PPPCSR:
+class PPPCSR(_Consumers):
     """Mirror of the reference class PPPCSR (PPPCSR.h:11-60): vertex-range partitions, one per GPU."""
+    _prefix = "pppcsr_"
 
     def __init__(self, init_n, src_n=None, lock_search=True, numDomain=1, partitionsPerDomain=1, use_numa=False,
                  devices=None, lib=None, local=None):
@@ -662,49 +656,6 @@ class PPPCSR:
         rc, rows, dests, vals = _gather(self.L.pppcsr_gather_neighbourhoods, self.h, vertices, with_values)
         self._chk(rc)
         return rows, dests, vals
-
-    # consumers on the device over every partition (include/ppcsr.h: pppcsr_bfs / pppcsr_pagerank; global vertex ids)
-    def bfs(self, start, with_ms=False):
-        out = np.empty(self.get_n(), np.uint32)
-        ms = ctypes.c_double(0.0)
-        self._chk(self.L.pppcsr_bfs(self.h, start, out.ctypes.data, ctypes.byref(ms)))
-        return (out, ms.value) if with_ms else out
-
-    def pagerank(self, node_values, with_ms=False):
-        vals = np.ascontiguousarray(node_values, np.float32)
-        assert len(vals) == self.get_n()
-        out = np.empty(len(vals), np.float32)
-        ms = ctypes.c_double(0.0)
-        self._chk(self.L.pppcsr_pagerank(self.h, vals.ctypes.data, out.ctypes.data, ctypes.byref(ms)))
-        return (out, ms.value) if with_ms else out
-
-    def sssp(self, start, with_ms=False):
-        """distances over the edge values from `start` (uint64, NO_PATH where no path leads)"""
-        out = np.empty(self.get_n(), np.uint64)
-        ms = ctypes.c_double(0.0)
-        self._chk(self.L.pppcsr_sssp(self.h, start, out.ctypes.data, ctypes.byref(ms)))
-        return (out, ms.value) if with_ms else out
-
-    def components(self, with_ms=False):
-        """weakly connected components: the smallest vertex id of every vertex's component (uint32)"""
-        out = np.empty(self.get_n(), np.uint32)
-        ms = ctypes.c_double(0.0)
-        self._chk(self.L.pppcsr_components(self.h, out.ctypes.data, ctypes.byref(ms)))
-        return (out, ms.value) if with_ms else out
-
-    def triangles(self, per_vertex=True, with_ms=False):
-        """(tri, total): triangles through every vertex (uint64; None unless per_vertex) and their number, counted in the
-        upper orientation ({a, b}, a < b, is an edge exactly when (a, b) is stored: include/ppcsr.h)"""
-        return _triangles(self, self.L.pppcsr_triangles, per_vertex, with_ms)
-
-    def kcore(self, with_ms=False):
-        """(core, kmax): the core number of every vertex (uint32, global ids) and the largest of them, in the upper
-        orientation that triangles() counts in"""
-        return _kcore(self, self.L.pppcsr_kcore, with_ms)
-
-    def common_neighbours(self, a, b, with_ms=False):
-        """counts[i] = stored destinations < n that a[i] and b[i] share (uint32; vertices >= n give 0)"""
-        return _common(self, self.L.pppcsr_common_neighbours, a, b, with_ms)
 
     def set_option(self, key, value):
         """sizes of the batched reads: "query_block", "gather_stage" (include/ppcsr.h: pppcsr_set_option)"""

@@ -153,45 +153,54 @@ int ppcsr_bulk_build(ppcsr_t h, const ppcsr_op *adds, uint64_t n, double *device
   if (!adds && n) return bad("bulk_build: null input");
   return ret(h->e, h->e->bulk_build(reinterpret_cast<const ppcsr::Op *>(adds), n, device_ms));
 }
+// the consumers of one engine: a consumer call over the one-entry table {engine, first vertex 0}
 int ppcsr_bfs(ppcsr_t h, uint32_t start, uint32_t *levels, double *device_ms) {
   H_CHECK();
   if (!levels) return bad("bfs: null output");
-  return ret(h->e, h->e->bfs(start, levels, device_ms));
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->bfs_over(&self, 1, h->e->n(), start, levels, device_ms));
 }
 int ppcsr_pagerank(ppcsr_t h, const float *node_values, float *out, double *device_ms) {
   H_CHECK();
   if (!node_values || !out) return bad("pagerank: null argument");
-  return ret(h->e, h->e->pagerank(node_values, out, device_ms));
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->pagerank_over(&self, 1, h->e->n(), node_values, out, device_ms));
 }
 int ppcsr_sssp(ppcsr_t h, uint32_t start, uint64_t *dist, double *device_ms) {
   H_CHECK();
   if (!dist) return bad("sssp: null output");
-  return ret(h->e, h->e->sssp(start, dist, device_ms));
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->sssp_over(&self, 1, h->e->n(), start, dist, device_ms));
 }
 int ppcsr_components(ppcsr_t h, uint32_t *labels, double *device_ms) {
   H_CHECK();
   if (!labels) return bad("components: null output");
-  return ret(h->e, h->e->components(labels, device_ms));
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->components_over(&self, 1, h->e->n(), labels, device_ms));
 }
 int ppcsr_kcore(ppcsr_t h, uint32_t *core, uint32_t *kmax, double *device_ms) {
   H_CHECK();
   if (!core && !kmax) return bad("kcore: null outputs");
-  return ret(h->e, h->e->kcore(core, kmax, device_ms));
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->kcore_over(&self, 1, h->e->n(), core, kmax, device_ms));
 }
 int ppcsr_triangles(ppcsr_t h, uint64_t *tri, uint64_t *total, double *device_ms) {
   H_CHECK();
   if (!tri && !total) return bad("triangles: null outputs");
-  return ret(h->e, h->e->triangles(tri, total, device_ms));
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->triangles_over(&self, 1, h->e->n(), tri, total, device_ms));
 }
 int ppcsr_common_neighbours(ppcsr_t h, const uint32_t *a, const uint32_t *b, uint64_t k, uint32_t *counts, double *device_ms) {
   H_CHECK();
   if (k && (!a || !b || !counts)) return bad("common_neighbours: null argument");
-  return ret(h->e, h->e->common_neighbours(a, b, k, counts, false, device_ms));
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->common_neighbours_over(&self, 1, h->e->n(), a, b, k, counts, false, device_ms));
 }
 int ppcsr_common_neighbours_device(ppcsr_t h, const uint32_t *d_a, const uint32_t *d_b, uint64_t k, uint32_t *d_counts, double *device_ms) {
   H_CHECK();
   if (k && (!d_a || !d_b || !d_counts)) return bad("common_neighbours: null argument");
-  return ret(h->e, h->e->common_neighbours(d_a, d_b, k, d_counts, true, device_ms));
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->common_neighbours_over(&self, 1, h->e->n(), d_a, d_b, k, d_counts, true, device_ms));
 }
 int ppcsr_export_state(ppcsr_t h, ppcsr_edge *items, ppcsr_node *nodes) {
   H_CHECK();
@@ -668,84 +677,62 @@ static int consumer_parts(pppcsr_t h, std::vector<ppcsr::ConsumerRef> *refs) {
   for (uint64_t k = 0; k < h->parts.size(); k++) refs->push_back(ppcsr::ConsumerRef{h->parts[k]->e, (uint32_t)h->distribution[k]});
   return 0;
 }
-int pppcsr_bfs(pppcsr_t h, uint32_t start, uint32_t *levels, double *device_ms) {
-  PP_CHECK();
-  if (!levels) return bad("bfs: null output");
+}  // extern "C"
+// one consumer call over every partition: the partitions' engines, the vertex count, `call` on the first partition's engine
+// (call(e, refs, P, n): the wrapper's own range checks, then the engine call through ret())
+template <class F>
+static int over_parts(pppcsr_t h, F call) {
   std::vector<ppcsr::ConsumerRef> refs;
-  int rc = consumer_parts(h, &refs);
+  const int rc = consumer_parts(h, &refs);
   if (rc != 0) return rc;
   uint64_t n = 0;
   pppcsr_get_n(h, &n);
-  if (start >= n) return bad("bfs: start vertex out of range");
-  Engine *e = refs[0].e;
-  return ret(e, e->bfs_over(refs.data(), (uint32_t)refs.size(), (uint32_t)n, start, levels, device_ms));
+  return call(refs[0].e, refs.data(), (uint32_t)refs.size(), (uint32_t)n);
+}
+using Refs = const ppcsr::ConsumerRef *;
+extern "C" {
+int pppcsr_bfs(pppcsr_t h, uint32_t start, uint32_t *levels, double *device_ms) {
+  PP_CHECK();
+  if (!levels) return bad("bfs: null output");
+  return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) {
+    if (start >= n) return bad("bfs: start vertex out of range");
+    return ret(e, e->bfs_over(r, P, n, start, levels, device_ms));
+  });
 }
 int pppcsr_pagerank(pppcsr_t h, const float *node_values, float *out, double *device_ms) {
   PP_CHECK();
   if (!node_values || !out) return bad("pagerank: null argument");
-  std::vector<ppcsr::ConsumerRef> refs;
-  int rc = consumer_parts(h, &refs);
-  if (rc != 0) return rc;
-  uint64_t n = 0;
-  pppcsr_get_n(h, &n);
-  Engine *e = refs[0].e;
-  return ret(e, e->pagerank_over(refs.data(), (uint32_t)refs.size(), (uint32_t)n, node_values, out, device_ms));
+  return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) { return ret(e, e->pagerank_over(r, P, n, node_values, out, device_ms)); });
 }
 int pppcsr_sssp(pppcsr_t h, uint32_t start, uint64_t *dist, double *device_ms) {
   PP_CHECK();
   if (!dist) return bad("sssp: null output");
-  std::vector<ppcsr::ConsumerRef> refs;
-  int rc = consumer_parts(h, &refs);
-  if (rc != 0) return rc;
-  uint64_t n = 0;
-  pppcsr_get_n(h, &n);
-  if (start >= n) return bad("sssp: start vertex out of range");
-  Engine *e = refs[0].e;
-  return ret(e, e->sssp_over(refs.data(), (uint32_t)refs.size(), (uint32_t)n, start, dist, device_ms));
+  return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) {
+    if (start >= n) return bad("sssp: start vertex out of range");
+    return ret(e, e->sssp_over(r, P, n, start, dist, device_ms));
+  });
 }
 int pppcsr_components(pppcsr_t h, uint32_t *labels, double *device_ms) {
   PP_CHECK();
   if (!labels) return bad("components: null output");
-  std::vector<ppcsr::ConsumerRef> refs;
-  int rc = consumer_parts(h, &refs);
-  if (rc != 0) return rc;
-  uint64_t n = 0;
-  pppcsr_get_n(h, &n);
-  Engine *e = refs[0].e;
-  return ret(e, e->components_over(refs.data(), (uint32_t)refs.size(), (uint32_t)n, labels, device_ms));
+  return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) { return ret(e, e->components_over(r, P, n, labels, device_ms)); });
 }
 int pppcsr_kcore(pppcsr_t h, uint32_t *core, uint32_t *kmax, double *device_ms) {
   PP_CHECK();
   if (!core && !kmax) return bad("kcore: null outputs");
-  std::vector<ppcsr::ConsumerRef> refs;
-  int rc = consumer_parts(h, &refs);
-  if (rc != 0) return rc;
-  uint64_t n = 0;
-  pppcsr_get_n(h, &n);
-  Engine *e = refs[0].e;
-  return ret(e, e->kcore_over(refs.data(), (uint32_t)refs.size(), (uint32_t)n, core, kmax, device_ms));
+  return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) { return ret(e, e->kcore_over(r, P, n, core, kmax, device_ms)); });
 }
 int pppcsr_triangles(pppcsr_t h, uint64_t *tri, uint64_t *total, double *device_ms) {
   PP_CHECK();
   if (!tri && !total) return bad("triangles: null outputs");
-  std::vector<ppcsr::ConsumerRef> refs;
-  int rc = consumer_parts(h, &refs);
-  if (rc != 0) return rc;
-  uint64_t n = 0;
-  pppcsr_get_n(h, &n);
-  Engine *e = refs[0].e;
-  return ret(e, e->triangles_over(refs.data(), (uint32_t)refs.size(), (uint32_t)n, tri, total, device_ms));
+  return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) { return ret(e, e->triangles_over(r, P, n, tri, total, device_ms)); });
 }
 int pppcsr_common_neighbours(pppcsr_t h, const uint32_t *a, const uint32_t *b, uint64_t k, uint32_t *counts, double *device_ms) {
   PP_CHECK();
   if (k && (!a || !b || !counts)) return bad("common_neighbours: null argument");
-  std::vector<ppcsr::ConsumerRef> refs;
-  int rc = consumer_parts(h, &refs);
-  if (rc != 0) return rc;
-  uint64_t n = 0;
-  pppcsr_get_n(h, &n);
-  Engine *e = refs[0].e;
-  return ret(e, e->common_neighbours_over(refs.data(), (uint32_t)refs.size(), (uint32_t)n, a, b, k, counts, false, device_ms));
+  return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) {
+    return ret(e, e->common_neighbours_over(r, P, n, a, b, k, counts, false, device_ms));
+  });
 }
 
 int pppcsr_apply_parts_device(pppcsr_t h, uint64_t first_part, uint64_t n_parts, const ppcsr_op *const *d_ops, const uint64_t *counts) {

@@ -2166,546 +2166,6 @@ int Engine::bulk_build_from(const Op *in_ops, bool on_device, uint64_t m, double
   return PPCSR_OK;
 }
 
-// ---- consumers ------------------------------------------------------------------------------------
-// The consumers run over a table of gapped arrays (pma_scan.h: ConsumerPart) — a PPPCSR's partitions, or this engine alone —
-// on this engine's stream.  The partitions' own streams must be idle first: their last batch may still be in flight.
-// *slots = slots of all arrays; the table goes to the device (one copy, into *d_tab) unless d_tab is null.
-int Engine::consumer_table(const ConsumerRef *parts, uint32_t P, uint32_t total_n, void **d_tab, uint64_t *slots) {
-  Impl &p = *p_;
-  std::vector<ConsumerPart> tab(P + 1);
-  uint64_t chunks = 0, tot = 0;
-  for (uint32_t k = 0; k < P; k++) {
-    const Impl &q = *parts[k].e->p_;
-    if (parts[k].e != this) GCHK(gpu::sync(q.stream));
-    tab[k] = ConsumerPart{q.v.items, q.v.nodes, q.v.g.N, chunks, q.v.g.n, parts[k].first, {0, 0}};
-    chunks += (q.v.g.N + 63) / 64;
-    tot += q.v.g.N;
-  }
-  tab[P] = ConsumerPart{nullptr, nullptr, 0, chunks, 0, total_n, {0, 0}};
-  *slots = tot;
-  if (!d_tab) return PPCSR_OK;
-  GCHK(gpu::dmalloc(d_tab, (P + 1) * sizeof(ConsumerPart)));
-  GCHK(gpu::h2d(*d_tab, tab.data(), (P + 1) * sizeof(ConsumerPart), p.stream));
-  GCHK(gpu::sync(p.stream));
-  return PPCSR_OK;
-}
-
-// bfs.h:15-36: level of every vertex from `start` (UINT32_MAX = unreachable); one launch per level, whatever the number of arrays
-int Engine::bfs(uint32_t start, uint32_t *levels, double *device_ms) {
-  const ConsumerRef self{this, 0};
-  return bfs_over(&self, 1, n(), start, levels, device_ms);
-}
-int Engine::bfs_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t start, uint32_t *levels, double *device_ms) {
-  Impl &p = *p_;
-  GCHK(gpu::set_device(device_));
-  const uint32_t nn = total_n;
-  if (start >= nn) return fail(PPCSR_EINVAL, "bfs: start vertex out of range");
-  uint32_t *d_lv = nullptr, *d_f0 = nullptr, *d_f1 = nullptr, *d_cnt = nullptr, *d_fb = nullptr, *d_vb = nullptr;
-  ConsumerPart *d_tab = nullptr;
-  DevGuard tmpg;
-  tmpg.add(&d_lv); tmpg.add(&d_f0); tmpg.add(&d_f1); tmpg.add(&d_cnt); tmpg.add(&d_fb); tmpg.add(&d_vb); tmpg.add(&d_tab);
-  uint64_t N = 0;  // slots of all arrays: what one streaming pass reads
-  int rc = consumer_table(parts, P, nn, (void **)&d_tab, &N);
-  if (rc != PPCSR_OK) return rc;
-  const ConsumerPart *tab = d_tab;
-  const uint64_t bit_words = ((uint64_t)nn + 63) / 64 * 2;  // frontier / visited bitmaps of the streaming levels
-  GCHK(gpu::dmalloc((void **)&d_fb, bit_words * sizeof(uint32_t)));
-  GCHK(gpu::dmalloc((void **)&d_vb, bit_words * sizeof(uint32_t)));
-  GCHK(gpu::dmalloc((void **)&d_lv, (uint64_t)nn * sizeof(uint32_t)));
-  GCHK(gpu::dmalloc((void **)&d_f0, (uint64_t)nn * sizeof(uint32_t)));
-  GCHK(gpu::dmalloc((void **)&d_f1, (uint64_t)nn * sizeof(uint32_t)));
-  // [0] vertices found, [1] a hub was left to the streaming pass, [kBfsStripeWords...] the streaming pass's striped count
-  constexpr uint32_t cnt_words = (kBfsStripes + 1) * kBfsStripeWords;
-  GCHK(gpu::dmalloc((void **)&d_cnt, cnt_words * sizeof(uint32_t)));
-  p.timer.start(p.stream);
-  GCHK(gpu::dset(d_lv, 0xFF, (uint64_t)nn * sizeof(uint32_t), p.stream));
-  const uint32_t zero = 0;
-  GCHK(gpu::h2d(d_lv + start, &zero, sizeof(uint32_t), p.stream));
-  GCHK(gpu::h2d(d_f0, &start, sizeof(uint32_t), p.stream));
-  // Hybrid: a small frontier is expanded one wave per vertex (k_bfs_level, builds the next frontier list); a frontier that
-  // is a sizeable share of the graph is expanded by one streaming pass over every gapped array (k_bfs_edges_bits) — its cost
-  // does not depend on hub degrees — and the list is rebuilt only when the frontier becomes small again.
-  uint32_t nfront = 1, level = 0;
-  uint32_t *cur = d_f0, *nxt = d_f1;
-  std::vector<uint32_t> h_cnt(cnt_words, 0);
-  auto striped = [&]() {
-    uint32_t sum = 0;
-    for (uint32_t k = 1; k <= kBfsStripes; k++) sum += h_cnt[k * kBfsStripeWords];
-    return sum;
-  };
-  bool have_list = true;
-  const uint32_t big = (uint32_t)std::max<uint64_t>(64, (uint64_t)nn / 256);  // frontier size from which the pass is cheaper
-  while (nfront > 0) {
-    GCHK(gpu::dset(d_cnt, 0, cnt_words * sizeof(uint32_t), p.stream));
-    if (nfront >= big) {
-      GPU_LAUNCH(p.stream, k_bfs_bits, grid_for(nn, 256, 4096), 256, (const uint32_t *)d_lv, nn, level, d_fb, d_vb);
-      GPU_LAUNCH(p.stream, k_bfs_edges_bits, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, level, (const uint32_t *)d_fb, (const uint32_t *)d_vb, d_lv, d_cnt + kBfsStripeWords);
-      have_list = false;
-    } else {
-      if (!have_list) {  // (the pass only counted claims — an upper bound; the list gives the exact frontier)
-        GPU_LAUNCH(p.stream, k_bfs_collect, grid_for(nn, 256), 256, (const uint32_t *)d_lv, nn, level, cur, d_cnt);
-        GCHK(gpu::d2h(h_cnt.data(), d_cnt, sizeof(uint32_t), p.stream));
-        GCHK(gpu::sync(p.stream));
-        nfront = h_cnt[0];
-        GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), p.stream));
-      }
-      GPU_LAUNCH(p.stream, k_bfs_level, grid_for(nfront, 4, 16384), 256, tab, P, nn, (const uint32_t *)cur, nfront, level, d_lv, nxt, d_cnt);
-      have_list = true;
-      std::swap(cur, nxt);
-    }
-    GCHK(gpu::d2h(h_cnt.data(), d_cnt, cnt_words * sizeof(uint32_t), p.stream));
-    GCHK(gpu::sync(p.stream));
-    GCHK(gpu::last_error());
-    if (h_cnt[1]) {  // hubs of this level were skipped by the per-vertex kernel: one pass finishes the level
-      GPU_LAUNCH(p.stream, k_bfs_bits, grid_for(nn, 256, 4096), 256, (const uint32_t *)d_lv, nn, level, d_fb, d_vb);
-      GPU_LAUNCH(p.stream, k_bfs_edges_bits, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, level, (const uint32_t *)d_fb, (const uint32_t *)d_vb, d_lv, d_cnt + kBfsStripeWords);
-      GCHK(gpu::d2h(h_cnt.data(), d_cnt, cnt_words * sizeof(uint32_t), p.stream));
-      GCHK(gpu::sync(p.stream));
-      GCHK(gpu::last_error());
-      have_list = false;
-    }
-    nfront = h_cnt[0] + striped();
-    level++;
-  }
-  p.timer.stop(p.stream);
-  GCHK(gpu::d2h(levels, d_lv, (uint64_t)nn * sizeof(uint32_t), p.stream));
-  GCHK(gpu::sync(p.stream));
-  if (device_ms) *device_ms = p.timer.ms();
-  return PPCSR_OK;
-}
-
-// Shortest paths over the edge values (pma_paths.h).  The hybrid of bfs_over, with rounds in place of levels: stamp[] holds
-// the round for which a vertex was last made active, so the round's bitmap and list come from k_bfs_bits / k_bfs_collect.
-// One host read per round; the call ends when a round lowers no distance.
-int Engine::sssp(uint32_t start, uint64_t *dist, double *device_ms) {
-  const ConsumerRef self{this, 0};
-  return sssp_over(&self, 1, n(), start, dist, device_ms);
-}
-int Engine::sssp_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t start, uint64_t *dist, double *device_ms) {
-  Impl &p = *p_;
-  GCHK(gpu::set_device(device_));
-  const uint32_t nn = total_n;
-  if (start >= nn) return fail(PPCSR_EINVAL, "sssp: start vertex out of range");
-  unsigned long long *d_dist = nullptr;
-  uint32_t *d_st = nullptr, *d_f0 = nullptr, *d_f1 = nullptr, *d_cnt = nullptr, *d_ab = nullptr, *d_vb = nullptr;
-  ConsumerPart *d_tab = nullptr;
-  DevGuard tmpg;
-  tmpg.add(&d_dist); tmpg.add(&d_st); tmpg.add(&d_f0); tmpg.add(&d_f1); tmpg.add(&d_cnt); tmpg.add(&d_ab); tmpg.add(&d_vb); tmpg.add(&d_tab);
-  uint64_t N = 0;  // slots of all arrays: what one streaming pass reads
-  int rc = consumer_table(parts, P, nn, (void **)&d_tab, &N);
-  if (rc != PPCSR_OK) return rc;
-  const ConsumerPart *tab = d_tab;
-  const uint64_t bit_words = ((uint64_t)nn + 63) / 64 * 2;  // active bitmap of the streaming rounds (d_vb: k_bfs_bits' second output, unused)
-  GCHK(gpu::dmalloc((void **)&d_ab, bit_words * sizeof(uint32_t)));
-  GCHK(gpu::dmalloc((void **)&d_vb, bit_words * sizeof(uint32_t)));
-  GCHK(gpu::dmalloc((void **)&d_dist, (uint64_t)nn * sizeof(unsigned long long)));
-  GCHK(gpu::dmalloc((void **)&d_st, (uint64_t)nn * sizeof(uint32_t)));
-  GCHK(gpu::dmalloc((void **)&d_f0, (uint64_t)nn * sizeof(uint32_t)));
-  GCHK(gpu::dmalloc((void **)&d_f1, (uint64_t)nn * sizeof(uint32_t)));
-  // [0] vertices made active, [1] a hub was left to the streaming pass, [kBfsStripeWords...] the streaming pass's striped count
-  constexpr uint32_t cnt_words = (kBfsStripes + 1) * kBfsStripeWords;
-  GCHK(gpu::dmalloc((void **)&d_cnt, cnt_words * sizeof(uint32_t)));
-  p.timer.start(p.stream);
-  GCHK(gpu::dset(d_dist, 0xFF, (uint64_t)nn * sizeof(unsigned long long), p.stream));
-  GCHK(gpu::dset(d_st, 0, (uint64_t)nn * sizeof(uint32_t), p.stream));
-  const unsigned long long zero = 0;
-  uint32_t round = 1;  // (stamp 0: never active)
-  GCHK(gpu::h2d(d_dist + start, &zero, sizeof(zero), p.stream));
-  GCHK(gpu::h2d(d_st + start, &round, sizeof(uint32_t), p.stream));
-  GCHK(gpu::h2d(d_f0, &start, sizeof(uint32_t), p.stream));
-  uint32_t nact = 1;
-  uint32_t *cur = d_f0, *nxt = d_f1;
-  std::vector<uint32_t> h_cnt(cnt_words, 0);
-  auto striped = [&]() {
-    uint32_t sum = 0;
-    for (uint32_t k = 1; k <= kBfsStripes; k++) sum += h_cnt[k * kBfsStripeWords];
-    return sum;
-  };
-  auto stream_round = [&]() {
-    GPU_LAUNCH(p.stream, k_bfs_bits, grid_for(nn, 256, 4096), 256, (const uint32_t *)d_st, nn, round, d_ab, d_vb);
-    GPU_LAUNCH(p.stream, k_sssp_edges, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, round, (const uint32_t *)d_ab, d_dist, d_st, d_cnt + kBfsStripeWords);
-  };
-  bool have_list = true;
-  const uint32_t big = (uint32_t)std::max<uint64_t>(64, (uint64_t)nn / 256);  // active-set size from which the pass is cheaper (as in bfs_over)
-  while (nact > 0) {
-    GCHK(gpu::dset(d_cnt, 0, cnt_words * sizeof(uint32_t), p.stream));
-    if (nact >= big) {
-      stream_round();
-      have_list = false;
-    } else {
-      if (!have_list) {  // (both passes count the vertices they activate exactly; the list itself comes from the stamps)
-        GPU_LAUNCH(p.stream, k_bfs_collect, grid_for(nn, 256), 256, (const uint32_t *)d_st, nn, round, cur, d_cnt);
-        GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), p.stream));
-      }
-      GPU_LAUNCH(p.stream, k_sssp_relax, grid_for(nact, 4, 16384), 256, tab, P, nn, (const uint32_t *)cur, nact, round, d_dist, d_st, nxt, d_cnt);
-      have_list = true;
-      std::swap(cur, nxt);
-    }
-    GCHK(gpu::d2h(h_cnt.data(), d_cnt, cnt_words * sizeof(uint32_t), p.stream));
-    GCHK(gpu::sync(p.stream));
-    GCHK(gpu::last_error());
-    if (h_cnt[1]) {  // hubs of this round were skipped by the per-vertex kernel: one pass relaxes their edges
-      stream_round();
-      GCHK(gpu::d2h(h_cnt.data(), d_cnt, cnt_words * sizeof(uint32_t), p.stream));
-      GCHK(gpu::sync(p.stream));
-      GCHK(gpu::last_error());
-      have_list = false;
-    }
-    nact = h_cnt[0] + striped();
-    round++;
-  }
-  p.timer.stop(p.stream);
-  GCHK(gpu::d2h(dist, d_dist, (uint64_t)nn * sizeof(unsigned long long), p.stream));
-  GCHK(gpu::sync(p.stream));
-  if (device_ms) *device_ms = p.timer.ms();
-  return PPCSR_OK;
-}
-
-// Weakly connected components (pma_paths.h): hook pass + pointer jumping until a hook pass finds no edge with two labels;
-// one host read per round.
-int Engine::components(uint32_t *labels, double *device_ms) {
-  const ConsumerRef self{this, 0};
-  return components_over(&self, 1, n(), labels, device_ms);
-}
-int Engine::components_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t *labels, double *device_ms) {
-  Impl &p = *p_;
-  GCHK(gpu::set_device(device_));
-  const uint32_t nn = total_n;
-  uint32_t *d_lab = nullptr, *d_cnt = nullptr;
-  ConsumerPart *d_tab = nullptr;
-  DevGuard tmpg;
-  tmpg.add(&d_lab); tmpg.add(&d_cnt); tmpg.add(&d_tab);
-  uint64_t N = 0;
-  int rc = consumer_table(parts, P, nn, (void **)&d_tab, &N);
-  if (rc != PPCSR_OK) return rc;
-  const ConsumerPart *tab = d_tab;
-  GCHK(gpu::dmalloc((void **)&d_lab, std::max<uint64_t>(nn, 1) * sizeof(uint32_t)));
-  constexpr uint32_t cnt_words = kBfsStripes * kBfsStripeWords;
-  GCHK(gpu::dmalloc((void **)&d_cnt, cnt_words * sizeof(uint32_t)));
-  std::vector<uint32_t> h_cnt(cnt_words, 0);
-  p.timer.start(p.stream);
-  if (nn) GPU_LAUNCH(p.stream, k_cc_init, grid_for(nn, 256, 4096), 256, d_lab, nn);
-  for (bool more = nn != 0; more;) {
-    GCHK(gpu::dset(d_cnt, 0, cnt_words * sizeof(uint32_t), p.stream));
-    GPU_LAUNCH(p.stream, k_cc_hook, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, d_lab, d_cnt);
-    GPU_LAUNCH(p.stream, k_cc_jump, grid_for(nn, 256, 4096), 256, d_lab, nn);
-    GCHK(gpu::d2h(h_cnt.data(), d_cnt, cnt_words * sizeof(uint32_t), p.stream));
-    GCHK(gpu::sync(p.stream));
-    GCHK(gpu::last_error());
-    more = false;
-    for (uint32_t k = 0; k < kBfsStripes; k++) more = more || h_cnt[k * kBfsStripeWords] != 0;
-  }
-  p.timer.stop(p.stream);
-  if (nn) GCHK(gpu::d2h(labels, d_lab, (uint64_t)nn * sizeof(uint32_t), p.stream));
-  GCHK(gpu::sync(p.stream));
-  if (device_ms) *device_ms = p.timer.ms();
-  return PPCSR_OK;
-}
-
-// Core numbers (pma_cores.h).  Stage 1 exports the upper-orientation graph as a compact symmetric adjacency (degree pass,
-// scan, fill pass); stage 2 peels it level by level in sub-rounds.  One host read of the small counter block per level (the
-// level and its first frontier) and per sub-round (the next frontier, the deferred long lists).  device_ms covers the whole
-// call: besides the kernels it holds the host read of the edge total and the allocation of the lists between the scan and
-// the fill pass, and every round trip of the peel.
-int Engine::kcore(uint32_t *core, uint32_t *kmax, double *device_ms) {
-  const ConsumerRef self{this, 0};
-  return kcore_over(&self, 1, n(), core, kmax, device_ms);
-}
-int Engine::kcore_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t *core, uint32_t *kmax, double *device_ms) {
-  Impl &p = *p_;
-  GCHK(gpu::set_device(device_));
-  const uint32_t nn = total_n;
-  uint32_t *d_deg = nullptr, *d_core = nullptr, *d_fill = nullptr, *d_adj = nullptr, *d_f0 = nullptr, *d_f1 = nullptr, *d_long = nullptr, *d_cnt = nullptr;
-  unsigned long long *d_off = nullptr, *d_tiles = nullptr;
-  ConsumerPart *d_tab = nullptr;
-  DevGuard tmpg;
-  tmpg.add(&d_deg); tmpg.add(&d_core); tmpg.add(&d_fill); tmpg.add(&d_adj); tmpg.add(&d_f0); tmpg.add(&d_f1); tmpg.add(&d_long); tmpg.add(&d_cnt);
-  tmpg.add(&d_off); tmpg.add(&d_tiles); tmpg.add(&d_tab);
-  uint64_t N = 0;  // slots of all arrays: what one streaming pass reads
-  int rc = consumer_table(parts, P, nn, (void **)&d_tab, &N);
-  if (rc != PPCSR_OK) return rc;
-  const ConsumerPart *tab = d_tab;
-  const uint64_t words = std::max<uint64_t>(nn, 1);
-  const uint32_t ntiles = (uint32_t)(((uint64_t)nn + kKcTile - 1) / kKcTile);
-  GCHK(gpu::dmalloc((void **)&d_deg, words * sizeof(uint32_t)));
-  GCHK(gpu::dmalloc((void **)&d_core, words * sizeof(uint32_t)));
-  GCHK(gpu::dmalloc((void **)&d_fill, words * sizeof(uint32_t)));
-  GCHK(gpu::dmalloc((void **)&d_f0, words * sizeof(uint32_t)));  // (a vertex enters one frontier once: no list exceeds n)
-  GCHK(gpu::dmalloc((void **)&d_f1, words * sizeof(uint32_t)));
-  GCHK(gpu::dmalloc((void **)&d_long, words * sizeof(uint32_t)));
-  GCHK(gpu::dmalloc((void **)&d_off, (words + 1) * sizeof(unsigned long long)));
-  GCHK(gpu::dmalloc((void **)&d_tiles, std::max<uint64_t>(ntiles, 1) * sizeof(unsigned long long)));
-  GCHK(gpu::dmalloc((void **)&d_cnt, kKcCntWords * sizeof(uint32_t)));
-  uint32_t top = 0;
-  p.timer.start(p.stream);
-  if (nn) {
-    // stage 1: deg[], off[] (off[nn] = 2 |E(G)|), adj[]
-    GCHK(gpu::dset(d_deg, 0, words * sizeof(uint32_t), p.stream));
-    GCHK(gpu::dset(d_fill, 0, words * sizeof(uint32_t), p.stream));
-    GPU_LAUNCH(p.stream, k_kc_init, grid_for(nn, 256, 4096), 256, d_core, nn);
-    GPU_LAUNCH(p.stream, k_kc_degree, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, d_deg);
-    GPU_LAUNCH(p.stream, k_kc_tile_sums, grid_for(ntiles, 1, 65536), 256, (const uint32_t *)d_deg, nn, ntiles, d_tiles);
-    GPU_LAUNCH(p.stream, k_kc_scan_tiles, 1, 64, d_tiles, ntiles, d_off + nn);
-    GPU_LAUNCH(p.stream, k_kc_scan_write, grid_for(ntiles, 1, 65536), 256, (const uint32_t *)d_deg, nn, ntiles, (const unsigned long long *)d_tiles, d_off);
-    unsigned long long entries = 0;
-    GCHK(gpu::d2h(&entries, d_off + nn, sizeof(entries), p.stream));
-    GCHK(gpu::sync(p.stream));
-    GCHK(gpu::last_error());
-    GCHK(gpu::dmalloc((void **)&d_adj, std::max<uint64_t>(entries, 1) * sizeof(uint32_t)));
-    GPU_LAUNCH(p.stream, k_kc_fill, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, (const unsigned long long *)d_off, d_fill, d_adj);
-    // stage 2
-    uint32_t h_cnt[4] = {0, 0, 0, 0};  // (host copy of the three words of the counter block that are in use, padded to 16 bytes)
-    uint32_t *cur = d_f0, *nxt = d_f1;
-    for (;;) {
-      GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), p.stream));
-      GCHK(gpu::dset(d_cnt + 2, 0xFF, sizeof(uint32_t), p.stream));
-      GPU_LAUNCH(p.stream, k_kc_min, grid_for(nn, 256, 1024), 256, (const uint32_t *)d_deg, (const uint32_t *)d_core, nn, d_cnt);
-      GPU_LAUNCH(p.stream, k_kc_collect, grid_for(nn, 256), 256, (const uint32_t *)d_deg, d_core, nn, cur, d_cnt);
-      GCHK(gpu::d2h(h_cnt, d_cnt, 3 * sizeof(uint32_t), p.stream));
-      GCHK(gpu::sync(p.stream));
-      GCHK(gpu::last_error());
-      uint32_t nfront = h_cnt[0];
-      const uint32_t k = h_cnt[2];
-      if (nfront == 0) break;  // (k == kMax: every vertex is assigned)
-      top = k;
-      while (nfront > 0) {
-        GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), p.stream));
-        GPU_LAUNCH(p.stream, k_kc_peel, grid_for(nfront, 4, 16384), 256, (const unsigned long long *)d_off, (const uint32_t *)d_adj, (const uint32_t *)cur,
-                   nfront, k, d_deg, d_core, nxt, d_long, d_cnt);
-        GCHK(gpu::d2h(h_cnt, d_cnt, 2 * sizeof(uint32_t), p.stream));
-        GCHK(gpu::sync(p.stream));
-        GCHK(gpu::last_error());
-        if (h_cnt[1]) {  // lists beyond one wave's reach: a second launch splits them over waves and appends to the same frontier
-          GPU_LAUNCH(p.stream, k_kc_peel_long, grid_for((uint64_t)h_cnt[1] * 16, 4, 4096), 256, (const unsigned long long *)d_off, (const uint32_t *)d_adj,
-                     (const uint32_t *)d_long, h_cnt[1], k, d_deg, d_core, nxt, d_cnt);
-          GCHK(gpu::d2h(h_cnt, d_cnt, sizeof(uint32_t), p.stream));
-          GCHK(gpu::sync(p.stream));
-          GCHK(gpu::last_error());
-        }
-        nfront = h_cnt[0];
-        std::swap(cur, nxt);
-      }
-    }
-  }
-  p.timer.stop(p.stream);
-  if (core && nn) GCHK(gpu::d2h(core, d_core, (uint64_t)nn * sizeof(uint32_t), p.stream));
-  GCHK(gpu::sync(p.stream));
-  if (kmax) *kmax = top;
-  if (device_ms) *device_ms = p.timer.ms();
-  return PPCSR_OK;
-}
-
-// Triangle counts and common-neighbour counts (pma_intersect.h).  Both intersect vertex ranges as sorted lists, which holds
-// in the regular regime only: a partition in the sequential regime (narrow == 0: ranges may be unsorted or overlapping until
-// the next re-check) is refused rather than answered on a wrong assumption.
-int Engine::intersect_regime(const ConsumerRef *parts, uint32_t P, const char *what, std::string *msg) {
-  for (uint32_t k = 0; k < P; k++)
-    if (parts[k].e->p_->v.g.narrow == 0u) {
-      *msg = std::string(what) + ": the structure is in the sequential regime (add_node after a doubling: vertex ranges may be unsorted "
-             "or overlapping, stats.narrow == 0) and sorted ranges cannot be intersected; it ends at the next range re-check";
-      return PPCSR_EUNSUPPORTED;
-    }
-  return PPCSR_OK;
-}
-int Engine::triangles(uint64_t *tri, uint64_t *total, double *device_ms) {
-  const ConsumerRef self{this, 0};
-  return triangles_over(&self, 1, n(), tri, total, device_ms);
-}
-int Engine::triangles_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint64_t *tri, uint64_t *total, double *device_ms) {
-  Impl &p = *p_;
-  GCHK(gpu::set_device(device_));
-  const uint32_t nn = total_n;
-  std::string msg;
-  if (intersect_regime(parts, P, "triangles", &msg) != PPCSR_OK) return fail(PPCSR_EUNSUPPORTED, msg);
-  unsigned long long *d_tri = nullptr, *d_tot = nullptr;
-  uint32_t *d_list = nullptr, *d_cnt = nullptr;
-  ConsumerPart *d_tab = nullptr;
-  DevGuard tmpg;
-  tmpg.add(&d_tri); tmpg.add(&d_tot); tmpg.add(&d_list); tmpg.add(&d_cnt); tmpg.add(&d_tab);
-  uint64_t N = 0;
-  int rc = consumer_table(parts, P, nn, (void **)&d_tab, &N);
-  if (rc != PPCSR_OK) return rc;
-  const ConsumerPart *tab = d_tab;
-  uint64_t chunks = 0;
-  for (uint32_t k = 0; k < P; k++) chunks += (parts[k].e->N() + 63) / 64;
-  if (chunks >= (1ull << 32)) return fail(PPCSR_EUNSUPPORTED, "triangles: more than 2^32 chunks");
-  constexpr uint32_t tot_words = kBfsStripes * kTriStripeWords;
-  if (tri) GCHK(gpu::dmalloc((void **)&d_tri, std::max<uint64_t>(nn, 1) * sizeof(unsigned long long)));
-  GCHK(gpu::dmalloc((void **)&d_tot, tot_words * sizeof(unsigned long long)));
-  GCHK(gpu::dmalloc((void **)&d_list, std::max<uint64_t>(chunks, 1) * sizeof(uint32_t)));  // chunks that hold an edge with a long range
-  GCHK(gpu::dmalloc((void **)&d_cnt, 32 * sizeof(uint32_t)));
-  p.timer.start(p.stream);
-  if (tri) GCHK(gpu::dset(d_tri, 0, std::max<uint64_t>(nn, 1) * sizeof(unsigned long long), p.stream));
-  GCHK(gpu::dset(d_tot, 0, tot_words * sizeof(unsigned long long), p.stream));
-  GCHK(gpu::dset(d_cnt, 0, 32 * sizeof(uint32_t), p.stream));
-  GPU_LAUNCH(p.stream, k_tri_edges, grid_for(chunks, 4, 8192), 256, tab, P, nn, d_tri, d_tot, d_list, d_cnt);
-  uint32_t ndefer = 0;
-  GCHK(gpu::d2h(&ndefer, d_cnt, sizeof(uint32_t), p.stream));
-  GCHK(gpu::sync(p.stream));
-  GCHK(gpu::last_error());
-  if (ndefer) GPU_LAUNCH(p.stream, k_tri_long, grid_for((uint64_t)ndefer * 4, 1, 16384), 256, tab, P, nn, d_tri, d_tot, (const uint32_t *)d_list, ndefer);
-  p.timer.stop(p.stream);
-  std::vector<unsigned long long> h_tot(tot_words, 0);
-  GCHK(gpu::d2h(h_tot.data(), d_tot, tot_words * sizeof(unsigned long long), p.stream));
-  if (tri && nn) GCHK(gpu::d2h(tri, d_tri, (uint64_t)nn * sizeof(unsigned long long), p.stream));
-  GCHK(gpu::sync(p.stream));
-  GCHK(gpu::last_error());
-  if (total) {
-    *total = 0;
-    for (uint32_t k = 0; k < kBfsStripes; k++) *total += h_tot[(uint64_t)k * kTriStripeWords];
-  }
-  if (device_ms) *device_ms = p.timer.ms();
-  return PPCSR_OK;
-}
-
-// pairs and counts: host memory (staged through the buffers of lookup_edges, lookup_stage pairs at a time), or this GPU's
-int Engine::common_neighbours(const uint32_t *a, const uint32_t *b, uint64_t k, uint32_t *counts, bool on_device, double *device_ms) {
-  const ConsumerRef self{this, 0};
-  return common_neighbours_over(&self, 1, n(), a, b, k, counts, on_device, device_ms);
-}
-int Engine::common_neighbours_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const uint32_t *a, const uint32_t *b, uint64_t nq,
-                                   uint32_t *counts, bool on_device, double *device_ms) {
-  Impl &p = *p_;
-  GCHK(gpu::set_device(device_));
-  std::string msg;
-  if (intersect_regime(parts, P, "common_neighbours", &msg) != PPCSR_OK) return fail(PPCSR_EUNSUPPORTED, msg);
-  if (device_ms) *device_ms = 0.0;
-  ConsumerPart *d_tab = nullptr;
-  DevGuard tmpg;
-  tmpg.add(&d_tab);
-  uint64_t N = 0;
-  int rc = consumer_table(parts, P, total_n, (void **)&d_tab, &N);
-  if (rc != PPCSR_OK) return rc;
-  if (nq == 0) return PPCSR_OK;
-  const ConsumerPart *tab = d_tab;
-  if (on_device) {
-    p.timer.start(p.stream);
-    GPU_LAUNCH(p.stream, k_common_neighbours, query_blocks(p, (nq + 63) / 64), 256, tab, P, total_n, a, b, nq, counts);
-    p.timer.stop(p.stream);
-    GCHK(gpu::sync(p.stream));
-    if (device_ms) *device_ms = p.timer.ms();
-  } else {
-    const uint64_t stage = std::min(nq, p.q.lookup_stage);
-    if (stage > p.q.lookup_cap) {
-      uint64_t c0 = p.q.lookup_cap, c1 = p.q.lookup_cap, c2 = p.q.lookup_cap;
-      if (grow_buf(&p.q.src, &c0, stage) || grow_buf(&p.q.dst, &c1, stage) || grow_buf(&p.q.val, &c2, stage)) {
-        p.q.lookup_cap = 0;
-        return fail(PPCSR_ENOMEM, "common_neighbours: staging");
-      }
-      p.q.lookup_cap = stage;
-    }
-    for (uint64_t i0 = 0; i0 < nq; i0 += stage) {
-      const uint64_t m = std::min(stage, nq - i0);
-      GCHK(gpu::h2d(p.q.src, a + i0, m * sizeof(uint32_t), p.stream));
-      GCHK(gpu::h2d(p.q.dst, b + i0, m * sizeof(uint32_t), p.stream));
-      p.timer.start(p.stream);
-      GPU_LAUNCH(p.stream, k_common_neighbours, query_blocks(p, (m + 63) / 64), 256, tab, P, total_n, (const uint32_t *)p.q.src,
-                 (const uint32_t *)p.q.dst, m, p.q.val);
-      p.timer.stop(p.stream);
-      GCHK(gpu::d2h(counts + i0, p.q.val, m * sizeof(uint32_t), p.stream));
-      GCHK(gpu::sync(p.stream));
-      if (device_ms) *device_ms += p.timer.ms();
-    }
-  }
-  GCHK(gpu::sync(p.stream));
-  GCHK(gpu::last_error());
-  return PPCSR_OK;
-}
-
-// stable sort of (key, value) pairs by key: rocPRIM's radix sort on the device, std::stable_sort in the CPU emulator
-static int sort_pairs_stable(gpu::stream_t st, uint32_t *kin, uint32_t *kout, float *vin, float *vout, uint64_t m, unsigned bits) {
-#if defined(PPCSR_SIM)
-  (void)st;
-  (void)bits;
-  std::vector<uint64_t> idx(m);
-  for (uint64_t i = 0; i < m; i++) idx[i] = i;
-  std::stable_sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) { return kin[a] < kin[b]; });
-  for (uint64_t i = 0; i < m; i++) {
-    kout[i] = kin[idx[i]];
-    vout[i] = vin[idx[i]];
-  }
-  return 0;
-#else
-  size_t tmp_bytes = 0;
-  if (rocprim::radix_sort_pairs(nullptr, tmp_bytes, kin, kout, vin, vout, (size_t)m, 0u, bits, st) != hipSuccess) return 3;
-  void *tmp = nullptr;
-  if (hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 1) != hipSuccess) return 2;
-  const hipError_t e = rocprim::radix_sort_pairs(tmp, tmp_bytes, kin, kout, vin, vout, (size_t)m, 0u, bits, st);
-  (void)hipStreamSynchronize(st);
-  (void)hipFree(tmp);
-  return e == hipSuccess ? 0 : 3;
-#endif
-}
-
-// pagerank.h:15-29: out[d] = sum over edges (s, d), in ascending s, of node_values[s] / num_neighbors(s).  The bulk scan
-// emits (dest, contribution) per edge in CSR order — array after array, in partition order, which is ascending global source
-// order because the partitions hold ascending vertex ranges — a STABLE sort by dest keeps ascending source order inside every
-// destination, and one thread per destination adds its run sequentially: the reference's order of fp32 additions.
-int Engine::pagerank(const float *node_values, float *out, double *device_ms) {
-  const ConsumerRef self{this, 0};
-  return pagerank_over(&self, 1, n(), node_values, out, device_ms);
-}
-int Engine::pagerank_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const float *node_values, float *out, double *device_ms) {
-  Impl &p = *p_;
-  GCHK(gpu::set_device(device_));
-  const uint32_t nn = total_n;
-  float *d_val = nullptr, *d_c0 = nullptr, *d_c1 = nullptr, *d_out = nullptr;
-  uint32_t *d_k0 = nullptr, *d_k1 = nullptr;
-  uint32_t *d_long = nullptr;  // [0]: count, [1..]: destinations with long runs
-  DevGuard tmpg;
-  tmpg.add(&d_val); tmpg.add(&d_c0); tmpg.add(&d_c1); tmpg.add(&d_out); tmpg.add(&d_k0); tmpg.add(&d_k1); tmpg.add(&d_long);
-  uint64_t N = 0;  // slots of all arrays: room for every edge
-  int rc = consumer_table(parts, P, nn, nullptr, &N);
-  if (rc != PPCSR_OK) return rc;
-  GCHK(gpu::dmalloc((void **)&d_val, (uint64_t)nn * sizeof(float)));
-  GCHK(gpu::dmalloc((void **)&d_out, (uint64_t)nn * sizeof(float)));
-  GCHK(gpu::dmalloc((void **)&d_k0, N * sizeof(uint32_t)));
-  GCHK(gpu::dmalloc((void **)&d_k1, N * sizeof(uint32_t)));
-  GCHK(gpu::dmalloc((void **)&d_c0, N * sizeof(float)));
-  GCHK(gpu::dmalloc((void **)&d_c1, N * sizeof(float)));
-  GCHK(gpu::h2d(d_val, node_values, (uint64_t)nn * sizeof(float), p.stream));
-  p.timer.start(p.stream);
-  // every array's edge count first (its place in the shared key / contribution arrays), then the contribution passes; the
-  // first array's pass needs no count (it starts at 0) and goes out with its counts, as the one-engine call always did
-  std::vector<uint32_t> tile(P);
-  std::vector<uint64_t> ntiles(P);
-  for (uint32_t k = 0; k < P; k++) {
-    rc = scan_count(parts[k].e, &tile[k], &ntiles[k]);
-    if (rc != PPCSR_OK) return rc;
-    const Impl &q = *parts[k].e->p_;
-    if (k == 0)
-      scan_write(parts[0].e, tile[0], ntiles[0], nullptr, reinterpret_cast<int *>(d_k0), q.v.g.N, d_val + parts[0].first, d_c0, nullptr, 0, nn);
-    GCHK(gpu::d2h(q.h_total, q.d_total, sizeof(unsigned long long), p.stream));
-  }
-  GCHK(gpu::sync(p.stream));
-  GCHK(gpu::last_error());
-  uint64_t m = 0;
-  for (uint32_t k = 0; k < P; k++) {
-    const uint64_t mk = *parts[k].e->p_->h_total;
-    if (k > 0)
-      scan_write(parts[k].e, tile[k], ntiles[k], nullptr, reinterpret_cast<int *>(d_k0 + m), mk, d_val + parts[k].first, d_c0 + m, nullptr,
-                 0, nn);
-    m += mk;
-  }
-  if (m) {
-    unsigned bits = 1;  // keys are clamped to [0, n]
-    while (bits < 32 && ((uint64_t)nn >> bits) != 0) bits++;
-    rc = sort_pairs_stable(p.stream, d_k0, d_k1, d_c0, d_c1, m, bits);
-    if (rc != 0) return fail(rc == 2 ? PPCSR_ENOMEM : PPCSR_EHIP, "pagerank: device sort failed");
-  }
-  GCHK(gpu::dmalloc((void **)&d_long, ((uint64_t)nn + 1) * sizeof(uint32_t)));
-  GCHK(gpu::dset(d_long, 0, sizeof(uint32_t), p.stream));
-  GPU_LAUNCH(p.stream, k_pr_segsum, grid_for(nn, 256), 256, (const uint32_t *)d_k1, (const float *)d_c1, m, nn, d_out, d_long + 1, d_long);
-  GPU_LAUNCH(p.stream, k_pr_longruns, 2048, 256, (const uint32_t *)d_k1, (const float *)d_c1, m, (const uint32_t *)(d_long + 1),
-             (const uint32_t *)d_long, d_out);
-  p.timer.stop(p.stream);
-  GCHK(gpu::d2h(out, d_out, (uint64_t)nn * sizeof(float), p.stream));
-  GCHK(gpu::sync(p.stream));
-  GCHK(gpu::last_error());
-  if (device_ms) *device_ms = p.timer.ms();
-  return PPCSR_OK;
-}
-
 int Engine::scan_all_device(double *ms, uint64_t *total) {
   Impl &p = *p_;
   GCHK(gpu::set_device(device_));
@@ -3423,3 +2883,7 @@ int capi_h2d_sync(void *dst, const void *src, size_t bytes) {
   if (e) return e;
   return gpu::sync(st);
 }
+
+// the consumers' host drivers: a source file of their own inside this unit, so that every build that
+// compiles engine.cc — the library's and the emulator's — sees them
+#include "engine_consumers.cc"

@@ -13,7 +13,7 @@ namespace ppcsr {
 struct View;  // pma_device.h
 struct Edge;
 
-// one partition of a consumer call over several engines (bfs_over / pagerank_over): its engine and its first global vertex
+// one partition of a consumer call (bfs_over and the others): its engine and its first global vertex
 class Engine;
 struct ConsumerRef {
   Engine *e;
@@ -94,31 +94,25 @@ class Engine {
   // graph-algorithm consumers over the gapped array (reference: src/utility/bfs.h, src/utility/pagerank.h)
   int bulk_build(const Op *host_ops, uint64_t m, double *device_ms);  // non-parity fast path
   int bulk_build_device(const Op *d_adds, uint64_t m, double *device_ms);  // the same, adds already in HBM (pppcsr_repartition)
-  int bfs(uint32_t start, uint32_t *levels, double *device_ms);
-  int pagerank(const float *node_values, float *out, double *device_ms);
-  // the same over P engines that hold consecutive vertex ranges of one graph of total_n vertices (a PPPCSR's partitions, in
-  // partition order; edges stored with a local src and a global dest).  Runs on THIS engine's stream and device, which every
-  // partition must share; bfs / pagerank are the one-partition case.  Writes nothing to any partition's graph state.
+  // Consumers (engine_consumers.cc) over P engines that hold consecutive vertex ranges of one graph of total_n vertices (a
+  // PPPCSR's partitions, in partition order; edges stored with a local src and a global dest); one engine is the one-entry case
+  // {this, 0}.  They run on THIS engine's stream and device, which every partition must share, and write nothing to any
+  // partition's graph state.
   int bfs_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t start, uint32_t *levels, double *device_ms);
   int pagerank_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const float *node_values, float *out, double *device_ms);
   // shortest paths over the edge values (dist: total_n entries, UINT64_MAX = no path) and weakly connected components
-  // (labels[v] = smallest vertex id of v's component), under the same contract (pma_paths.h)
-  int sssp(uint32_t start, uint64_t *dist, double *device_ms);
-  int components(uint32_t *labels, double *device_ms);
+  // (labels[v] = smallest vertex id of v's component) (pma_paths.h)
   int sssp_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t start, uint64_t *dist, double *device_ms);
   int components_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t *labels, double *device_ms);
-  // core numbers of the upper-orientation graph triangles counts in (pma_cores.h), under the same contract and in either
-  // regime: core (total_n entries, may be null), *kmax (may be null): the largest core number
-  int kcore(uint32_t *core, uint32_t *kmax, double *device_ms);
+  // core numbers of the upper-orientation graph triangles counts in (pma_cores.h), in either regime: core (total_n entries,
+  // may be null), *kmax (may be null): the largest core number
   int kcore_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t *core, uint32_t *kmax, double *device_ms);
-  // consumers that intersect two neighbourhoods (pma_intersect.h), under the same contract.  triangles: upper orientation —
-  // {a, b}, a < b, is an edge exactly when (a, b) is stored; tri (total_n entries, may be null): triangles through every
-  // vertex; *total (may be null): triangles.  common_neighbours: counts[i] = stored dests < total_n shared by a[i] and b[i]
-  // (vertices >= total_n: 0); a, b, counts are host memory, or this GPU's when on_device.  Both fail with PPCSR_EUNSUPPORTED
-  // while a partition is in the sequential regime (narrow == 0).
-  int triangles(uint64_t *tri, uint64_t *total, double *device_ms);
+  // consumers that intersect two neighbourhoods (pma_intersect.h).  triangles: upper orientation — {a, b}, a < b, is an edge
+  // exactly when (a, b) is stored; tri (total_n entries, may be null): triangles through every vertex; *total (may be null):
+  // triangles.  common_neighbours: counts[i] = stored dests < total_n shared by a[i] and b[i] (vertices >= total_n: 0); a, b,
+  // counts are host memory, or this GPU's when on_device.  Both fail with PPCSR_EUNSUPPORTED while a partition is in the
+  // sequential regime (narrow == 0).
   int triangles_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint64_t *tri, uint64_t *total, double *device_ms);
-  int common_neighbours(const uint32_t *a, const uint32_t *b, uint64_t k, uint32_t *counts, bool on_device, double *device_ms);
   int common_neighbours_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const uint32_t *a, const uint32_t *b, uint64_t k,
                              uint32_t *counts, bool on_device, double *device_ms);
   int export_state(Edge *items, Node *nodes);
@@ -177,6 +171,7 @@ class Engine {
   struct Impl;
 
  private:
+  struct ConsumerScope;  // engine_consumers.cc
   Impl *p_;
   int device_ = 0;
   std::string err_;

@@ -1,0 +1,497 @@
+// Host drivers of the graph-algorithm consumers (kernels: pma_consumer.h, pma_scan.h, pma_paths.h, pma_cores.h,
+// pma_intersect.h).  Included at the end of engine.cc: part of the engine's single translation unit, in the library
+// (csrc/ppcsr_hip.hip) and in the emulator (tests/hostsim/ppcsr_sim.cpp) alike.
+namespace ppcsr {
+
+// The consumers run over a table of gapped arrays (pma_consumer.h: ConsumerPart) — a PPPCSR's partitions, or one engine alone —
+// on this engine's stream.  The partitions' own streams must be idle first: their last batch may still be in flight.
+// *slots = slots of all arrays; the table goes to the device (one copy, into *d_tab) unless d_tab is null.
+int Engine::consumer_table(const ConsumerRef *parts, uint32_t P, uint32_t total_n, void **d_tab, uint64_t *slots) {
+  Impl &p = *p_;
+  std::vector<ConsumerPart> tab(P + 1);
+  uint64_t chunks = 0, tot = 0;
+  for (uint32_t k = 0; k < P; k++) {
+    const Impl &q = *parts[k].e->p_;
+    if (parts[k].e != this) GCHK(gpu::sync(q.stream));
+    tab[k] = ConsumerPart{q.v.items, q.v.nodes, q.v.g.N, chunks, q.v.g.n, parts[k].first, {0, 0}};
+    chunks += (q.v.g.N + 63) / 64;
+    tot += q.v.g.N;
+  }
+  tab[P] = ConsumerPart{nullptr, nullptr, 0, chunks, 0, total_n, {0, 0}};
+  *slots = tot;
+  if (!d_tab) return PPCSR_OK;
+  GCHK(gpu::dmalloc(d_tab, (P + 1) * sizeof(ConsumerPart)));
+  GCHK(gpu::h2d(*d_tab, tab.data(), (P + 1) * sizeof(ConsumerPart), p.stream));
+  GCHK(gpu::sync(p.stream));
+  return PPCSR_OK;
+}
+
+// Triangle counts and common-neighbour counts intersect vertex ranges as sorted lists, which holds in the regular regime
+// only: a partition in the sequential regime (narrow == 0: ranges may be unsorted or overlapping until the next re-check) is
+// refused rather than answered on a wrong assumption.
+int Engine::intersect_regime(const ConsumerRef *parts, uint32_t P, const char *what, std::string *msg) {
+  for (uint32_t k = 0; k < P; k++)
+    if (parts[k].e->p_->v.g.narrow == 0u) {
+      *msg = std::string(what) + ": the structure is in the sequential regime (add_node after a doubling: vertex ranges may be unsorted "
+             "or overlapping, stats.narrow == 0) and sorted ranges cannot be intersected; it ends at the next range re-check";
+      return PPCSR_EUNSUPPORTED;
+    }
+  return PPCSR_OK;
+}
+
+// counter block of the hybrid loop: [0] vertices found, [1] a hub was left to the streaming pass, [kBfsStripeWords...] the
+// streaming pass's striped count
+constexpr uint32_t kHybridCntWords = (kBfsStripes + 1) * kBfsStripeWords;
+
+// One consumer call: what every *_over does before and after its own launches.  open() selects the device, refuses the
+// sequential regime for a consumer that intersects, and builds the table; alloc() hands out the call's device buffers, all of
+// which are freed on every exit path; start() / stop() / done() run the timer and hand device_ms out.
+struct Engine::ConsumerScope {
+  Engine &eng;
+  Impl &p;
+  std::vector<void *> bufs;
+  const ConsumerPart *tab_ = nullptr;
+  uint64_t slots_ = 0;
+  int rc = PPCSR_OK;  // the first allocation that failed (later ones are not tried)
+
+  explicit ConsumerScope(Engine *e) : eng(*e), p(*e->p_) {}
+  ConsumerScope(const ConsumerScope &) = delete;  // (it owns the buffers; a launch's arguments are copies of plain pointers)
+  ~ConsumerScope() {
+    for (void *b : bufs) gpu::dfree(b);
+  }
+  int fail(int code, const std::string &msg) { return eng.fail(code, msg); }
+  // intersects: the consumer's name when it needs sorted, disjoint vertex ranges
+  int open(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const char *intersects = nullptr, bool device_table = true) {
+    GCHK(gpu::set_device(eng.device_));
+    std::string msg;
+    if (intersects && eng.intersect_regime(parts, P, intersects, &msg) != PPCSR_OK) return fail(PPCSR_EUNSUPPORTED, msg);
+    void *d_tab = nullptr;
+    const int e = eng.consumer_table(parts, P, total_n, device_table ? &d_tab : nullptr, &slots_);
+    if (d_tab) bufs.push_back(d_tab);
+    tab_ = static_cast<const ConsumerPart *>(d_tab);
+    return e;
+  }
+  const ConsumerPart *table() const { return tab_; }
+  uint64_t slots() const { return slots_; }  // slots of all arrays: what one streaming pass reads
+  template <class T>
+  T *alloc(const char *what, uint64_t count) {
+    void *b = nullptr;
+    if (rc != PPCSR_OK) return nullptr;
+    const int e = gpu::dmalloc(&b, count * sizeof(T));
+    if (e != 0) {
+      rc = fail(PPCSR_EHIP, std::string("device allocation of ") + what + ": " + gpu::err_str(e));
+      return nullptr;
+    }
+    bufs.push_back(b);
+    return static_cast<T *>(b);
+  }
+  void start() { p.timer.start(p.stream); }
+  void stop() { p.timer.stop(p.stream); }
+  int done(double *device_ms) {
+    GCHK(gpu::sync(p.stream));
+    GCHK(gpu::last_error());
+    if (device_ms) *device_ms = p.timer.ms();
+    return PPCSR_OK;
+  }
+
+  // The hybrid loop of bfs_over and sssp_over, from a frontier of one vertex (in d_f0) at step `step` until a step finds
+  // nothing.  A small frontier is expanded one wave per vertex (per_vertex(cur, nfront, step, nxt): builds the next frontier
+  // list); a frontier that is a sizeable share of the graph is expanded by one streaming pass over every gapped array
+  // (pass(step)) — its cost does not depend on hub degrees — and the list is rebuilt from d_key (levels / stamps: the
+  // frontier is { v : key[v] == step }) only when the frontier becomes small again.  One host read per step.
+  // reread_list: the pass's count is an upper bound (BFS counts claims), so the exact length is read back with the list;
+  // an exact count (SSSP: the stamp admits each vertex once) is not read again.
+  template <class Pass, class PerVertex>
+  int hybrid(uint32_t nn, const uint32_t *d_key, uint32_t step, uint32_t *d_f0, uint32_t *d_f1, uint32_t *d_cnt, bool reread_list, Pass pass,
+             PerVertex per_vertex) {
+    uint32_t nfront = 1;
+    uint32_t *cur = d_f0, *nxt = d_f1;
+    std::vector<uint32_t> h_cnt(kHybridCntWords, 0);
+    bool have_list = true;
+    const uint32_t big = (uint32_t)std::max<uint64_t>(64, (uint64_t)nn / 256);  // frontier size from which the pass is cheaper
+    for (; nfront > 0; step++) {
+      GCHK(gpu::dset(d_cnt, 0, kHybridCntWords * sizeof(uint32_t), p.stream));
+      if (nfront >= big) {
+        pass(step);
+        have_list = false;
+      } else {
+        if (!have_list) {
+          GPU_LAUNCH(p.stream, k_bfs_collect, grid_for(nn, 256), 256, d_key, nn, step, cur, d_cnt);
+          if (reread_list) {
+            GCHK(gpu::d2h(h_cnt.data(), d_cnt, sizeof(uint32_t), p.stream));
+            GCHK(gpu::sync(p.stream));
+            nfront = h_cnt[0];
+          }
+          GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), p.stream));
+        }
+        per_vertex((const uint32_t *)cur, nfront, step, nxt);
+        have_list = true;
+        std::swap(cur, nxt);
+      }
+      GCHK(gpu::d2h(h_cnt.data(), d_cnt, kHybridCntWords * sizeof(uint32_t), p.stream));
+      GCHK(gpu::sync(p.stream));
+      GCHK(gpu::last_error());
+      if (h_cnt[1]) {  // hubs of this step were skipped by the per-vertex kernel: one pass finishes the step
+        pass(step);
+        GCHK(gpu::d2h(h_cnt.data(), d_cnt, kHybridCntWords * sizeof(uint32_t), p.stream));
+        GCHK(gpu::sync(p.stream));
+        GCHK(gpu::last_error());
+        have_list = false;
+      }
+      nfront = h_cnt[0];
+      for (uint32_t k = 1; k <= kBfsStripes; k++) nfront += h_cnt[k * kBfsStripeWords];
+    }
+    return PPCSR_OK;
+  }
+};
+
+// bfs.h:15-36: level of every vertex from `start` (UINT32_MAX = unreachable); one launch per level, whatever the number of arrays
+int Engine::bfs_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t start, uint32_t *levels, double *device_ms) {
+  const uint32_t nn = total_n;
+  if (start >= nn) return fail(PPCSR_EINVAL, "bfs: start vertex out of range");  // (refused before the device is even selected)
+  ConsumerScope cs(this);
+  int rc = cs.open(parts, P, nn);
+  if (rc != PPCSR_OK) return rc;
+  Impl &p = *p_;
+  const ConsumerPart *tab = cs.table();
+  const uint64_t N = cs.slots();
+  const uint64_t bit_words = ((uint64_t)nn + 63) / 64 * 2;  // frontier / visited bitmaps of the streaming levels
+  uint32_t *d_fb = cs.alloc<uint32_t>("d_fb", bit_words), *d_vb = cs.alloc<uint32_t>("d_vb", bit_words);
+  uint32_t *d_lv = cs.alloc<uint32_t>("d_lv", nn), *d_f0 = cs.alloc<uint32_t>("d_f0", nn), *d_f1 = cs.alloc<uint32_t>("d_f1", nn);
+  uint32_t *d_cnt = cs.alloc<uint32_t>("d_cnt", kHybridCntWords);
+  if (cs.rc != PPCSR_OK) return cs.rc;
+  cs.start();
+  GCHK(gpu::dset(d_lv, 0xFF, (uint64_t)nn * sizeof(uint32_t), p.stream));
+  const uint32_t zero = 0;
+  GCHK(gpu::h2d(d_lv + start, &zero, sizeof(uint32_t), p.stream));
+  GCHK(gpu::h2d(d_f0, &start, sizeof(uint32_t), p.stream));
+  rc = cs.hybrid(
+      nn, d_lv, 0, d_f0, d_f1, d_cnt, true,
+      [&](uint32_t level) {
+        GPU_LAUNCH(p.stream, k_bfs_bits, grid_for(nn, 256, 4096), 256, (const uint32_t *)d_lv, nn, level, d_fb, d_vb);
+        GPU_LAUNCH(p.stream, k_bfs_edges_bits, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, level, (const uint32_t *)d_fb,
+                   (const uint32_t *)d_vb, d_lv, d_cnt + kBfsStripeWords);
+      },
+      [&](const uint32_t *cur, uint32_t nfront, uint32_t level, uint32_t *nxt) {
+        GPU_LAUNCH(p.stream, k_bfs_level, grid_for(nfront, 4, 16384), 256, tab, P, nn, cur, nfront, level, d_lv, nxt, d_cnt);
+      });
+  if (rc != PPCSR_OK) return rc;
+  cs.stop();
+  GCHK(gpu::d2h(levels, d_lv, (uint64_t)nn * sizeof(uint32_t), p.stream));
+  return cs.done(device_ms);
+}
+
+// Shortest paths over the edge values (pma_paths.h).  The hybrid loop with rounds in place of levels: stamp[] holds the round
+// for which a vertex was last made active, so the round's bitmap and list come from k_bfs_bits / k_bfs_collect.  The call
+// ends when a round lowers no distance.
+int Engine::sssp_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t start, uint64_t *dist, double *device_ms) {
+  const uint32_t nn = total_n;
+  if (start >= nn) return fail(PPCSR_EINVAL, "sssp: start vertex out of range");
+  ConsumerScope cs(this);
+  int rc = cs.open(parts, P, nn);
+  if (rc != PPCSR_OK) return rc;
+  Impl &p = *p_;
+  const ConsumerPart *tab = cs.table();
+  const uint64_t N = cs.slots();
+  const uint64_t bit_words = ((uint64_t)nn + 63) / 64 * 2;  // active bitmap of the streaming rounds (d_vb: k_bfs_bits' second output, unused)
+  uint32_t *d_ab = cs.alloc<uint32_t>("d_ab", bit_words), *d_vb = cs.alloc<uint32_t>("d_vb", bit_words);
+  unsigned long long *d_dist = cs.alloc<unsigned long long>("d_dist", nn);
+  uint32_t *d_st = cs.alloc<uint32_t>("d_st", nn), *d_f0 = cs.alloc<uint32_t>("d_f0", nn), *d_f1 = cs.alloc<uint32_t>("d_f1", nn);
+  uint32_t *d_cnt = cs.alloc<uint32_t>("d_cnt", kHybridCntWords);
+  if (cs.rc != PPCSR_OK) return cs.rc;
+  cs.start();
+  GCHK(gpu::dset(d_dist, 0xFF, (uint64_t)nn * sizeof(unsigned long long), p.stream));
+  GCHK(gpu::dset(d_st, 0, (uint64_t)nn * sizeof(uint32_t), p.stream));
+  const unsigned long long zero = 0;
+  const uint32_t round0 = 1;  // (stamp 0: never active)
+  GCHK(gpu::h2d(d_dist + start, &zero, sizeof(zero), p.stream));
+  GCHK(gpu::h2d(d_st + start, &round0, sizeof(uint32_t), p.stream));
+  GCHK(gpu::h2d(d_f0, &start, sizeof(uint32_t), p.stream));
+  rc = cs.hybrid(
+      nn, d_st, round0, d_f0, d_f1, d_cnt, false,
+      [&](uint32_t round) {
+        GPU_LAUNCH(p.stream, k_bfs_bits, grid_for(nn, 256, 4096), 256, (const uint32_t *)d_st, nn, round, d_ab, d_vb);
+        GPU_LAUNCH(p.stream, k_sssp_edges, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, round, (const uint32_t *)d_ab, d_dist, d_st,
+                   d_cnt + kBfsStripeWords);
+      },
+      [&](const uint32_t *cur, uint32_t nact, uint32_t round, uint32_t *nxt) {
+        GPU_LAUNCH(p.stream, k_sssp_relax, grid_for(nact, 4, 16384), 256, tab, P, nn, cur, nact, round, d_dist, d_st, nxt, d_cnt);
+      });
+  if (rc != PPCSR_OK) return rc;
+  cs.stop();
+  GCHK(gpu::d2h(dist, d_dist, (uint64_t)nn * sizeof(unsigned long long), p.stream));
+  return cs.done(device_ms);
+}
+
+// Weakly connected components (pma_paths.h): hook pass + pointer jumping until a hook pass finds no edge with two labels;
+// one host read per round.
+int Engine::components_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t *labels, double *device_ms) {
+  const uint32_t nn = total_n;
+  ConsumerScope cs(this);
+  const int rc = cs.open(parts, P, nn);
+  if (rc != PPCSR_OK) return rc;
+  Impl &p = *p_;
+  const ConsumerPart *tab = cs.table();
+  const uint64_t N = cs.slots();
+  constexpr uint32_t cnt_words = kBfsStripes * kBfsStripeWords;
+  uint32_t *d_lab = cs.alloc<uint32_t>("d_lab", std::max<uint64_t>(nn, 1)), *d_cnt = cs.alloc<uint32_t>("d_cnt", cnt_words);
+  if (cs.rc != PPCSR_OK) return cs.rc;
+  std::vector<uint32_t> h_cnt(cnt_words, 0);
+  cs.start();
+  if (nn) GPU_LAUNCH(p.stream, k_cc_init, grid_for(nn, 256, 4096), 256, d_lab, nn);
+  for (bool more = nn != 0; more;) {
+    GCHK(gpu::dset(d_cnt, 0, cnt_words * sizeof(uint32_t), p.stream));
+    GPU_LAUNCH(p.stream, k_cc_hook, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, d_lab, d_cnt);
+    GPU_LAUNCH(p.stream, k_cc_jump, grid_for(nn, 256, 4096), 256, d_lab, nn);
+    GCHK(gpu::d2h(h_cnt.data(), d_cnt, cnt_words * sizeof(uint32_t), p.stream));
+    GCHK(gpu::sync(p.stream));
+    GCHK(gpu::last_error());
+    more = false;
+    for (uint32_t k = 0; k < kBfsStripes; k++) more = more || h_cnt[k * kBfsStripeWords] != 0;
+  }
+  cs.stop();
+  if (nn) GCHK(gpu::d2h(labels, d_lab, (uint64_t)nn * sizeof(uint32_t), p.stream));
+  return cs.done(device_ms);
+}
+
+// Core numbers (pma_cores.h).  Stage 1 exports the upper-orientation graph as a compact symmetric adjacency (degree pass,
+// scan, fill pass); stage 2 peels it level by level in sub-rounds.  One host read of the small counter block per level (the
+// level and its first frontier) and per sub-round (the next frontier, the deferred long lists).  device_ms covers the whole
+// call: besides the kernels it holds the host read of the edge total and the allocation of the lists between the scan and
+// the fill pass, and every round trip of the peel.
+int Engine::kcore_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t *core, uint32_t *kmax, double *device_ms) {
+  const uint32_t nn = total_n;
+  ConsumerScope cs(this);
+  const int rc = cs.open(parts, P, nn);
+  if (rc != PPCSR_OK) return rc;
+  Impl &p = *p_;
+  const ConsumerPart *tab = cs.table();
+  const uint64_t N = cs.slots();
+  const uint64_t words = std::max<uint64_t>(nn, 1);
+  const uint32_t ntiles = (uint32_t)(((uint64_t)nn + kKcTile - 1) / kKcTile);
+  uint32_t *d_deg = cs.alloc<uint32_t>("d_deg", words), *d_core = cs.alloc<uint32_t>("d_core", words), *d_fill = cs.alloc<uint32_t>("d_fill", words);
+  uint32_t *d_f0 = cs.alloc<uint32_t>("d_f0", words), *d_f1 = cs.alloc<uint32_t>("d_f1", words);  // (a vertex enters one frontier once: no list exceeds n)
+  uint32_t *d_long = cs.alloc<uint32_t>("d_long", words);
+  unsigned long long *d_off = cs.alloc<unsigned long long>("d_off", words + 1), *d_tiles = cs.alloc<unsigned long long>("d_tiles", std::max<uint64_t>(ntiles, 1));
+  uint32_t *d_cnt = cs.alloc<uint32_t>("d_cnt", kKcCntWords);
+  if (cs.rc != PPCSR_OK) return cs.rc;
+  uint32_t top = 0;
+  cs.start();
+  if (nn) {
+    // stage 1: deg[], off[] (off[nn] = 2 |E(G)|), adj[]
+    GCHK(gpu::dset(d_deg, 0, words * sizeof(uint32_t), p.stream));
+    GCHK(gpu::dset(d_fill, 0, words * sizeof(uint32_t), p.stream));
+    GPU_LAUNCH(p.stream, k_kc_init, grid_for(nn, 256, 4096), 256, d_core, nn);
+    GPU_LAUNCH(p.stream, k_kc_degree, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, d_deg);
+    GPU_LAUNCH(p.stream, k_kc_tile_sums, grid_for(ntiles, 1, 65536), 256, (const uint32_t *)d_deg, nn, ntiles, d_tiles);
+    GPU_LAUNCH(p.stream, k_kc_scan_tiles, 1, 64, d_tiles, ntiles, d_off + nn);
+    GPU_LAUNCH(p.stream, k_kc_scan_write, grid_for(ntiles, 1, 65536), 256, (const uint32_t *)d_deg, nn, ntiles, (const unsigned long long *)d_tiles, d_off);
+    unsigned long long entries = 0;
+    GCHK(gpu::d2h(&entries, d_off + nn, sizeof(entries), p.stream));
+    GCHK(gpu::sync(p.stream));
+    GCHK(gpu::last_error());
+    uint32_t *d_adj = cs.alloc<uint32_t>("d_adj", std::max<uint64_t>(entries, 1));
+    if (cs.rc != PPCSR_OK) return cs.rc;
+    GPU_LAUNCH(p.stream, k_kc_fill, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, (const unsigned long long *)d_off, d_fill, d_adj);
+    // stage 2
+    uint32_t h_cnt[4] = {0, 0, 0, 0};  // (host copy of the three words of the counter block that are in use, padded to 16 bytes)
+    uint32_t *cur = d_f0, *nxt = d_f1;
+    for (;;) {
+      GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), p.stream));
+      GCHK(gpu::dset(d_cnt + 2, 0xFF, sizeof(uint32_t), p.stream));
+      GPU_LAUNCH(p.stream, k_kc_min, grid_for(nn, 256, 1024), 256, (const uint32_t *)d_deg, (const uint32_t *)d_core, nn, d_cnt);
+      GPU_LAUNCH(p.stream, k_kc_collect, grid_for(nn, 256), 256, (const uint32_t *)d_deg, d_core, nn, cur, d_cnt);
+      GCHK(gpu::d2h(h_cnt, d_cnt, 3 * sizeof(uint32_t), p.stream));
+      GCHK(gpu::sync(p.stream));
+      GCHK(gpu::last_error());
+      uint32_t nfront = h_cnt[0];
+      const uint32_t k = h_cnt[2];
+      if (nfront == 0) break;  // (k == kMax: every vertex is assigned)
+      top = k;
+      while (nfront > 0) {
+        GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), p.stream));
+        GPU_LAUNCH(p.stream, k_kc_peel, grid_for(nfront, 4, 16384), 256, (const unsigned long long *)d_off, (const uint32_t *)d_adj, (const uint32_t *)cur,
+                   nfront, k, d_deg, d_core, nxt, d_long, d_cnt);
+        GCHK(gpu::d2h(h_cnt, d_cnt, 2 * sizeof(uint32_t), p.stream));
+        GCHK(gpu::sync(p.stream));
+        GCHK(gpu::last_error());
+        if (h_cnt[1]) {  // lists beyond one wave's reach: a second launch splits them over waves and appends to the same frontier
+          GPU_LAUNCH(p.stream, k_kc_peel_long, grid_for((uint64_t)h_cnt[1] * 16, 4, 4096), 256, (const unsigned long long *)d_off, (const uint32_t *)d_adj,
+                     (const uint32_t *)d_long, h_cnt[1], k, d_deg, d_core, nxt, d_cnt);
+          GCHK(gpu::d2h(h_cnt, d_cnt, sizeof(uint32_t), p.stream));
+          GCHK(gpu::sync(p.stream));
+          GCHK(gpu::last_error());
+        }
+        nfront = h_cnt[0];
+        std::swap(cur, nxt);
+      }
+    }
+  }
+  cs.stop();
+  if (core && nn) GCHK(gpu::d2h(core, d_core, (uint64_t)nn * sizeof(uint32_t), p.stream));
+  if (kmax) *kmax = top;
+  return cs.done(device_ms);
+}
+
+// Triangle counts (pma_intersect.h): one pass over every chunk, then the chunks that hold an edge with a long range again
+int Engine::triangles_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint64_t *tri, uint64_t *total, double *device_ms) {
+  const uint32_t nn = total_n;
+  ConsumerScope cs(this);
+  int rc = cs.open(parts, P, nn, "triangles");
+  if (rc != PPCSR_OK) return rc;
+  Impl &p = *p_;
+  const ConsumerPart *tab = cs.table();
+  uint64_t chunks = 0;
+  for (uint32_t k = 0; k < P; k++) chunks += (parts[k].e->N() + 63) / 64;
+  if (chunks >= (1ull << 32)) return fail(PPCSR_EUNSUPPORTED, "triangles: more than 2^32 chunks");
+  constexpr uint32_t tot_words = kBfsStripes * kTriStripeWords;
+  unsigned long long *d_tri = tri ? cs.alloc<unsigned long long>("d_tri", std::max<uint64_t>(nn, 1)) : nullptr;
+  unsigned long long *d_tot = cs.alloc<unsigned long long>("d_tot", tot_words);
+  uint32_t *d_list = cs.alloc<uint32_t>("d_list", std::max<uint64_t>(chunks, 1));  // chunks that hold an edge with a long range
+  uint32_t *d_cnt = cs.alloc<uint32_t>("d_cnt", 32);
+  if (cs.rc != PPCSR_OK) return cs.rc;
+  cs.start();
+  if (tri) GCHK(gpu::dset(d_tri, 0, std::max<uint64_t>(nn, 1) * sizeof(unsigned long long), p.stream));
+  GCHK(gpu::dset(d_tot, 0, tot_words * sizeof(unsigned long long), p.stream));
+  GCHK(gpu::dset(d_cnt, 0, 32 * sizeof(uint32_t), p.stream));
+  GPU_LAUNCH(p.stream, k_tri_edges, grid_for(chunks, 4, 8192), 256, tab, P, nn, d_tri, d_tot, d_list, d_cnt);
+  uint32_t ndefer = 0;
+  GCHK(gpu::d2h(&ndefer, d_cnt, sizeof(uint32_t), p.stream));
+  GCHK(gpu::sync(p.stream));
+  GCHK(gpu::last_error());
+  if (ndefer) GPU_LAUNCH(p.stream, k_tri_long, grid_for((uint64_t)ndefer * 4, 1, 16384), 256, tab, P, nn, d_tri, d_tot, (const uint32_t *)d_list, ndefer);
+  cs.stop();
+  std::vector<unsigned long long> h_tot(tot_words, 0);
+  GCHK(gpu::d2h(h_tot.data(), d_tot, tot_words * sizeof(unsigned long long), p.stream));
+  if (tri && nn) GCHK(gpu::d2h(tri, d_tri, (uint64_t)nn * sizeof(unsigned long long), p.stream));
+  rc = cs.done(device_ms);
+  if (rc == PPCSR_OK && total) {
+    *total = 0;
+    for (uint32_t k = 0; k < kBfsStripes; k++) *total += h_tot[(uint64_t)k * kTriStripeWords];
+  }
+  return rc;
+}
+
+// Common-neighbour counts (pma_intersect.h).  Pairs and counts: host memory (staged through the buffers of lookup_edges,
+// lookup_stage pairs at a time), or this GPU's
+int Engine::common_neighbours_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const uint32_t *a, const uint32_t *b, uint64_t nq,
+                                   uint32_t *counts, bool on_device, double *device_ms) {
+  ConsumerScope cs(this);
+  const int rc = cs.open(parts, P, total_n, "common_neighbours");
+  if (rc != PPCSR_OK) return rc;
+  if (device_ms) *device_ms = 0.0;  // (a call that open() refuses leaves *device_ms alone, as every other consumer does)
+  if (nq == 0) return PPCSR_OK;
+  Impl &p = *p_;
+  const ConsumerPart *tab = cs.table();
+  if (on_device) {
+    cs.start();
+    GPU_LAUNCH(p.stream, k_common_neighbours, query_blocks(p, (nq + 63) / 64), 256, tab, P, total_n, a, b, nq, counts);
+    cs.stop();
+    return cs.done(device_ms);
+  }
+  const uint64_t stage = std::min(nq, p.q.lookup_stage);
+  if (stage > p.q.lookup_cap) {
+    uint64_t c0 = p.q.lookup_cap, c1 = p.q.lookup_cap, c2 = p.q.lookup_cap;
+    if (grow_buf(&p.q.src, &c0, stage) || grow_buf(&p.q.dst, &c1, stage) || grow_buf(&p.q.val, &c2, stage)) {
+      p.q.lookup_cap = 0;
+      return fail(PPCSR_ENOMEM, "common_neighbours: staging");
+    }
+    p.q.lookup_cap = stage;
+  }
+  for (uint64_t i0 = 0; i0 < nq; i0 += stage) {
+    const uint64_t m = std::min(stage, nq - i0);
+    GCHK(gpu::h2d(p.q.src, a + i0, m * sizeof(uint32_t), p.stream));
+    GCHK(gpu::h2d(p.q.dst, b + i0, m * sizeof(uint32_t), p.stream));
+    cs.start();
+    GPU_LAUNCH(p.stream, k_common_neighbours, query_blocks(p, (m + 63) / 64), 256, tab, P, total_n, (const uint32_t *)p.q.src,
+               (const uint32_t *)p.q.dst, m, p.q.val);
+    cs.stop();
+    GCHK(gpu::d2h(counts + i0, p.q.val, m * sizeof(uint32_t), p.stream));
+    GCHK(gpu::sync(p.stream));
+    if (device_ms) *device_ms += p.timer.ms();
+  }
+  return cs.done(nullptr);
+}
+
+// stable sort of (key, value) pairs by key: rocPRIM's radix sort on the device, std::stable_sort in the CPU emulator
+static int sort_pairs_stable(gpu::stream_t st, uint32_t *kin, uint32_t *kout, float *vin, float *vout, uint64_t m, unsigned bits) {
+#if defined(PPCSR_SIM)
+  (void)st;
+  (void)bits;
+  std::vector<uint64_t> idx(m);
+  for (uint64_t i = 0; i < m; i++) idx[i] = i;
+  std::stable_sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) { return kin[a] < kin[b]; });
+  for (uint64_t i = 0; i < m; i++) {
+    kout[i] = kin[idx[i]];
+    vout[i] = vin[idx[i]];
+  }
+  return 0;
+#else
+  size_t tmp_bytes = 0;
+  if (rocprim::radix_sort_pairs(nullptr, tmp_bytes, kin, kout, vin, vout, (size_t)m, 0u, bits, st) != hipSuccess) return 3;
+  void *tmp = nullptr;
+  if (hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 1) != hipSuccess) return 2;
+  const hipError_t e = rocprim::radix_sort_pairs(tmp, tmp_bytes, kin, kout, vin, vout, (size_t)m, 0u, bits, st);
+  (void)hipStreamSynchronize(st);
+  (void)hipFree(tmp);
+  return e == hipSuccess ? 0 : 3;
+#endif
+}
+
+// pagerank.h:15-29: out[d] = sum over edges (s, d), in ascending s, of node_values[s] / num_neighbors(s).  The bulk scan
+// emits (dest, contribution) per edge in CSR order — array after array, in partition order, which is ascending global source
+// order because the partitions hold ascending vertex ranges — a STABLE sort by dest keeps ascending source order inside every
+// destination, and one thread per destination adds its run sequentially: the reference's order of fp32 additions.
+int Engine::pagerank_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const float *node_values, float *out, double *device_ms) {
+  const uint32_t nn = total_n;
+  ConsumerScope cs(this);
+  int rc = cs.open(parts, P, nn, nullptr, false);
+  if (rc != PPCSR_OK) return rc;
+  Impl &p = *p_;
+  const uint64_t N = cs.slots();  // room for every edge
+  float *d_val = cs.alloc<float>("d_val", nn), *d_out = cs.alloc<float>("d_out", nn);
+  uint32_t *d_k0 = cs.alloc<uint32_t>("d_k0", N), *d_k1 = cs.alloc<uint32_t>("d_k1", N);
+  float *d_c0 = cs.alloc<float>("d_c0", N), *d_c1 = cs.alloc<float>("d_c1", N);
+  if (cs.rc != PPCSR_OK) return cs.rc;
+  GCHK(gpu::h2d(d_val, node_values, (uint64_t)nn * sizeof(float), p.stream));
+  cs.start();
+  // every array's edge count first (its place in the shared key / contribution arrays), then the contribution passes; the
+  // first array's pass needs no count (it starts at 0) and goes out with its counts, as the one-engine call always did
+  std::vector<uint32_t> tile(P);
+  std::vector<uint64_t> ntiles(P);
+  for (uint32_t k = 0; k < P; k++) {
+    rc = scan_count(parts[k].e, &tile[k], &ntiles[k]);
+    if (rc != PPCSR_OK) return rc;
+    const Impl &q = *parts[k].e->p_;
+    if (k == 0)
+      scan_write(parts[0].e, tile[0], ntiles[0], nullptr, reinterpret_cast<int *>(d_k0), q.v.g.N, d_val + parts[0].first, d_c0, nullptr, 0, nn);
+    GCHK(gpu::d2h(q.h_total, q.d_total, sizeof(unsigned long long), p.stream));
+  }
+  GCHK(gpu::sync(p.stream));
+  GCHK(gpu::last_error());
+  uint64_t m = 0;
+  for (uint32_t k = 0; k < P; k++) {
+    const uint64_t mk = *parts[k].e->p_->h_total;
+    if (k > 0)
+      scan_write(parts[k].e, tile[k], ntiles[k], nullptr, reinterpret_cast<int *>(d_k0 + m), mk, d_val + parts[k].first, d_c0 + m, nullptr,
+                 0, nn);
+    m += mk;
+  }
+  if (m) {
+    unsigned bits = 1;  // keys are clamped to [0, n]
+    while (bits < 32 && ((uint64_t)nn >> bits) != 0) bits++;
+    rc = sort_pairs_stable(p.stream, d_k0, d_k1, d_c0, d_c1, m, bits);
+    if (rc != 0) return fail(rc == 2 ? PPCSR_ENOMEM : PPCSR_EHIP, "pagerank: device sort failed");
+  }
+  uint32_t *d_long = cs.alloc<uint32_t>("d_long", (uint64_t)nn + 1);  // [0]: count, [1..]: destinations with long runs
+  if (cs.rc != PPCSR_OK) return cs.rc;
+  GCHK(gpu::dset(d_long, 0, sizeof(uint32_t), p.stream));
+  GPU_LAUNCH(p.stream, k_pr_segsum, grid_for(nn, 256), 256, (const uint32_t *)d_k1, (const float *)d_c1, m, nn, d_out, d_long + 1, d_long);
+  GPU_LAUNCH(p.stream, k_pr_longruns, 2048, 256, (const uint32_t *)d_k1, (const float *)d_c1, m, (const uint32_t *)(d_long + 1),
+             (const uint32_t *)d_long, d_out);
+  cs.stop();
+  GCHK(gpu::d2h(out, d_out, (uint64_t)nn * sizeof(float), p.stream));
+  return cs.done(device_ms);
+}
+
+}  // namespace ppcsr

@@ -1,6 +1,6 @@
-// Core numbers (k-core decomposition) over the table of gapped arrays (pma_scan.h: ConsumerPart, cp_chunk_owner).  The edge
-// set is the one k_cc_hook streams: live non-sentinel slots, slot N-1 excluded, local src < n_p, global dests < n — taken from
-// each item's own src, so nothing here assumes that vertex ranges are sorted or disjoint (the sequential regime is answered).
+// Core numbers (k-core decomposition) over the table of gapped arrays (pma_consumer.h).  The edge set is the one k_cc_hook
+// streams: the live edges of cp_load_chunks — taken from each item's own src, so nothing here assumes that vertex ranges
+// are sorted or disjoint (the sequential regime is answered).
 // The undirected graph G is the one k_tri_edges counts in, the upper orientation: {a, b}, a < b < n, is an edge exactly when
 // the pair (a, b) is stored; pairs with src > dst and self-loops play no part.  A pair is stored at most once, so G is simple.
 //
@@ -45,7 +45,8 @@
 // The frontier a sub-round appends is a function of the graph (w crosses k exactly when enough of its neighbours are in
 // frontiers of this level), so levels and sub-rounds equal those of a synchronous peel on the host.
 #pragma once
-#include "pma_paths.h"
+#include "pma_consumer.h"
+#include "pma_paths.h"  // kCcRunLanes
 
 namespace ppcsr {
 
@@ -81,49 +82,27 @@ PMA_DEV void kc_source_runs(bool up, uint32_t src, int lane, bool &lead, uint32_
   }
 }
 
-// four 64-slot chunks of the concatenated chunk space (the load phase of k_cc_hook): per chunk the lane's item, whether it
-// is an upper edge of G, and its global source
-constexpr int kKcChunks = 4;
-PMA_DEV void kc_load_chunks(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, uint64_t ch0, uint64_t nchunks, int lane,
-                            Edge *e, uint32_t *a, bool *up) {
-#pragma unroll
-  for (int b = 0; b < kKcChunks; b++) {
-    const Edge *items = tab[0].items;  // (one array: no search)
-    uint64_t s = (ch0 + b) * 64 + (uint64_t)lane, N = tab[0].N;
-    uint32_t first = 0, pn = tab[0].n;
-    if (P > 1 && ch0 + b < nchunks) {
-      const uint32_t k = cp_chunk_owner(tab, P, ch0 + b);
-      items = tab[k].items;
-      s -= tab[k].chunk0 * 64;
-      N = tab[k].N;
-      first = tab[k].first;
-      pn = tab[k].n;
-    }
-    e[b] = null_edge();
-    if (ch0 + b < nchunks && s + 1 < N) e[b] = items[s];  // (slot N-1 is never part of a neighbourhood)
-    const bool live = e[b].value != 0 && !is_sentinel(e[b]) && e[b].src < pn && e[b].dest < n;
-    a[b] = e[b].src + first;
-    up[b] = live && a[b] < e[b].dest;
-  }
-}
-
 // ---- stage 1: the symmetric adjacency of G ---------------------------------------------------------------------------------------------
+// (both passes: the streaming load, then per chunk the upper edges of G and their source runs)
 PMA_KERNEL void k_kc_degree(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, uint32_t *deg) {
   const int lane = wv::lane();
   const uint64_t nchunks = tab[P].chunk0;
-  const uint64_t wstride = (uint64_t)wv::grid_dim() * (wv::block_dim() >> 6);
-  constexpr int kB = kKcChunks;
-  for (uint64_t ch0 = wv::uni(((uint64_t)wv::block_idx() * (wv::block_dim() >> 6) + wv::wave_in_block()) * kB); ch0 < nchunks;
-       ch0 += wstride * kB) {
+  const uint64_t wstride = cp_waves();
+  const Edge *const items0 = tab[0].items;
+  const uint64_t N0 = tab[0].N;
+  const uint32_t n0 = tab[0].n;
+  constexpr int kB = 4;
+  for (uint64_t ch0 = wv::uni(cp_wave() * kB); ch0 < nchunks; ch0 += wstride * kB) {
     Edge e[kB];
     uint32_t a[kB];
     bool up[kB];
-    kc_load_chunks(tab, P, n, ch0, nchunks, lane, e, a, up);
+    cp_load_chunks<kB>(tab, P, n, items0, N0, n0, ch0, nchunks, lane, e, a, up);
 #pragma unroll
     for (int b = 0; b < kB; b++) {
       bool lead;
       uint32_t cnt, rank;
       int leader;
+      up[b] = up[b] && a[b] < e[b].dest;
       kc_source_runs(up[b], a[b], lane, lead, cnt, rank, leader);
       if (lead) wv::atomic_add_u32(&deg[a[b]], cnt);
       if (up[b]) wv::atomic_add_u32(&deg[e[b].dest], 1u);
@@ -135,19 +114,22 @@ PMA_KERNEL void k_kc_fill(const ConsumerPart *__restrict__ tab, uint32_t P, uint
                           uint32_t *fill, uint32_t *adj) {
   const int lane = wv::lane();
   const uint64_t nchunks = tab[P].chunk0;
-  const uint64_t wstride = (uint64_t)wv::grid_dim() * (wv::block_dim() >> 6);
-  constexpr int kB = kKcChunks;
-  for (uint64_t ch0 = wv::uni(((uint64_t)wv::block_idx() * (wv::block_dim() >> 6) + wv::wave_in_block()) * kB); ch0 < nchunks;
-       ch0 += wstride * kB) {
+  const uint64_t wstride = cp_waves();
+  const Edge *const items0 = tab[0].items;
+  const uint64_t N0 = tab[0].N;
+  const uint32_t n0 = tab[0].n;
+  constexpr int kB = 4;
+  for (uint64_t ch0 = wv::uni(cp_wave() * kB); ch0 < nchunks; ch0 += wstride * kB) {
     Edge e[kB];
     uint32_t a[kB];
     bool up[kB];
-    kc_load_chunks(tab, P, n, ch0, nchunks, lane, e, a, up);
+    cp_load_chunks<kB>(tab, P, n, items0, N0, n0, ch0, nchunks, lane, e, a, up);
 #pragma unroll
     for (int b = 0; b < kB; b++) {
       bool lead;
       uint32_t cnt, rank;
       int leader;
+      up[b] = up[b] && a[b] < e[b].dest;
       kc_source_runs(up[b], a[b], lane, lead, cnt, rank, leader);
       uint32_t base = 0;
       if (lead) base = wv::atomic_add_u32(&fill[a[b]], cnt);
@@ -253,7 +235,7 @@ PMA_KERNEL void k_kc_min(const uint32_t *__restrict__ deg, const uint32_t *__res
   }
 }
 // first frontier of the level k = cnt[2] (written by the launch before): every unassigned vertex with deg == k is assigned
-// and listed, in the ballot-and-one-atomic-per-wave form of k_bfs_collect
+// and listed
 PMA_KERNEL void k_kc_collect(const uint32_t *__restrict__ deg, uint32_t *core, uint32_t n, uint32_t *front, uint32_t *cnt) {
   const int lane = wv::lane();
   const uint32_t k = cnt[2];
@@ -262,16 +244,8 @@ PMA_KERNEL void k_kc_collect(const uint32_t *__restrict__ deg, uint32_t *core, u
   for (uint64_t base = (uint64_t)wv::block_idx() * wv::block_dim() + (wv::thread_idx() & ~63u); base < n; base += stride) {
     const uint64_t u = base + (uint64_t)lane;
     const bool in = u < n && core[u] == kMax && deg[u] == k;
-    const uint64_t m = wv::ballot(in);
-    if (m) {
-      uint32_t b = 0;
-      if (lane == 0) b = wv::atomic_add_u32(cnt, (uint32_t)wv::popc64(m));
-      b = wv::shfl(b, 0);
-      if (in) {
-        core[u] = k;
-        front[b + dev::lanemask_lt_count(m, lane)] = (uint32_t)u;
-      }
-    }
+    if (in) core[u] = k;
+    cp_append(in, (uint32_t)u, front, cnt, lane);
   }
 }
 // adj[b, e) of a frontier vertex of level k, 64 entries per step, one atomic per wave per step on the counter
@@ -287,21 +261,15 @@ PMA_DEV void kc_peel_range(const uint32_t *__restrict__ adj, uint64_t b, uint64_
       if (deg[w] > k) won = wv::atomic_add_u32(&deg[w], 0xFFFFFFFFu) == k + 1u;
       if (won) core[w] = k;
     }
-    const uint64_t m = wv::ballot(won);
-    if (m) {
-      uint32_t q = 0;
-      if (lane == 0) q = wv::atomic_add_u32(cnt, (uint32_t)wv::popc64(m));
-      q = wv::shfl(q, 0);
-      if (won) next[q + dev::lanemask_lt_count(m, lane)] = w;
-    }
+    cp_append(won, w, next, cnt, lane);
   }
 }
 // one sub-round: a wave per frontier vertex; a list beyond kBfsWaveSlots entries is left to k_kc_peel_long (longl, cnt[1])
 PMA_KERNEL void k_kc_peel(const unsigned long long *__restrict__ off, const uint32_t *__restrict__ adj, const uint32_t *__restrict__ front,
                           uint32_t nfront, uint32_t k, uint32_t *deg, uint32_t *core, uint32_t *next, uint32_t *longl, uint32_t *cnt) {
   const int lane = wv::lane();
-  const uint64_t wstride = (uint64_t)wv::grid_dim() * (wv::block_dim() >> 6);
-  for (uint64_t f = (uint64_t)wv::block_idx() * (wv::block_dim() >> 6) + wv::wave_in_block(); f < nfront; f += wstride) {
+  const uint64_t wstride = cp_waves();
+  for (uint64_t f = cp_wave(); f < nfront; f += wstride) {
     const uint32_t u = wv::uni(front[f]);
     const uint64_t b = off[u], e = off[(uint64_t)u + 1];
     if (e - b > kBfsWaveSlots) {
@@ -316,8 +284,8 @@ PMA_KERNEL void k_kc_peel(const unsigned long long *__restrict__ off, const uint
 PMA_KERNEL void k_kc_peel_long(const unsigned long long *__restrict__ off, const uint32_t *__restrict__ adj, const uint32_t *__restrict__ longl,
                                uint32_t nlong, uint32_t k, uint32_t *deg, uint32_t *core, uint32_t *next, uint32_t *cnt) {
   const int lane = wv::lane();
-  const uint64_t waves = (uint64_t)wv::grid_dim() * (wv::block_dim() >> 6);
-  const uint64_t gw = wv::uni((uint64_t)wv::block_idx() * (wv::block_dim() >> 6) + wv::wave_in_block());
+  const uint64_t waves = cp_waves();
+  const uint64_t gw = wv::uni(cp_wave());
   const uint64_t per = waves / nlong ? waves / nlong : 1, groups = waves / per;
   if (gw >= groups * per) return;
   for (uint64_t i = gw / per; i < nlong; i += groups) {

@@ -1,6 +1,6 @@
 // Consumers that intersect two neighbourhoods: triangle counts and common-neighbour counts over the table of gapped arrays
-// (pma_scan.h: ConsumerPart, cp_owner, cp_chunk_owner).  The edge set is the one the BFS kernels walk: live non-sentinel slots
-// of (beginning, end), slot N-1 excluded, local src < n_p, global dests < n.
+// (pma_consumer.h).  The edge set is the one the BFS kernels walk: live non-sentinel slots of (beginning, end), slot N-1
+// excluded, local src < n_p, global dests < n.
 //
 // A vertex's live slots are kept in ascending dest order (the update path's search depends on it), so two neighbourhoods are
 // intersected where they lie: no CSR export, no sort.  The ranges are gapped — a slot is read, found null and skipped — and
@@ -16,7 +16,7 @@
 //                 all waves (or probed, when it is lopsided the other way)
 // The vertex ranges must be sorted and disjoint: the host side refuses the sequential regime (narrow == 0).
 #pragma once
-#include "pma_scan.h"
+#include "pma_consumer.h"
 
 namespace ppcsr {
 
@@ -300,15 +300,6 @@ PMA_DEV void tri_credit(unsigned long long *tri, uint32_t a, uint32_t b, uint32_
     m &= ~wv::ballot(in);
   }
 }
-// the workgroup's triangles into the striped total
-PMA_DEV void tri_total(unsigned long long *total, unsigned long long mine, unsigned long long *red) {
-  if (wv::lane() == 0) red[wv::wave_in_block()] = mine;
-  wv::block_sync();
-  if (wv::thread_idx() == 0) {
-    const unsigned long long all = red[0] + red[1] + red[2] + red[3];
-    if (all) wv::atomic_add_u64(total + (uint64_t)(wv::block_idx() % kBfsStripes) * kTriStripeWords, all);
-  }
-}
 // One 64-slot chunk per wave at a time.  Edges with two short ranges: one per lane, all at once; the others one after the
 // other on the whole wave; those with a range beyond kBfsWaveSlots are left to k_tri_long (their chunk goes on a list).
 // tri may be null (only the total is wanted).  dlist / dcount: the listed chunks (room for every chunk) and their number.
@@ -318,9 +309,9 @@ PMA_KERNEL void k_tri_edges(const ConsumerPart *__restrict__ tab, uint32_t P, ui
   PMA_SHARED unsigned long long red[4];
   const int lane = wv::lane(), w = wv::wave_in_block();
   const uint64_t nchunks = tab[P].chunk0;
-  const uint64_t wstride = (uint64_t)wv::grid_dim() * (wv::block_dim() >> 6);
+  const uint64_t wstride = cp_waves();
   unsigned long long mine = 0;  // (wave-uniform)
-  for (uint64_t ch = wv::uni((uint64_t)wv::block_idx() * (wv::block_dim() >> 6) + (uint64_t)w); ch < nchunks; ch += wstride) {
+  for (uint64_t ch = wv::uni(cp_wave()); ch < nchunks; ch += wstride) {
     const TriItem it = tri_item(tab, P, n, ch, lane);
     if (wv::ballot(it.item) == 0) continue;
     if (wv::ballot(it.lng) != 0 && lane == 0) dlist[wv::atomic_add_u32(dcount, 1u)] = (uint32_t)ch;
@@ -338,7 +329,7 @@ PMA_KERNEL void k_tri_edges(const ConsumerPart *__restrict__ tab, uint32_t P, ui
     if (tri) tri_credit(tri, it.a, it.b, cnt);
     mine += wv::reduce_add(cnt);
   }
-  tri_total(total, mine, red);
+  cp_striped_add<unsigned long long, kTriStripeWords>(total, mine, red);
 }
 // The listed chunks again, a quarter of a chunk (16 slots) per workgroup at a time: every edge with a long range is
 // intersected by the whole workgroup, so a hub's edges spread over the chip and none of them is one wave's work.
@@ -363,7 +354,7 @@ PMA_KERNEL void k_tri_long(const ConsumerPart *__restrict__ tab, uint32_t P, uin
     if (tri) tri_credit(tri, it.a, it.b, cnt);  // (each wave credits its share)
     mine += wv::reduce_add(cnt);
   }
-  tri_total(total, mine, red);
+  cp_striped_add<unsigned long long, kTriStripeWords>(total, mine, red);
 }
 
 // ---- common neighbours -------------------------------------------------------------------------------------------------------

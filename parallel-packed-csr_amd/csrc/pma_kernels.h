@@ -3,6 +3,7 @@
 //   pma_spec_rounds.h  speculative rounds (o_plan / o_check / o_apply / o_big / o_settle): the default scheduler
 //   pma_rebalance.h    whole-array / big-window rebalance, in-place window rebalance, snapshots, maintenance
 //   pma_probe.h        debugging probe of the position chain (ppcsr_debug_chain_probe)
+//   pma_consumer.h     what the consumers share: the table of gapped arrays, the streaming chunk loader, striped counts, list append
 //   pma_scan.h         queries, bulk neighbour scan, bulk build, BFS / PageRank
 //   pma_paths.h        shortest paths over the edge values, weakly connected components
 //   pma_cores.h        core numbers (k-core decomposition): symmetric adjacency export, peeling in sub-rounds
@@ -15,6 +16,7 @@
 #include "pma_spec_rounds.h"
 #include "pma_rebalance.h"
 #include "pma_probe.h"
+#include "pma_consumer.h"
 #include "pma_scan.h"
 #include "pma_paths.h"
 #include "pma_cores.h"

@@ -1,8 +1,8 @@
 // Consumers that use the edge VALUES and the edges as undirected pairs: single-source shortest paths and weakly connected
-// components over the table of gapped arrays (pma_scan.h: ConsumerPart, cp_owner, cp_chunk_owner).  The edge set is the one
-// the BFS kernels walk: live non-sentinel slots of (beginning, end), slot N-1 excluded, local src < n_p, global dests < n.
+// components over the table of gapped arrays (pma_consumer.h).  The edge set is the one the BFS kernels walk: the live edges
+// of cp_load_chunks.
 #pragma once
-#include "pma_scan.h"
+#include "pma_consumer.h"
 
 namespace ppcsr {
 
@@ -30,24 +30,14 @@ PMA_DEV bool sssp_relax_edge(unsigned long long nd, uint32_t dst, uint32_t round
 PMA_KERNEL void k_sssp_relax(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, const uint32_t *front, uint32_t nfront,
                              uint32_t round, unsigned long long *dist, uint32_t *stamp, uint32_t *next, uint32_t *next_count) {
   const int lane = wv::lane();
-  const uint64_t wstride = (uint64_t)wv::grid_dim() * (wv::block_dim() >> 6);
+  const uint64_t wstride = cp_waves();
   const Edge *const items0 = tab[0].items;
   const Node *const nodes0 = tab[0].nodes;
-  for (uint64_t f = (uint64_t)wv::block_idx() * (wv::block_dim() >> 6) + wv::wave_in_block(); f < nfront; f += wstride) {
+  for (uint64_t f = cp_wave(); f < nfront; f += wstride) {
     const uint32_t u = wv::uni(front[f]);
-    const Edge *items = items0;
+    const Edge *items;
     Node nd;
-    if (P == 1) {
-      nd = nodes0[u];
-    } else {
-      const uint32_t k = cp_owner(tab, P, u);
-      items = tab[k].items;
-      nd = tab[k].nodes[u - tab[k].first];
-    }
-    if ((uint64_t)nd.end - (uint64_t)nd.beginning > kBfsWaveSlots) {  // a hub: leave it to one streaming pass (k_sssp_edges)
-      if (lane == 0) next_count[1] = 1u;
-      continue;
-    }
+    if (!cp_frontier_vertex(tab, P, items0, nodes0, u, lane, &next_count[1], items, nd)) continue;  // (k_sssp_edges)
     const unsigned long long du = dist[u];
     for (uint64_t base = (uint64_t)nd.beginning + 1; base < (uint64_t)nd.end; base += 64) {
       const uint64_t s = base + (uint64_t)lane;
@@ -58,13 +48,7 @@ PMA_KERNEL void k_sssp_relax(const ConsumerPart *__restrict__ tab, uint32_t P, u
       }
       bool won = false;
       if (val != 0 && dst < n && du + val < dist[dst]) won = sssp_relax_edge(du + val, dst, round, dist, stamp);
-      const uint64_t m = wv::ballot(won);
-      if (m) {
-        uint32_t b = 0;
-        if (lane == 0) b = wv::atomic_add_u32(next_count, (uint32_t)wv::popc64(m));
-        b = wv::shfl(b, 0);
-        if (won) next[b + dev::lanemask_lt_count(m, lane)] = dst;
-      }
+      cp_append(won, dst, next, next_count, lane);
     }
   }
 }
@@ -74,62 +58,34 @@ PMA_KERNEL void k_sssp_relax(const ConsumerPart *__restrict__ tab, uint32_t P, u
 // this pass made active for the next round — exactly, since the stamp admits each vertex once.
 PMA_KERNEL void k_sssp_edges(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, uint32_t round,
                              const uint32_t *__restrict__ active_bits, unsigned long long *dist, uint32_t *stamp, uint32_t *found) {
+  PMA_SHARED uint32_t red[4];
   const int lane = wv::lane();
   const uint64_t nchunks = tab[P].chunk0;
-  const uint64_t wstride = (uint64_t)wv::grid_dim() * (wv::block_dim() >> 6);
-  const Edge *const items0 = tab[0].items;  // (one array: no search, no table look-up inside the loop)
+  const uint64_t wstride = cp_waves();
+  const Edge *const items0 = tab[0].items;
   const uint64_t N0 = tab[0].N;
   const uint32_t n0 = tab[0].n;
   uint32_t mine = 0;
   constexpr int kB = 4;
-  for (uint64_t ch0 = wv::uni(((uint64_t)wv::block_idx() * (wv::block_dim() >> 6) + wv::wave_in_block()) * kB); ch0 < nchunks;
-       ch0 += wstride * kB) {
+  for (uint64_t ch0 = wv::uni(cp_wave() * kB); ch0 < nchunks; ch0 += wstride * kB) {
     Edge e[kB];
-    uint32_t first[kB], pn[kB];
-#pragma unroll
-    for (int b = 0; b < kB; b++) {
-      const Edge *items = items0;
-      uint64_t s = (ch0 + b) * 64 + (uint64_t)lane, N = N0;
-      first[b] = 0;
-      pn[b] = n0;
-      if (P > 1 && ch0 + b < nchunks) {
-        const uint32_t k = cp_chunk_owner(tab, P, ch0 + b);
-        items = tab[k].items;
-        s -= tab[k].chunk0 * 64;
-        N = tab[k].N;
-        first[b] = tab[k].first;
-        pn[b] = tab[k].n;
-      }
-      e[b] = null_edge();
-      if (ch0 + b < nchunks && s + 1 < N) e[b] = items[s];  // (slot N-1 is never part of a neighbourhood)
-    }
-    // phases over all kB chunks, so that the kB gathers of a phase are in flight together
+    uint32_t src[kB];
     bool hit[kB];
+    cp_load_chunks<kB>(tab, P, n, items0, N0, n0, ch0, nchunks, lane, e, src, hit);
+    // phases over all kB chunks, so that the kB gathers of a phase are in flight together (k_bfs_edges_bits)
     unsigned long long nd[kB], dd[kB];
 #pragma unroll
-    for (int b = 0; b < kB; b++) {
-      const bool live = e[b].value != 0 && !is_sentinel(e[b]) && e[b].src < pn[b] && e[b].dest < n;
-      const uint32_t src = e[b].src + first[b];
-      hit[b] = live && ((active_bits[src >> 5] >> (src & 31u)) & 1u);
-      first[b] = src;
-    }
+    for (int b = 0; b < kB; b++) hit[b] = hit[b] && ((active_bits[src[b] >> 5] >> (src[b] & 31u)) & 1u);
 #pragma unroll
     for (int b = 0; b < kB; b++) {
-      nd[b] = hit[b] ? dist[first[b]] + e[b].value : kNoPath;
+      nd[b] = hit[b] ? dist[src[b]] + e[b].value : kNoPath;
       dd[b] = hit[b] ? dist[e[b].dest] : 0ull;
     }
 #pragma unroll
     for (int b = 0; b < kB; b++)
       if (nd[b] < dd[b] && sssp_relax_edge(nd[b], e[b].dest, round, dist, stamp)) mine++;
   }
-  PMA_SHARED uint32_t red[4];
-  mine = wv::reduce_add(mine);
-  if (lane == 0) red[wv::wave_in_block()] = mine;
-  wv::block_sync();
-  if (wv::thread_idx() == 0) {
-    const uint32_t all = red[0] + red[1] + red[2] + red[3];
-    if (all) wv::atomic_add_u32(found + (uint64_t)(wv::block_idx() % kBfsStripes) * kBfsStripeWords, all);
-  }
+  cp_striped_add<uint32_t, kBfsStripeWords>(found, wv::reduce_add(mine), red);
 }
 
 // ---- weakly connected components: min-label propagation with pointer jumping ---------------------------------------------
@@ -145,46 +101,26 @@ PMA_KERNEL void k_cc_init(uint32_t *labels, uint32_t n) {
 // finishes in few rounds).  Loads may be stale (too large): the atomic min decides.  `found` counts the edges that differed.
 constexpr int kCcRunLanes = 8;  // lanes of a wave on one source from which its run is reduced before the atomic
 PMA_KERNEL void k_cc_hook(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, uint32_t *labels, uint32_t *found) {
+  PMA_SHARED uint32_t red[4];
   const int lane = wv::lane();
   const uint64_t nchunks = tab[P].chunk0;
-  const uint64_t wstride = (uint64_t)wv::grid_dim() * (wv::block_dim() >> 6);
+  const uint64_t wstride = cp_waves();
   const Edge *const items0 = tab[0].items;
   const uint64_t N0 = tab[0].N;
   const uint32_t n0 = tab[0].n;
   uint32_t mine = 0;
   constexpr int kB = 4;
-  for (uint64_t ch0 = wv::uni(((uint64_t)wv::block_idx() * (wv::block_dim() >> 6) + wv::wave_in_block()) * kB); ch0 < nchunks;
-       ch0 += wstride * kB) {
+  for (uint64_t ch0 = wv::uni(cp_wave() * kB); ch0 < nchunks; ch0 += wstride * kB) {
     Edge e[kB];
-    uint32_t first[kB], pn[kB];
-#pragma unroll
-    for (int b = 0; b < kB; b++) {
-      const Edge *items = items0;
-      uint64_t s = (ch0 + b) * 64 + (uint64_t)lane, N = N0;
-      first[b] = 0;
-      pn[b] = n0;
-      if (P > 1 && ch0 + b < nchunks) {
-        const uint32_t k = cp_chunk_owner(tab, P, ch0 + b);
-        items = tab[k].items;
-        s -= tab[k].chunk0 * 64;
-        N = tab[k].N;
-        first[b] = tab[k].first;
-        pn[b] = tab[k].n;
-      }
-      e[b] = null_edge();
-      if (ch0 + b < nchunks && s + 1 < N) e[b] = items[s];  // (slot N-1 is never part of a neighbourhood)
-    }
+    uint32_t src[kB];
     bool live[kB];
+    cp_load_chunks<kB>(tab, P, n, items0, N0, n0, ch0, nchunks, lane, e, src, live);
     uint32_t lu[kB], lv[kB];
 #pragma unroll
-    for (int b = 0; b < kB; b++) {
-      live[b] = e[b].value != 0 && !is_sentinel(e[b]) && e[b].src < pn[b] && e[b].dest < n;
-      first[b] += e[b].src;  // global source
-      live[b] = live[b] && first[b] != e[b].dest;
-    }
+    for (int b = 0; b < kB; b++) live[b] = live[b] && src[b] != e[b].dest;
 #pragma unroll
     for (int b = 0; b < kB; b++) {
-      lu[b] = live[b] ? labels[first[b]] : 0u;
+      lu[b] = live[b] ? labels[src[b]] : 0u;
       lv[b] = live[b] ? labels[e[b].dest] : 0u;
     }
 #pragma unroll
@@ -192,13 +128,13 @@ PMA_KERNEL void k_cc_hook(const ConsumerPart *__restrict__ tab, uint32_t P, uint
       const bool diff = lu[b] != lv[b];
       uint32_t lo = lu[b] < lv[b] ? lu[b] : lv[b];
       const uint32_t hi = lu[b] < lv[b] ? lv[b] : lu[b];
-      const uint32_t x = lu[b] < lv[b] ? e[b].dest : first[b];
+      const uint32_t x = lu[b] < lv[b] ? e[b].dest : src[b];
       // Lanes that lower THEIR SOURCE share the target with their neighbours (a vertex's slots are contiguous): 64 atomics on
       // one word are served one after the other, and a hub's run fills whole waves.  The runs at the two ends of the wave's
       // pending lanes — a run that fills the wave is both — are reduced to their smallest label and one lane issues it
       // (the others' edges still count as differing; whatever they would have stored is not below that minimum).
       bool issue = diff;
-      const bool own = diff && x == first[b];
+      const bool own = diff && x == src[b];
       const uint64_t pend = wv::ballot(own);
       if (pend) {
         const int ends[2] = {wv::ctz64(pend), 63 - wv::clz64(pend)};
@@ -225,14 +161,7 @@ PMA_KERNEL void k_cc_hook(const ConsumerPart *__restrict__ tab, uint32_t P, uint
       if (diff) mine++;
     }
   }
-  PMA_SHARED uint32_t red[4];
-  mine = wv::reduce_add(mine);
-  if (lane == 0) red[wv::wave_in_block()] = mine;
-  wv::block_sync();
-  if (wv::thread_idx() == 0) {
-    const uint32_t all = red[0] + red[1] + red[2] + red[3];
-    if (all) wv::atomic_add_u32(found + (uint64_t)(wv::block_idx() % kBfsStripes) * kBfsStripeWords, all);
-  }
+  cp_striped_add<uint32_t, kBfsStripeWords>(found, wv::reduce_add(mine), red);
 }
 // labels[v] = the end of v's label chain.  labels[x] <= x, so a chain falls strictly until it meets a fixed point; only
 // thread v stores to labels[v], and what it stores is not above what it read there.

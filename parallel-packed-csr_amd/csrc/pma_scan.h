@@ -2,6 +2,7 @@
 // non-parity bulk build, BFS and PageRank over the gapped array (src/utility/bfs.h, pagerank.h).
 #pragma once
 #include "pma_rebalance.h"
+#include "pma_consumer.h"
 
 namespace ppcsr {
 
@@ -272,64 +273,20 @@ PMA_KERNEL void k_bb_edges(View v, const unsigned long long *keys, const uint32_
 }
 
 // ---- graph-algorithm consumers over the gapped array (reference: src/utility/bfs.h, src/utility/pagerank.h) -----------
-// The consumers run over a TABLE of gapped arrays: the partitions of a PPPCSR (vertex ranges [first, first + n), edges stored
-// with a partition-local src and a global dest), or one engine as a one-entry table.  Vertex ids in levels[], the frontier
-// lists and bitmaps are global.  The table has P + 1 entries: entry P only closes the two searchable columns (first = the
-// vertex count of the whole graph, chunk0 = the number of 64-slot chunks of all arrays).
-struct ConsumerPart {
-  const Edge *items;
-  const Node *nodes;
-  uint64_t N;       // slots
-  uint64_t chunk0;  // 64-slot chunks of the arrays before this one
-  uint32_t n;       // vertices
-  uint32_t first;   // global id of vertex 0
-  uint32_t pad[2];
-};
-static_assert(sizeof(ConsumerPart) == 48, "consumer table entry");
-// owner of global vertex u (wave-uniform): the last entry whose first vertex is <= u — an empty partition shares its first
-// vertex with the next one, which is the owner (the rule of PPPCSR.cpp:58-66)
-PMA_DEV uint32_t cp_owner(const ConsumerPart *tab, uint32_t P, uint32_t u) {
-  uint32_t lo = 0, hi = P - 1;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) >> 1;
-    if (tab[mid].first <= u) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-// array that holds chunk ch of the concatenated chunk space (wave-uniform)
-PMA_DEV uint32_t cp_chunk_owner(const ConsumerPart *tab, uint32_t P, uint64_t ch) {
-  uint32_t lo = 0, hi = P - 1;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) >> 1;
-    if (tab[mid].chunk0 <= ch) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
+// They run over the table of gapped arrays of pma_consumer.h (ConsumerPart), with global vertex ids.
 // BFS, one level per launch: one wave per frontier vertex finds the vertex's array, walks its slot range (beginning, end) 64
 // slots at a time, skips nulls, claims unvisited neighbours with a compare-and-swap on their level and appends them to the next
 // frontier (one atomic per wave per 64 slots).  Levels are unique, so the result equals the reference's queue-based walk exactly.
-constexpr uint64_t kBfsWaveSlots = 4096;  // longest slot range one wave walks on its own
 PMA_KERNEL void k_bfs_level(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, const uint32_t *front, uint32_t nfront,
                             uint32_t level, uint32_t *levels, uint32_t *next, uint32_t *next_count) {
   const int lane = wv::lane();
-  const uint64_t wstride = (uint64_t)wv::grid_dim() * (wv::block_dim() >> 6);
-  const Edge *const items0 = tab[0].items;  // (one array: no search, no table look-up inside the loop)
+  const uint64_t wstride = cp_waves();
+  const Edge *const items0 = tab[0].items;
   const Node *const nodes0 = tab[0].nodes;
-  for (uint64_t f = (uint64_t)wv::block_idx() * (wv::block_dim() >> 6) + wv::wave_in_block(); f < nfront; f += wstride) {
-    const uint32_t u = wv::uni(front[f]);
-    const Edge *items = items0;
+  for (uint64_t f = cp_wave(); f < nfront; f += wstride) {
+    const Edge *items;
     Node nd;
-    if (P == 1) {
-      nd = nodes0[u];
-    } else {
-      const uint32_t k = cp_owner(tab, P, u);
-      items = tab[k].items;
-      nd = tab[k].nodes[u - tab[k].first];
-    }
-    if ((uint64_t)nd.end - (uint64_t)nd.beginning > kBfsWaveSlots) {  // a hub: leave it to one streaming pass (k_bfs_edges_bits)
-      if (lane == 0) next_count[1] = 1u;
-      continue;
-    }
+    if (!cp_frontier_vertex(tab, P, items0, nodes0, wv::uni(front[f]), lane, &next_count[1], items, nd)) continue;  // (k_bfs_edges_bits)
     for (uint64_t base = (uint64_t)nd.beginning + 1; base < (uint64_t)nd.end; base += 64) {
       const uint64_t s = base + (uint64_t)lane;
       uint32_t val = 0, dst = 0;
@@ -339,46 +296,13 @@ PMA_KERNEL void k_bfs_level(const ConsumerPart *__restrict__ tab, uint32_t P, ui
       }
       bool won = false;
       if (val != 0 && dst < n && levels[dst] == kMax) won = wv::atomic_cas_u32(&levels[dst], kMax, level + 1u) == kMax;
-      const uint64_t m = wv::ballot(won);
-      if (m) {
-        uint32_t b = 0;
-        if (lane == 0) b = wv::atomic_add_u32(next_count, (uint32_t)wv::popc64(m));
-        b = wv::shfl(b, 0);
-        if (won) next[b + dev::lanemask_lt_count(m, lane)] = dst;
-      }
+      cp_append(won, dst, next, next_count, lane);
     }
   }
 }
-// BFS level for a LARGE frontier: one streaming pass over the gapped array instead of one wave per frontier vertex (whose
-// hubs would serialise the level): every live edge whose source sits on the current level claims its destination.  All
-// writers of a level store the same value, so plain stores suffice; `found` counts the claims (an upper bound is enough:
-// it only steers the choice of the next level's kernel, and zero means "done").
-PMA_KERNEL void k_bfs_edges(View v, uint32_t level, uint32_t *levels, uint32_t *found) {
-  const int lane = wv::lane();
-  const uint64_t N = v.g.N, nchunks = (N + 63) / 64;
-  const uint64_t wstride = (uint64_t)wv::grid_dim() * (wv::block_dim() >> 6);
-  uint32_t mine = 0;
-  for (uint64_t ch = (uint64_t)wv::block_idx() * (wv::block_dim() >> 6) + wv::wave_in_block(); ch < nchunks; ch += wstride) {
-    const uint64_t s = ch * 64 + (uint64_t)lane;
-    Edge e = null_edge();
-    if (s + 1 < N) e = v.items[s];  // (slot N-1 is never part of a neighbourhood)
-    const bool live = e.value != 0 && !is_sentinel(e) && e.src < v.g.n && e.dest < v.g.n;
-    if (live && levels[e.src] == level && levels[e.dest] == kMax) {
-      levels[e.dest] = level + 1u;
-      mine++;
-    }
-  }
-  mine = wv::reduce_add(mine);
-  if (lane == 0 && mine) wv::atomic_add_u32(found, mine);
-}
-// The streaming level, bitmap form.  The level's two per-edge tests — "is the source on the frontier", "is the destination
-// still unvisited" — used to be two gathers from levels[] (4 MB at n = 1 M: 64-B lines fetched for 4 B, and the pass ran
-// at 0.7-1.3 TB/s).  k_bfs_bits packs both answers into two bitmaps of n/8 bytes (128 KB: L2-resident on every XCD) with
-// one coalesced sweep over levels[] per level; k_bfs_edges_bits then streams the array with four 64-slot chunks in flight
-// per wave and touches levels[] only for edges into vertices that were unvisited when the level began.  Measured on an
-// RMAT-20 / 10 M-edge graph (201 MB of slots): 35-38 us on light levels (5.5 TB/s), 63 / 40 us on the two heavy ones.
-// (Claiming destinations with atomic ORs into the visited bitmap instead — exact `found`, one store per vertex — cost
-// 195 / 100 us: 0.4 M atomics on 1024 cache lines are served by the memory side one line at a time.)
+// The streaming level's two per-edge tests — "is the source on the frontier", "is the destination still unvisited" — as two
+// bitmaps of n/8 bytes (128 KB at n = 1 M: L2-resident on every XCD), built with one coalesced sweep over levels[] per level.
+// As two gathers from levels[] (4 MB at n = 1 M: 64-B lines fetched for 4 B) the pass ran at 0.7-1.3 TB/s.
 PMA_KERNEL void k_bfs_bits(const uint32_t *levels, uint32_t n, uint32_t level, uint32_t *front_bits, uint32_t *visited_bits) {
   const int lane = wv::lane();
   const uint64_t stride = (uint64_t)wv::grid_dim() * wv::block_dim();
@@ -392,50 +316,37 @@ PMA_KERNEL void k_bfs_bits(const uint32_t *levels, uint32_t n, uint32_t level, u
     }
   }
 }
-// (The chunk space is the concatenation of the table's arrays: each chunk finds its array by a wave-uniform search of the chunk
-// prefix — with one array, a search of no steps — and its edges get global sources, src + first.)
-constexpr uint32_t kBfsStripes = 64, kBfsStripeWords = 32;
+// BFS level for a LARGE frontier: one streaming pass over the gapped arrays instead of one wave per frontier vertex (whose
+// hubs would serialise the level): every live edge whose source sits on the current level claims its destination.  All
+// writers of a level store the same value, so plain stores suffice; `found` counts the claims (an upper bound is enough:
+// it only steers the choice of the next level's kernel, and zero means "done").  Four 64-slot chunks are in flight per
+// wave (cp_load_chunks), and levels[] is touched only for edges into vertices that were unvisited when the level began.
+// Measured on an RMAT-20 / 10 M-edge graph (201 MB of slots): 35-38 us on light levels (5.5 TB/s), 63 / 40 us on the two
+// heavy ones.  (Claiming destinations with atomic ORs into the visited bitmap instead — exact `found`, one store per
+// vertex — cost 195 / 100 us: 0.4 M atomics on 1024 cache lines are served by the memory side one line at a time.)
 PMA_KERNEL void k_bfs_edges_bits(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, uint32_t level,
                                  const uint32_t *__restrict__ front_bits, const uint32_t *__restrict__ visited_bits, uint32_t *levels,
                                  uint32_t *found) {
+  PMA_SHARED uint32_t red[4];
   const int lane = wv::lane();
   const uint64_t nchunks = tab[P].chunk0;
-  const uint64_t wstride = (uint64_t)wv::grid_dim() * (wv::block_dim() >> 6);
-  const Edge *const items0 = tab[0].items;  // (one array: no search, no table look-up inside the loop)
+  const uint64_t wstride = cp_waves();
+  const Edge *const items0 = tab[0].items;
   const uint64_t N0 = tab[0].N;
   const uint32_t n0 = tab[0].n;
   uint32_t mine = 0;
   constexpr int kB = 4;
-  for (uint64_t ch0 = wv::uni(((uint64_t)wv::block_idx() * (wv::block_dim() >> 6) + wv::wave_in_block()) * kB); ch0 < nchunks;
-       ch0 += wstride * kB) {
+  for (uint64_t ch0 = wv::uni(cp_wave() * kB); ch0 < nchunks; ch0 += wstride * kB) {
     Edge e[kB];
-    uint32_t first[kB], pn[kB];
-#pragma unroll
-    for (int b = 0; b < kB; b++) {
-      const Edge *items = items0;
-      uint64_t s = (ch0 + b) * 64 + (uint64_t)lane, N = N0;
-      first[b] = 0;
-      pn[b] = n0;
-      if (P > 1 && ch0 + b < nchunks) {
-        const uint32_t k = cp_chunk_owner(tab, P, ch0 + b);
-        items = tab[k].items;
-        s -= tab[k].chunk0 * 64;
-        N = tab[k].N;
-        first[b] = tab[k].first;
-        pn[b] = tab[k].n;
-      }
-      e[b] = null_edge();
-      if (ch0 + b < nchunks && s + 1 < N) e[b] = items[s];  // (slot N-1 is never part of a neighbourhood)
-    }
+    uint32_t src[kB];
+    bool hit[kB];
+    cp_load_chunks<kB>(tab, P, n, items0, N0, n0, ch0, nchunks, lane, e, src, hit);
     // Four phases, each over all kB chunks, so that the kB gathers of a phase are in flight TOGETHER (written one chunk after
     // the other, the levels[] load of chunk b+1 waits for the store of chunk b: they may alias).
-    bool hit[kB];
     uint32_t bit[kB], old[kB];
 #pragma unroll
     for (int b = 0; b < kB; b++) {
-      const bool live = e[b].value != 0 && !is_sentinel(e[b]) && e[b].src < pn[b] && e[b].dest < n;
-      const uint32_t src = e[b].src + first[b];
-      hit[b] = live && ((front_bits[src >> 5] >> (src & 31u)) & 1u);
+      hit[b] = hit[b] && ((front_bits[src[b] >> 5] >> (src[b] & 31u)) & 1u);
       bit[b] = 1u << (e[b].dest & 31u);
     }
 #pragma unroll
@@ -455,17 +366,7 @@ PMA_KERNEL void k_bfs_edges_bits(const ConsumerPart *__restrict__ tab, uint32_t 
       }
     }
   }
-  // (`found` is kBfsStripes counters on cache lines of their own, one add per workgroup: on a heavy level nearly every wave
-  // has claims, and 32 K adds to ONE word are served one after the other by the memory side — that was 260-290 us of the
-  // 320 / 290 us the heavy levels took, whatever the per-edge work looked like)
-  PMA_SHARED uint32_t red[4];
-  mine = wv::reduce_add(mine);
-  if (lane == 0) red[wv::wave_in_block()] = mine;
-  wv::block_sync();
-  if (wv::thread_idx() == 0) {
-    const uint32_t all = red[0] + red[1] + red[2] + red[3];
-    if (all) wv::atomic_add_u32(found + (uint64_t)(wv::block_idx() % kBfsStripes) * kBfsStripeWords, all);
-  }
+  cp_striped_add<uint32_t, kBfsStripeWords>(found, wv::reduce_add(mine), red);
 }
 // frontier list of one level (used when a small frontier follows an edge-centric level)
 PMA_KERNEL void k_bfs_collect(const uint32_t *levels, uint32_t n, uint32_t level, uint32_t *front, uint32_t *count) {
@@ -473,14 +374,7 @@ PMA_KERNEL void k_bfs_collect(const uint32_t *levels, uint32_t n, uint32_t level
   const uint64_t stride = (uint64_t)wv::grid_dim() * wv::block_dim();
   for (uint64_t base = (uint64_t)wv::block_idx() * wv::block_dim() + (wv::thread_idx() & ~63u); base < n; base += stride) {
     const uint64_t u = base + (uint64_t)lane;
-    const bool in = u < n && levels[u] == level;
-    const uint64_t m = wv::ballot(in);
-    if (m) {
-      uint32_t b = 0;
-      if (lane == 0) b = wv::atomic_add_u32(count, (uint32_t)wv::popc64(m));
-      b = wv::shfl(b, 0);
-      if (in) front[b + dev::lanemask_lt_count(m, lane)] = (uint32_t)u;
-    }
+    cp_append(u < n && levels[u] == level, (uint32_t)u, front, count, lane);
   }
 }
 // PageRank push, last step: contributions sorted (stably) by destination; every destination's run is added IN ORDER —

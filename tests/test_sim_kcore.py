@@ -6,13 +6,15 @@ import ctypes
 import numpy as np
 import pytest
 
-from consumers_model import global_edges, last_slot_free, partition_states
+from consumers_model import global_edges, last_slot_free, model_bfs, partition_states
 from helpers import load_pkg
 from kcore_model import assert_hard, hardness, model_kcore
+from paths_model import global_edges_valued, model_components, model_sssp
 from test_sim_engine import SIM_SO, build_sim
 from test_sim_pppcsr_consumers import make, mixed_stream, tune
+from triangles_model import model_common_neighbours, model_triangles
 
-EINVAL, EHIP, EUNSUPPORTED = 1, 3, 4
+EINVAL, ENOMEM, EHIP, EUNSUPPORTED = 1, 2, 3, 4
 
 
 @pytest.fixture(scope="module")
@@ -254,39 +256,127 @@ def test_sim_kcore_errors(lib, streams):
     pp.close()
 
 
+def alloc_failures(lib, streams, P, prepare, min_allocs):
+    """Every device allocation of one consumer call fails in turn.  prepare(pp, states) -> (call, expect, verify): call(k) is
+    the C call whose k-th allocation fails (k = 0: none does) and returns its status, expect(k) is the status that failure
+    must give, verify(k) runs the next call and compares it with the model.  After each failure the partition states are
+    unchanged."""
+    n = 400
+    counter = ctypes.c_int.in_dll(lib, "g_sim_fail_alloc")
+    pp = make(lib, n, P)
+    s, d = streams.rmat_edges_folded(n, 9, 3000, seed=8)
+    pp.apply(streams.adds(s, d))
+    states = partition_states(pp)
+    call, expect, verify = prepare(pp, states)
+    counter.value = 1 << 30
+    assert call(0) == 0
+    allocs = (1 << 30) - counter.value
+    lib.ppcsr_sim_fail_alloc_after(0)
+    assert allocs >= min_allocs, allocs
+    for k in range(1, allocs + 1):
+        lib.ppcsr_sim_fail_alloc_after(k)
+        try:
+            rc = call(k)
+        finally:
+            lib.ppcsr_sim_fail_alloc_after(0)
+        assert rc == expect(k), (k, rc)
+        for (f0, i0, n0), (f1, i1, n1) in zip(states, partition_states(pp)):
+            np.testing.assert_array_equal(i0, i1)
+            np.testing.assert_array_equal(n0, n1)
+        verify(k)
+    pp.close()
+
+
 def test_sim_kcore_allocation_failures(lib, streams):
     """every device allocation of the call fails in turn: the allocation status comes back, the state is unchanged, and the
     next call succeeds and equals the model"""
-    n = 400
-    counter = ctypes.c_int.in_dll(lib, "g_sim_fail_alloc")
-    for P in (1, 3):
-        pp = make(lib, n, P)
-        s, d = streams.rmat_edges_folded(n, 9, 3000, seed=8)
-        pp.apply(streams.adds(s, d))
-        states = partition_states(pp)
-        src, dst = global_edges(states)
-        want = model_kcore(src, dst, n)
+    def prepare(pp, states):
+        n = pp.get_n()
+        want = model_kcore(*global_edges(states), n)
         core = np.empty(n, np.uint32)
         kmax = ctypes.c_uint32()
-        counter.value = 1 << 30
-        assert pp.L.pppcsr_kcore(pp.h, core.ctypes.data, ctypes.byref(kmax), None) == 0
-        allocs = (1 << 30) - counter.value
-        lib.ppcsr_sim_fail_alloc_after(0)
-        assert allocs >= 8, allocs  # the table, degrees, cores, offsets, cursors, frontiers, counters, the adjacency
-        for k in range(1, allocs + 1):
-            lib.ppcsr_sim_fail_alloc_after(k)
-            try:
-                rc = pp.L.pppcsr_kcore(pp.h, core.ctypes.data, ctypes.byref(kmax), None)
-            finally:
-                lib.ppcsr_sim_fail_alloc_after(0)
-            assert rc == EHIP, (k, rc)  # (what a failed allocation of bfs / sssp / components returns)
-            for (f0, i0, n0), (f1, i1, n1) in zip(states, partition_states(pp)):
-                np.testing.assert_array_equal(i0, i1)
-                np.testing.assert_array_equal(n0, n1)
+
+        def verify(k):
             got, top = pp.kcore()
             np.testing.assert_array_equal(got, want)
             assert top == want.max()
-        pp.close()
+        # (EHIP: what a failed allocation of bfs / sssp / components returns)
+        return lambda k: pp.L.pppcsr_kcore(pp.h, core.ctypes.data, ctypes.byref(kmax), None), lambda k: EHIP, verify
+    for P in (1, 3):
+        # the table, degrees, cores, offsets, cursors, frontiers, counters, the adjacency
+        alloc_failures(lib, streams, P, prepare, 8)
+
+
+def _prepare_bfs(pp, states):
+    n, start = pp.get_n(), 3
+    want, _ = model_bfs(*global_edges(states), n, start)
+    out = np.empty(n, np.uint32)
+    return (lambda k: pp.L.pppcsr_bfs(pp.h, start, out.ctypes.data, None), lambda k: EHIP,
+            lambda k: np.testing.assert_array_equal(pp.bfs(start), want))
+
+
+def _prepare_sssp(pp, states):
+    n, start = pp.get_n(), 3
+    want = model_sssp(*global_edges_valued(states), n, start)
+    out = np.empty(n, np.uint64)
+    return (lambda k: pp.L.pppcsr_sssp(pp.h, start, out.ctypes.data, None), lambda k: EHIP,
+            lambda k: np.testing.assert_array_equal(pp.sssp(start), want))
+
+
+def _prepare_components(pp, states):
+    n = pp.get_n()
+    want = model_components(*global_edges(states), n)
+    out = np.empty(n, np.uint32)
+    return (lambda k: pp.L.pppcsr_components(pp.h, out.ctypes.data, None), lambda k: EHIP,
+            lambda k: np.testing.assert_array_equal(pp.components(), want))
+
+
+def _prepare_triangles(pp, states):
+    n = pp.get_n()
+    want, total = model_triangles(*global_edges(states), n)
+    tri = np.empty(n, np.uint64)
+    tot = ctypes.c_uint64()
+
+    def verify(k):
+        got, t = pp.triangles()
+        np.testing.assert_array_equal(got, want)
+        assert t == total
+    return lambda k: pp.L.pppcsr_triangles(pp.h, tri.ctypes.data, ctypes.byref(tot), None), lambda k: EHIP, verify
+
+
+def _prepare_common_neighbours(pp, states):
+    """the host form stages the pairs in three buffers that grow with the batch and are kept: every call brings a longer batch
+    than any before it, so that each call allocates the table and the three of them"""
+    n = pp.get_n()
+    src, dst = global_edges(states)
+    rng = np.random.default_rng(5)
+
+    def pairs(m):
+        return rng.integers(0, n + 20, m).astype(np.uint32), rng.integers(0, n + 20, m).astype(np.uint32)
+
+    def call(k):
+        a, b = pairs(128 * (k + 1))
+        out = np.empty(len(a), np.uint32)
+        return pp.L.pppcsr_common_neighbours(pp.h, a.ctypes.data, b.ctypes.data, len(a), out.ctypes.data, None)
+
+    def verify(k):
+        a, b = pairs(128 * (k + 1) + 64)
+        np.testing.assert_array_equal(pp.common_neighbours(a, b), model_common_neighbours(src, dst, n, a, b))
+    # the table is a device allocation of the call (EHIP); the staging buffers report out of memory (ENOMEM)
+    return call, lambda k: EHIP if k == 1 else ENOMEM, verify
+
+
+@pytest.mark.parametrize("P", [1, 3])
+@pytest.mark.parametrize("prepare,min_allocs", [(_prepare_bfs, 7), (_prepare_sssp, 8), (_prepare_components, 3), (_prepare_triangles, 5),
+                                                (_prepare_common_neighbours, 4)],
+                         ids=["bfs", "sssp", "components", "triangles", "common_neighbours"])
+def test_sim_consumer_allocation_failures(lib, streams, prepare, min_allocs, P):
+    """the allocation path of every consumer that takes its buffers from the device per call, as
+    test_sim_kcore_allocation_failures: each allocation fails in turn, the status is the allocation's, nothing is written,
+    and the next call equals the model.  (pagerank is not among them: its first call allocates scratch that the partitions keep, so
+    later calls make fewer allocations than the counted one and this helper fails on it — before the consumers shared one
+    allocation path just as after.)"""
+    alloc_failures(lib, streams, P, prepare, min_allocs)
 
 
 def test_kcore_model_against_networkx(lib, streams):
