@@ -191,13 +191,22 @@ int ppcsr_stats(ppcsr_t h, ppcsr_stats_t *out);
  *   reads      test hooks that move the seams of the batched reads (defaults = the shipped sizes; values in [1, 2^32]):
  *              "query_lookup_stage" (host lookups — and host common-neighbour pairs — per H2D / D2H round trip; 2^22), "query_gather_rows" (queried vertices
  *              per gather block; 2^20), "query_gather_chunks" (64-slot chunks per gather block; 2^22), "query_gather_stage"
- *              (edges per D2H window of a host gather; 2^22) */
+ *              (edges per D2H window of a host gather; 2^22)
+ *   snapshots  test hooks: "snap_grid" (cap on the workgroups of the two kernels that synchronise a snapshot incrementally, in
+ *              [1, 4096]; default 4096 — a small value moves their grid-stride seam down to arrays of a few thousand slots),
+ *              "snap_count" (1: count what every incremental synchronisation copies, see ppcsr_debug_snap_counters; default 0) */
 int ppcsr_set_option(ppcsr_t h, const char *key, int64_t value);
 /* device-side copy of the whole state and return to it (used by the benchmark to replay a batch on the same
  * core graph, and by the engine itself as the rollback point of speculative rounds); no reference equivalent.
  * After the first copy both directions are incremental: only leaves / node records written since (dirty tags) move */
 int ppcsr_snapshot(ppcsr_t h);
 int ppcsr_restore(ppcsr_t h);
+/* Debugging: which way the snapshot machinery went.  out[0..3]: full saves, full loads, incremental commits, incremental
+ * rollbacks since creation, counted over BOTH snapshots (the user's and the speculative epochs' rollback point), host-side and
+ * always on.  out[4], out[5]: leaves / node records copied by the last incremental synchronisation of either snapshot — collected
+ * only while option "snap_count" is 1 (0 until then; the option adds a stream synchronisation to every incremental
+ * synchronisation, so it is for tests).  EINVAL: null handle or out. */
+int ppcsr_debug_snap_counters(ppcsr_t h, uint64_t out[6]);
 /* debugging / measurement helpers */
 int ppcsr_check_invariants(ppcsr_t h, uint64_t *bad_leaves);
 int ppcsr_bench_scan_all(ppcsr_t h, double *ms, uint64_t *total);

@@ -59,7 +59,7 @@ EXPORTED = [
     "ppcsr_create", "ppcsr_destroy", "ppcsr_add_edge", "ppcsr_remove_edge", "ppcsr_add_node", "ppcsr_apply_batch",
     "ppcsr_apply_batch_device", "ppcsr_edge_exists", "ppcsr_get_n", "ppcsr_get_node", "ppcsr_geometry",
     "ppcsr_get_neighbourhood", "ppcsr_read_neighbourhood", "ppcsr_scan_all", "ppcsr_bulk_build", "ppcsr_bfs", "ppcsr_pagerank", "ppcsr_export_state", "ppcsr_stats",
-    "ppcsr_set_option", "ppcsr_snapshot", "ppcsr_restore", "ppcsr_check_invariants", "ppcsr_bench_scan_all", "ppcsr_bench_rebalance", "ppcsr_bench_resize", "ppcsr_strerror",
+    "ppcsr_set_option", "ppcsr_snapshot", "ppcsr_restore", "ppcsr_debug_snap_counters", "ppcsr_check_invariants", "ppcsr_bench_scan_all", "ppcsr_bench_rebalance", "ppcsr_bench_resize", "ppcsr_strerror",
     "ppcsr_last_error", "ppcsr_device_count", "pppcsr_create", "pppcsr_destroy", "pppcsr_num_partitions",
     "pppcsr_get_partition", "pppcsr_partition_start", "pppcsr_partition", "pppcsr_add_edge", "pppcsr_remove_edge",
     "pppcsr_edge_exists", "pppcsr_get_neighbourhood", "pppcsr_get_node", "pppcsr_get_n", "pppcsr_add_node",
@@ -156,6 +156,7 @@ def load_library(path=None):
     L.ppcsr_set_option.argtypes = [c_vp, ctypes.c_char_p, c_i64]
     L.ppcsr_snapshot.argtypes = [c_vp]
     L.ppcsr_restore.argtypes = [c_vp]
+    L.ppcsr_debug_snap_counters.argtypes = [c_vp, c_vp]
     L.ppcsr_check_invariants.argtypes = [c_vp, ctypes.POINTER(c_u64)]
     L.ppcsr_bench_scan_all.argtypes = [c_vp, ctypes.POINTER(c_dbl), ctypes.POINTER(c_u64)]
     L.ppcsr_bench_rebalance.argtypes = [c_vp, c_u64, c_int, ctypes.POINTER(c_dbl)]
@@ -442,6 +443,13 @@ class PCSR(_Consumers):
 
     def snapshot(self): self._chk(self.L.ppcsr_snapshot(self.h))
     def restore(self): self._chk(self.L.ppcsr_restore(self.h))
+
+    def debug_snap_counters(self):
+        """Debugging (ppcsr_debug_snap_counters): dict of full_saves, full_loads, inc_commits, inc_rollbacks — both snapshots,
+        since creation — and leaves_copied, nodes_copied of the last incremental synchronisation (option snap_count = 1)"""
+        out = np.zeros(6, np.uint64)
+        self._chk(self.L.ppcsr_debug_snap_counters(self.h, out.ctypes.data))
+        return dict(zip(("full_saves", "full_loads", "inc_commits", "inc_rollbacks", "leaves_copied", "nodes_copied"), (int(x) for x in out)))
 
     def check_invariants(self):
         bad = c_u64()

@@ -88,6 +88,13 @@ struct Engine::Impl {
     uint64_t gen = 0;      // array generation it belongs to (a resize / bulk build / add_node starts a new one: full copy)
   };
   Snap snap, esnap;
+  // test hooks (ppcsr_debug_snap_counters): workgroup cap of the two sync kernels (option "snap_grid"); full saves, full loads,
+  // incremental commits, incremental rollbacks over both snapshots, then leaves / node records the last incremental sync copied
+  // (the last two only while option "snap_count" is on: d_snapcnt is zeroed in front of the sync and read back behind it)
+  uint32_t snap_grid = 4096;
+  bool snap_count = false;
+  uint64_t snap_ctr[6] = {0, 0, 0, 0, 0, 0};
+  unsigned long long *d_snapcnt = nullptr;
   // dirty tags: writers stamp View::ldirty / vdirty with `serial`; every snapshot synchronisation advances it
   uint32_t serial = 1;
   uint64_t array_gen = 1;
@@ -486,6 +493,7 @@ Engine::~Engine() {
   gpu::hfree(p.h_total);
   GPU_DFREE(p.d_table);
   if (p.d_ip) GPU_DFREE(p.d_ip);
+  if (p.d_snapcnt) GPU_DFREE(p.d_snapcnt);
   GPU_DFREE(p.d_plans);
   if (p.d_ops) GPU_DFREE(p.d_ops);
   if (p.d_rank) GPU_DFREE(p.d_rank);
@@ -636,6 +644,21 @@ int Engine::set_option(const char *key, int64_t value) {
                 : k == "query_gather_rows" ? p.q.gather_rows
                 : k == "query_gather_chunks" ? p.q.gather_chunks : p.q.gather_stage;
     f = (uint64_t)value;
+    return PPCSR_OK;
+  }
+  // snapshot hooks (test hooks as well): the workgroup cap of k_snap_sync_leaves / k_snap_sync_nodes, which moves their
+  // grid-stride seam down to small arrays, and the counting of what an incremental synchronisation copies
+  if (k == "snap_grid") {
+    if (value < 1 || value > 4096) return fail(PPCSR_EINVAL, "snap_grid must be in [1, 4096]");
+    p.snap_grid = (uint32_t)value;
+    return PPCSR_OK;
+  }
+  if (k == "snap_count") {
+    if (value && !p.d_snapcnt) {
+      gpu::set_device(device_);
+      GCHK(gpu::dmalloc((void **)&p.d_snapcnt, 2 * sizeof(unsigned long long)));
+    }
+    p.snap_count = value != 0;
     return PPCSR_OK;
   }
   if (k == "rb_inplace_cpw") {
@@ -2330,6 +2353,28 @@ static void advance_serial(Engine::Impl &p, uint32_t by) {
 static bool snap_in_step(const Engine::Impl &p, const Engine::Impl::Snap &sn) {
   return sn.valid && sn.gen == p.array_gen && sn.v.g.N == p.v.g.N && sn.v.g.n == p.v.g.n && sn.v.g.logN == p.v.g.logN && p.serial < 0xFFFFFF00u;
 }
+// the two sync kernels over the live arrays and snapshot `sn`, which is in step with them (to_live = 0: commit, 1: rollback).
+// Option snap_count: the leaves / node records copied come back in snap_ctr[4], [5] — a memset in front and a read-back with a
+// stream synchronisation behind the launches; off, the launches get nullptr and nothing is added around them.
+static int snap_sync(Engine::Impl &p, Engine::Impl::Snap &sn, uint32_t newtag, uint32_t to_live) {
+  const uint64_t leaves = p.v.g.N >> p.v.g.sh, grid = p.snap_grid;
+  unsigned long long *cnt = p.snap_count ? p.d_snapcnt : nullptr;
+  int e;
+  if (cnt && (e = gpu::dset(cnt, 0, 2 * sizeof(unsigned long long), p.stream))) return e;
+  GPU_LAUNCH(p.stream, k_snap_sync_leaves, (uint32_t)std::min<uint64_t>((leaves + 255) / 256, grid), 256, p.v.items, p.v.leafcnt, sn.v.items, sn.v.leafcnt,
+             p.v.ldirty, leaves, p.v.g.sh, sn.synced, newtag, to_live, cnt);
+  if (p.v.g.n)
+    GPU_LAUNCH(p.stream, k_snap_sync_nodes, (uint32_t)std::min<uint64_t>(((uint64_t)p.v.g.n + 255) / 256, grid), 256, p.v.nodes, sn.v.nodes, p.v.vdirty,
+               (uint64_t)p.v.g.n, sn.synced, newtag, to_live, cnt ? cnt + 1 : (unsigned long long *)nullptr);
+  if (cnt) {
+    unsigned long long h[2] = {0, 0};
+    if ((e = gpu::d2h(h, cnt, sizeof(h), p.stream))) return e;
+    if ((e = gpu::sync(p.stream))) return e;
+    p.snap_ctr[4] = h[0];
+    p.snap_ctr[5] = h[1];
+  }
+  return 0;
+}
 // live state -> snapshot.  In step with the arrays (same generation): only what was written since its last synchronisation
 // (dirty tags); otherwise a full copy.
 static int snap_commit(Engine::Impl &p, Engine::Impl::Snap &sn) {
@@ -2345,13 +2390,10 @@ static int snap_commit(Engine::Impl &p, Engine::Impl::Snap &sn) {
   if (!snap_in_step(p, sn)) {
     if ((e = snap_full_save(p, sn))) return e;
     sn.gen = p.array_gen;
+    p.snap_ctr[0]++;
   } else {
-    const uint64_t leaves = p.v.g.N >> p.v.g.sh;
-    GPU_LAUNCH(p.stream, k_snap_sync_leaves, (uint32_t)std::min<uint64_t>((leaves + 255) / 256, 4096), 256, p.v.items, p.v.leafcnt, sn.v.items, sn.v.leafcnt,
-               p.v.ldirty, leaves, p.v.g.sh, sn.synced, 0u, 0u, (unsigned long long *)nullptr);
-    if (p.v.g.n)
-      GPU_LAUNCH(p.stream, k_snap_sync_nodes, (uint32_t)std::min<uint64_t>(((uint64_t)p.v.g.n + 255) / 256, 4096), 256, p.v.nodes, sn.v.nodes, p.v.vdirty,
-                 (uint64_t)p.v.g.n, sn.synced, 0u, 0u);
+    if ((e = snap_sync(p, sn, 0u, 0u))) return e;
+    p.snap_ctr[2]++;
   }
   sn.synced = p.serial;
   advance_serial(p, 1);
@@ -2362,6 +2404,7 @@ static int snap_rollback(Engine::Impl &p, Engine::Impl::Snap &sn, Engine::Impl::
   int e;
   if (!snap_in_step(p, sn)) {
     if ((e = snap_full_load(p, sn))) return e;
+    p.snap_ctr[1]++;
     p.array_gen++;  // the live arrays were rewritten wholesale: nothing the other snapshot knows about them holds
     sn.gen = p.array_gen;
     other.gen = 0;
@@ -2369,13 +2412,9 @@ static int snap_rollback(Engine::Impl &p, Engine::Impl::Snap &sn, Engine::Impl::
     advance_serial(p, 1);
     return 0;
   }
-  const uint64_t leaves = p.v.g.N >> p.v.g.sh;
   const uint32_t newtag = p.serial + 1u;  // what the rollback writes is "written" for the other snapshot
-  GPU_LAUNCH(p.stream, k_snap_sync_leaves, (uint32_t)std::min<uint64_t>((leaves + 255) / 256, 4096), 256, p.v.items, p.v.leafcnt, sn.v.items, sn.v.leafcnt,
-             p.v.ldirty, leaves, p.v.g.sh, sn.synced, newtag, 1u, (unsigned long long *)nullptr);
-  if (p.v.g.n)
-    GPU_LAUNCH(p.stream, k_snap_sync_nodes, (uint32_t)std::min<uint64_t>(((uint64_t)p.v.g.n + 255) / 256, 4096), 256, p.v.nodes, sn.v.nodes, p.v.vdirty,
-               (uint64_t)p.v.g.n, sn.synced, newtag, 1u);
+  if ((e = snap_sync(p, sn, newtag, 1u))) return e;
+  p.snap_ctr[3]++;
   sn.synced = newtag;
   advance_serial(p, 2);
   return 0;
@@ -2386,6 +2425,12 @@ int Engine::snapshot() {
   GCHK(gpu::set_device(device_));
   GCHK(snap_commit(p, p.snap));
   GCHK(gpu::sync(p.stream));
+  return PPCSR_OK;
+}
+
+int Engine::snap_counters(uint64_t out[6]) {
+  if (!out) return fail(PPCSR_EINVAL, "snap counters: no output");
+  for (int i = 0; i < 6; i++) out[i] = p_->snap_ctr[i];
   return PPCSR_OK;
 }
 

@@ -126,6 +126,8 @@ class Engine {
   int snapshot();  // device-side copy of the whole state (items, nodes, leaf counts, geometry)
   int restore();   // back to the last snapshot (device-to-device)  // whole-window rebalance kernel timing
 
+  int snap_counters(uint64_t out[6]);  // ppcsr_debug_snap_counters (include/ppcsr.h)
+
   uint64_t N() const;
   uint32_t n() const;
   int logN() const;

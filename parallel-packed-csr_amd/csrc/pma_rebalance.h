@@ -873,10 +873,14 @@ PMA_KERNEL void k_snap_sync_leaves(Edge *live, uint32_t *live_cnt, Edge *snap, u
   }
   if (copied != nullptr && lane == 0 && mine) wv::atomic_add_u64(copied, mine);
 }
-PMA_KERNEL void k_snap_sync_nodes(Node *live, Node *snap, uint32_t *tag, uint64_t n, uint32_t synced, uint32_t newtag, uint32_t to_live) {
+// (copied, both kernels: nullptr, or a counter that receives the number of entries copied — ppcsr_debug_snap_counters)
+PMA_KERNEL void k_snap_sync_nodes(Node *live, Node *snap, uint32_t *tag, uint64_t n, uint32_t synced, uint32_t newtag, uint32_t to_live,
+                                  unsigned long long *copied) {
   const uint64_t stride = (uint64_t)wv::grid_dim() * wv::block_dim();
+  unsigned long long mine = 0;
   for (uint64_t u = (uint64_t)wv::block_idx() * wv::block_dim() + wv::thread_idx(); u < n; u += stride) {
     if (tag[u] > synced) {
+      mine++;
       if (to_live) {
         live[u] = snap[u];
         tag[u] = newtag;
@@ -885,6 +889,7 @@ PMA_KERNEL void k_snap_sync_nodes(Node *live, Node *snap, uint32_t *tag, uint64_
       }
     }
   }
+  if (copied != nullptr && mine) wv::atomic_add_u64(copied, mine);
 }
 PMA_KERNEL void k_fill_u32(uint32_t *p, uint64_t n, uint32_t value) {
   const uint64_t stride = (uint64_t)wv::grid_dim() * wv::block_dim();

@@ -952,9 +952,11 @@ PMA_KERNEL void o_apply_x(OptArgs a) {
 PMA_MARK(0) PMA_MARK(1) PMA_MARK(2) PMA_MARK(3) PMA_MARK(4) PMA_MARK(5) PMA_MARK(6) PMA_MARK(7)
 #undef PMA_MARK
 
-// test hook: one workgroup rebalances one window with the big-window routine (leaf counts must be exact)
+// test hook: one workgroup rebalances one window with the big-window routine (leaf counts must be exact).  The routine stamps the
+// node records it moves; the leaves of a window are stamped by whoever queues it (apply_op, k_exclusive), here by the hook itself
 PMA_KERNEL void k_block_rebalance(View v, uint64_t wstart, uint64_t wlen, Edge *scratch) {
   PMA_SHARED dev::BigShared sh;
+  if (wv::wave_in_block() == 0) dev::mark_leaves(v, wstart >> v.g.sh, (wstart + wlen - 1) >> v.g.sh);
   dev::redistribute_block(v, wstart, wlen, scratch, sh);
 }
 

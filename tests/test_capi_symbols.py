@@ -25,6 +25,7 @@ def test_header_symbols_exported(lib):
     missing = [s for s in sorted(declared) if not hasattr(lib, s)]
     assert not missing, missing
     assert set(load_pkg().EXPORTED) <= declared
+    assert "ppcsr_debug_snap_counters" in declared and "ppcsr_debug_snap_counters" in load_pkg().EXPORTED
 
 
 def test_no_cpu_fallback(lib):
