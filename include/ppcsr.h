@@ -115,7 +115,11 @@ int ppcsr_gather_neighbourhoods_device(ppcsr_t h, const uint32_t *d_vertices, ui
  * produces depends on the insertion history.  This call yields a valid packed-memory array with the same neighbourhoods,
  * the same num_neighbors (every add counts, duplicates keep the last value) and the same invariants, but NOT the slot
  * layout of the one-by-one build; updates applied afterwards go through the ordinary (sequentially exact) path.  Entries
- * with op == 0 or src >= n are ignored, as add_edge ignores them.  Fails with EINVAL if the graph already holds edges. */
+ * with op == 0 or src >= n are ignored, as add_edge ignores them.  Fails with EINVAL if the graph already holds edges.
+ * The layout is determined (tests/bulk_model.py holds it slot by slot): with E surviving edges the array keeps its size N or
+ * doubles it until (n + E + 1) / N < 3/4, the root's upper density — the root still accepts one more insert; it never
+ * shrinks —, and the sequence sentinel 0, edges of vertex 0 ascending, sentinel 1, ... takes the slots redistribute()
+ * (PCSR.cpp:207-247) gives n + E elements in the window of the whole array. */
 int ppcsr_bulk_build(ppcsr_t h, const ppcsr_op *adds, uint64_t n, double *device_ms);
 /* Graph-algorithm consumers run on the device over the gapped array.
  * bfs — src/utility/bfs.h:15-36: levels[v] = BFS level of v from `start`, UINT32_MAX when unreachable (levels: n entries).
@@ -421,7 +425,8 @@ int pppcsr_exchange_bulk_build(pppcsr_t h, pppcsr_comm_t c, const ppcsr_op *d_ad
 int pppcsr_repartition_export(pppcsr_t h, const uint64_t *new_starts, const ppcsr_op **d_ops, uint64_t *n, const ppcsr_op **d_nn,
                               uint64_t *n_nn);
 int pppcsr_set_num_neighbors_device(pppcsr_t h, const ppcsr_op *d_recs, uint64_t n);
-int pppcsr_bulk_build_device(pppcsr_t h, const ppcsr_op *d_adds, uint64_t n); /* global src; every receiving partition must be empty */
+/* global src; every receiving partition must be empty (ignored rows are received too); a partition no row is routed to is not touched */
+int pppcsr_bulk_build_device(pppcsr_t h, const ppcsr_op *d_adds, uint64_t n);
 int pppcsr_repartition(pppcsr_t h, const uint64_t *new_starts);
 int pppcsr_balanced_starts(pppcsr_t h, uint64_t *starts_out);
 

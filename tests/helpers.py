@@ -32,6 +32,16 @@ def load_pkg():
     return _load("ppcsr_amd", os.path.join(PKG_DIR, "__init__.py"))
 
 
+def hip_runtime():
+    """ctypes handle of the HIP runtime this process holds already, for hipMalloc / hipMemcpy / hipFree in GPU tests; call it after
+    load_pkg().load_library().  Where PyTorch is installed the engine shares the wheel's runtime (__init__.py _share_hip_runtime:
+    loaded by path, symbols global, SONAME libamdhip64.so.<major>), and asking the loader for "libamdhip64.so" by name would bring
+    in a SECOND runtime, the system's — which need not even load beside the wheel's HSA runtime.  So: the global symbols first."""
+    import ctypes
+    g = ctypes.CDLL(None)
+    return g if hasattr(g, "hipMalloc") else ctypes.CDLL("libamdhip64.so")
+
+
 def digest(items, nodes, geom):
     h = hashlib.sha256()
     h.update(np.array(geom, np.int64).tobytes())
@@ -163,18 +173,23 @@ def live_triples(items, base=0):
     return out
 
 
-def check_repartitioned(new_states, old_states, old_starts, new_starts, total_n, build_bulk):
+def check_repartitioned(new_states, old_states, old_starts, new_starts, total_n, build_bulk=None, lock_search=True):
     """the rule of pppcsr_repartition (include/ppcsr.h) checked on raw states: new_states[k] / old_states[k] = (items, nodes) of
-    partition k after / before.  A partition whose vertex range did not change is untouched bit for bit.  A changed one
-    equals what the SAME bulk path builds from the edges that fall into its new range — build_bulk(size, adds) -> (items,
-    nodes) of a fresh engine of `size` vertices bulk-built from `adds` (partition-local src, ascending (src, dest)) — except
-    for num_neighbors, which every vertex carries over unchanged (it is a counter of calls, not the degree)."""
+    partition k after / before.  A partition whose vertex range did not change is untouched bit for bit.  A changed one equals
+    the exact host model of the bulk build (tests/bulk_model.py) of the edges that fall into its new range — partition-local src,
+    ascending (src, dest), into the array a fresh Oracle of that many vertices has — or, when no edge falls into it, that fresh
+    Oracle's state: nothing is routed to it, so nothing builds it.  Except for num_neighbors, which every vertex carries over
+    unchanged (it is a counter of calls, not the degree).  build_bulk(size, adds) -> (items, nodes), when given, replaces the
+    model as the expectation.  Returns the expected (items, nodes) of every partition (None for one without vertices)."""
+    from bulk_model import bulk_model
+    from oracle_lib import Oracle
     P = len(old_states)
     end = lambda st, k: int(st[k + 1]) if k + 1 < P else int(total_n)
     changed = [int(old_starts[k]) != int(new_starts[k]) or end(old_starts, k) != end(new_starts, k) for k in range(P)]
     moved = [live_triples(old_states[k][0], int(old_starts[k])) for k in range(P) if changed[k]]
     moved = np.concatenate(moved) if moved else np.zeros((0, 3), np.uint32)
     nn_old = np.concatenate([np.asarray(old_states[k][1], np.uint32).reshape(-1, 3)[:, 2] for k in range(P)])  # by global vertex
+    want = []
     for k in range(P):
         it, nd = new_states[k]
         nd = np.asarray(nd, np.uint32).reshape(-1, 3)
@@ -182,19 +197,29 @@ def check_repartitioned(new_states, old_states, old_starts, new_starts, total_n,
         assert len(nd) == hi - lo, f"partition {k}: {len(nd)} vertices, range [{lo}, {hi})"
         if not changed[k]:
             assert np.array_equal(it, old_states[k][0]) and np.array_equal(nd, np.asarray(old_states[k][1], np.uint32).reshape(-1, 3)), f"partition {k} was to stay untouched"
+            want.append((old_states[k][0], old_states[k][1]) if hi > lo else None)
             continue
         sub = moved[(moved[:, 0] >= lo) & (moved[:, 0] < hi)].copy()
         sub[:, 0] -= np.uint32(lo)
         if hi > lo:
-            eit, end_ = build_bulk(hi - lo, sub)
-            end_ = np.asarray(end_, np.uint32).reshape(-1, 3)
+            if build_bulk is not None:
+                eit, end_ = build_bulk(hi - lo, sub)
+            else:
+                fresh = Oracle(hi - lo, lock_search=lock_search)
+                eit, end_ = bulk_model(hi - lo, fresh.geometry()[0], sub, lock_search=lock_search) if len(sub) else fresh.state()
+            end_ = np.asarray(end_, np.uint32).reshape(-1, 3).copy()
+            end_[:, 2] = nn_old[lo:hi]
+            want.append((eit, end_))
             assert np.array_equal(it, eit), f"partition {k}: edges[] differ from the bulk build of its new range"
             assert np.array_equal(nd[:, :2], end_[:, :2]), f"partition {k}: vertex ranges differ from the bulk build"
         np.testing.assert_array_equal(nd[:, 2], nn_old[lo:hi], err_msg=f"partition {k}: num_neighbors not carried over")
         if hi > lo:
             check_pma_invariants(np.asarray(it, np.uint32).reshape(-1, 3), nd)
+        else:
+            want.append(None)
         if len(sub):
             np.testing.assert_array_equal(live_triples(it, lo), sub + np.array([lo, 0, 0], np.uint32))
+    return want
 
 
 # ---- exact models of the batched reads (ppcsr_lookup_edges / ppcsr_gather_neighbourhoods) on an exported state ------------

@@ -231,22 +231,10 @@ def test_native_exchange_and_repartition_world2_hostsim(n_global, n_parts):
     for k, (items, nodes) in enumerate(flat(0)):
         oi, on = parts[k].state()
         assert np.array_equal(items, oi) and np.array_equal(nodes, on), f"partition {k} after the exchanged batches"
-    # the repartition rule, checked on the raw states (the bulk path itself run on a fresh emulator engine)
-    from helpers import load_pkg
-    from test_sim_engine import SIM_SO
-    pkg = load_pkg()
-    lib = pkg.load_library(SIM_SO)
-
-    def build_bulk(size, adds):
-        e = pkg.PCSR(size, lib=lib)
-        e.bulk_build(adds)
-        out = e.state()
-        e.close()
-        return out
-
-    check_repartitioned(flat(1), flat(0), old, new, n_global, build_bulk)
-    # updates after the rebuild are exact again: oracles started from the rebuilt states
-    parts = [Oracle.from_state(*st) for st in flat(1)]
+    # the repartition rule, checked on the raw states against the exact host model of the bulk build (tests/bulk_model.py)
+    want = check_repartitioned(flat(1), flat(0), old, new, n_global)
+    # updates after the rebuild are exact again: oracles started from the expected states
+    parts = [Oracle.from_state(*st) for st in want]
     glob = np.concatenate(after)
     own = np.searchsorted(new, glob[:, 0], side="right") - 1
     for k in range(n_parts):

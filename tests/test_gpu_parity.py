@@ -451,8 +451,10 @@ def test_partial_window_rebalance_in_place(pkg, streams, shape, lists):
 
 
 def test_bulk_build_fast_path(pkg, streams):
-    """non-parity bulk build of a 1 M-edge RMAT graph: valid PMA invariants, same edge set / values /
-    num_neighbors as the one-by-one build (oracle), consumers agree, and ordinary updates afterwards keep all of it"""
+    """non-parity bulk build of a 1 M-edge RMAT graph: the state is the exact host model's (tests/bulk_model.py; the
+    seams are in tests/test_gpu_bulk.py), which holds the edge set / values / num_neighbors of the one-by-one build (oracle),
+    consumers agree, and ordinary updates afterwards stay bit-exact against an oracle started from the model"""
+    from bulk_model import bulk_model
     from helpers import check_pma_invariants, edge_view, reference_consumers
     scale, m = 16, 1_000_000
     n = 1 << scale
@@ -462,24 +464,24 @@ def test_bulk_build_fast_path(pkg, streams):
     ops[3::17, 0] = n + 5       # ignored: src >= n
     ops[1000:2000] = ops[0:1000]  # duplicates: counted, last value wins
     ops[1000:2000, 2] = 9
-    eng, o = pkg.PCSR(n), Oracle(n)
+    eng, one_by_one = pkg.PCSR(n), Oracle(n)
+    N0 = eng.geometry()[0]
     ms = eng.bulk_build(ops, with_ms=True)
-    o.apply(ops[ops[:, 2] != 0])
-    ei, en = eng.state()
-    check_pma_invariants(ei, en)
-    assert eng.check_invariants() == 0
-    for a, b in zip(edge_view(ei, en), edge_view(*o.state())):
+    assert np.isfinite(ms) and ms >= 0.0
+    one_by_one.apply(ops[ops[:, 2] != 0])
+    mi, mn = bulk_model(n, N0, ops)
+    check_pma_invariants(mi, mn)
+    for a, b in zip(edge_view(mi, mn), edge_view(*one_by_one.state())):
         np.testing.assert_array_equal(a, b)
-    lv, _ = reference_consumers(o, 0, np.ones(n, np.float32))
+    o = Oracle.from_state(mi, mn)
+    _same(eng, o, "bulk build")
+    lv, _ = reference_consumers(one_by_one, 0, np.ones(n, np.float32))
     np.testing.assert_array_equal(eng.bfs(0), lv)
     s2, d2 = streams.rmat_edges(scale, 200_000, seed=52)
     more = streams.mixed_existing_stream(ops[(ops[:, 2] != 0) & (ops[:, 0] < n)][:300_000], streams.adds(s2, d2), seed=53)
     eng.apply(more)
     o.apply(more)
-    ei, en = eng.state()
-    check_pma_invariants(ei, en)
-    for a, b in zip(edge_view(ei, en), edge_view(*o.state())):
-        np.testing.assert_array_equal(a, b)
+    _same(eng, o, "updates after the bulk build")
     with pytest.raises(pkg.PpcsrError):
         eng.bulk_build(ops)
 
@@ -619,7 +621,7 @@ def _d2d(dst, src, nbytes):
 @pytest.mark.parametrize("P", [4, 8])
 def test_repartition(pkg, streams, P):
     """pppcsr_repartition: partitions whose range stays are untouched bit for bit; partitions that change equal
-    what the same bulk path builds from the edges of their new range, with every vertex's num_neighbors carried over
+    the exact host model of the bulk build (tests/bulk_model.py) of the edges of their new range, with every vertex's num_neighbors carried over
     (tests/helpers.py check_repartitioned: edge set, vertex ranges, PMA invariants); neighbourhoods survive; updates applied
     afterwards are bit-exact against oracles started from the rebuilt states.  Skewed graph (RMAT labels) to balanced starts
     and back; duplicates and deletes of missing edges in the load make num_neighbors differ from the degree."""
@@ -638,24 +640,17 @@ def test_repartition(pkg, streams, P):
     st = pp.balanced_starts()
     assert st[0] == 0 and np.all(np.diff(st.astype(np.int64)) >= 0)
 
-    def build_bulk(size, adds):
-        e = pkg.PCSR(size)
-        e.bulk_build(adds)
-        out = e.state()
-        e.close()
-        return out
-
     for new in (st, old):  # to the balanced layout and back to the uniform one
         before = [pp.partition(k).state() for k in range(P)]
         pp.repartition(new)
         assert pp.get_n() == n and [pp.partition_start(k) for k in range(P)] == [int(x) for x in new]
         after = [pp.partition(k).state() for k in range(P)]
-        check_repartitioned(after, before, old, new, n, build_bulk)
+        want = check_repartitioned(after, before, old, new, n)  # (against the exact host model of the bulk build)
         for k in range(P):
             assert pp.partition(k).check_invariants() == 0
         for v, adj in adj_before.items():
             np.testing.assert_array_equal(pp.get_neighbourhood(v), adj)
-        parts = [Oracle.from_state(*after[k]) for k in range(P)]
+        parts = [Oracle.from_state(*want[k]) for k in range(P)]
         upd = streams.mixed_existing_stream(core[:50000], streams.random_stream(n, 30000, seed=int(new[1]) % 1000), seed=11)
         pp.apply(upd)
         own = np.searchsorted(new, upd[:, 0], side="right") - 1

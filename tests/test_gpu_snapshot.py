@@ -9,7 +9,7 @@ import pytest
 
 import snap_cases as sc
 import snap_checks as ck
-from helpers import load_pkg
+from helpers import hip_runtime, load_pkg
 
 pytestmark = pytest.mark.gpu
 
@@ -20,7 +20,7 @@ def backend():
     pkg.load_library()  # must be the in-tree HIP build; raises if missing
 
     import ctypes
-    hip = ctypes.CDLL("libamdhip64.so")  # (the runtime the engine library holds already)
+    hip = hip_runtime()  # (the runtime the engine library holds already)
     hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
     hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
     hip.hipFree.argtypes = [ctypes.c_void_p]

@@ -387,8 +387,10 @@ def test_sim_slide_off_the_end(sim, streams):
 
 
 def test_sim_bulk_build(sim, streams):
-    """non-parity bulk build: same edge set / values / num_neighbors as the one-by-one build, valid PMA
-    invariants, and ordinary updates afterwards keep both"""
+    """non-parity bulk build: the state is the exact host model's (tests/bulk_model.py; the seams are in
+    tests/test_sim_bulk.py), which holds the edge set / values / num_neighbors of the one-by-one build, and ordinary updates
+    afterwards stay bit-exact against an oracle started from the model"""
+    from bulk_model import bulk_model
     from helpers import check_pma_invariants as _check_invariants_numpy, edge_view as _edge_view
     n = 150
     ops = streams.random_stream(n, 4000, seed=41, p_delete=0.0)
@@ -396,23 +398,22 @@ def test_sim_bulk_build(sim, streams):
     ops[5::13, 0] = n + 7    # ignored entries (src >= n)
     ops[100:200] = ops[0:100]  # duplicates (count in num_neighbors; last value wins)
     ops[100:200, 2] += 3
-    e, o = sim(n, mode=1), Oracle(n)
+    e, one_by_one = sim(n, mode=1), Oracle(n)
+    N0 = e.geometry()[0]
     e.bulk_build(ops)
     for r in ops:
         if r[2] != 0:
-            o.add_edge(int(r[0]), int(r[1]), int(r[2]))
-    ei, en = e.state()
-    _check_invariants_numpy(ei, en)
-    assert e.check_invariants() == 0
-    for a, b in zip(_edge_view(ei, en), _edge_view(*o.state())):
+            one_by_one.add_edge(int(r[0]), int(r[1]), int(r[2]))
+    mi, mn = bulk_model(n, N0, ops)
+    _check_invariants_numpy(mi, mn)
+    for a, b in zip(_edge_view(mi, mn), _edge_view(*one_by_one.state())):
         np.testing.assert_array_equal(a, b)
+    o = Oracle.from_state(mi, mn)
+    _same(e, o, "bulk build")
     more = streams.random_stream(n, 3000, seed=42, p_delete=0.4)
     e.apply(more)
     o.apply(more)
-    ei, en = e.state()
-    _check_invariants_numpy(ei, en)
-    for a, b in zip(_edge_view(ei, en), _edge_view(*o.state())):
-        np.testing.assert_array_equal(a, b)
+    _same(e, o, "updates after the bulk build")
     with pytest.raises(Exception):
         e.bulk_build(ops)  # only an empty graph can be bulk-built
 
@@ -530,13 +531,6 @@ def test_sim_xchg_steps_and_repartition(streams):
     with pytest.raises(pkg.PpcsrError):
         pp.repartition(np.array([0, 150, 100, 200], np.uint64))
 
-    def build_bulk(size, adds):  # the same bulk path on a fresh engine
-        e = pkg.PCSR(size, lib=lib)
-        e.bulk_build(adds)
-        out = e.state()
-        e.close()
-        return out
-
     for new in (np.array([0, 50, 50, 299], np.uint64), st):
         before = [pp.partition(k).state() for k in range(P)]
         (d_moved, n_moved), (d_nn, n_nn) = pp.repartition_export(new)  # (pppcsr_repartition = these three steps; the recreated
@@ -546,9 +540,9 @@ def test_sim_xchg_steps_and_repartition(streams):
         tune()
         assert [pp.partition_start(k) for k in range(P)] == [int(x) for x in new]
         after = [pp.partition(k).state() for k in range(P)]
-        check_repartitioned(after, before, old, new, n, build_bulk)
-        # updates after the (non-parity) rebuild are exact again: oracles started from the engine's state
-        parts = [Oracle.from_state(*after[k]) for k in range(P)]
+        want = check_repartitioned(after, before, old, new, n)  # (against the exact host model of the bulk build)
+        # updates after the (non-parity) rebuild are exact again: oracles started from the expected states
+        parts = [Oracle.from_state(*(want[k] if want[k] is not None else after[k])) for k in range(P)]
         ops2 = streams.random_stream(n, 500, seed=6 + int(new[1]), p_delete=0.3)
         pp.apply(ops2)
         own = np.searchsorted(new, ops2[:, 0], side="right") - 1
