@@ -143,6 +143,35 @@ int ppcsr_pagerank(ppcsr_t h, const float *node_values, float *out, double *devi
 #define PPCSR_NO_PATH 0xFFFFFFFFFFFFFFFFull
 int ppcsr_sssp(ppcsr_t h, uint32_t start, uint64_t *dist, double *device_ms);
 int ppcsr_components(ppcsr_t h, uint32_t *labels, double *device_ms);
+/* Shortest-path counts and betweenness centrality (Brandes 2001), over exactly the edge set ppcsr_bfs walks: live non-sentinel
+ * slots, slot N - 1 excluded, local src < n, destinations >= n skipped.  The edges are DIRECTED and their values play no part.
+ * path_counts — the forward phase alone.  levels[v] is what ppcsr_bfs gives (UINT32_MAX when unreachable); sigma[v] is the
+ *   NUMBER of shortest (fewest-edges) directed paths from `start` to v, in fp64: sigma[start] = 1, 0 when unreachable
+ *   (levels, sigma: n entries; either may be NULL, not both).  Every addition adds integers, so sigma is exact and does not
+ *   depend on the order of the additions while every count is below 2^53; beyond that each sum is rounded to fp64 in an
+ *   unspecified order.  Counts are fp64 and not 64-bit integers on purpose: a chain of 70 two-wide diamonds already has 2^70
+ *   paths.  Counts beyond the fp64 range (above about 1.8e308) are NOT guarded: they become infinite, and betweenness from
+ *   such a source is then NaN.
+ * betweenness — for every source s, with level and sigma from s,
+ *     delta_s(v) = sum over stored (v, w) with level(w) = level(v) + 1 of (sigma(v) / sigma(w)) * (1 + delta_s(w))
+ *     bc[v]      = sum over i < k with sources[i] != v of delta_{sources[i]}(v)                        (bc: n entries)
+ *   Endpoints are excluded, nothing is halved and nothing is normalised.  A repeated source counts once each time; k == 0
+ *   gives all zeros; sources = 0 .. n - 1 gives exact betweenness.  For a graph stored symmetrically this is twice the
+ *   undirected value; it equals networkx betweenness_centrality(DiGraph, normalized=False).  The arithmetic is fp64 as
+ *   written — one division, one addition and one multiplication per edge of the shortest-path DAG, unfused — and the sums may
+ *   be taken in any order, so the last bits can differ from run to run.
+ *   Accuracy: all terms are non-negative, so a sum of m terms in any order or tree carries a relative error of at most
+ *   (m - 1) u, u = 2^-53, and a term adds three roundings.  delta of a vertex therefore carries at most dmax + 2 roundings more
+ *   than the deepest delta it is built from, where dmax is the largest out-degree; with D the deepest BFS level over the
+ *   sources that is D (dmax + 2) u, and bc adds at most k such values: to first order, while sigma is exact,
+ *     |bc[v] - exact| <= (D (dmax + 2) + k) * 2^-53 * exact.
+ * Same contract as every consumer: synchronous on the engine's stream, sees every batch applied before it, writes nothing to
+ * the graph (state, stats, dirty tags and snapshot unchanged), device_ms may be NULL.  The calls intersect nothing, so — as
+ * bfs and components — they also answer in the sequential regime (stats.narrow == 0).  EINVAL: null handle; levels and sigma
+ * both NULL; bc NULL; sources NULL with k > 0; any sources[i] >= n (checked before the first launch: nothing has run);
+ * start >= n. */
+int ppcsr_path_counts(ppcsr_t h, uint32_t start, uint32_t *levels, double *sigma, double *device_ms);
+int ppcsr_betweenness(ppcsr_t h, const uint32_t *sources, uint64_t k, double *bc, double *device_ms);
 /* Core numbers (the k-core decomposition), over the edge set ppcsr_components hooks (live non-sentinel slots, slot N - 1
  * excluded, destinations >= n skipped) and in the undirected graph G ppcsr_triangles counts in, the upper orientation: {a, b},
  * a < b < n, is an edge exactly when the pair (a, b) is stored; stored pairs with src > dst and self-loops play no part — so
@@ -342,6 +371,13 @@ int pppcsr_components(pppcsr_t h, uint32_t *labels, double *device_ms);
  * pppcsr_components; a partition in the sequential regime is answered.  EINVAL: null handle, core and kmax both NULL, or a
  * partition not resident in this process.  EUNSUPPORTED: the partitions sit on more than one device. */
 int pppcsr_kcore(pppcsr_t h, uint32_t *core, uint32_t *kmax, double *device_ms);
+/* ppcsr_path_counts / ppcsr_betweenness over the GLOBAL vertex ids (start, sources; levels, sigma, bc: pppcsr_get_n entries),
+ * one device call over every partition's array: path_counts does not depend on the partitioning, betweenness only within its
+ * error bound (the order of the sums differs).  Same contract as pppcsr_sssp; a partition in the sequential regime is
+ * answered.  EINVAL: as the single calls (start or a source >= pppcsr_get_n), or a partition not resident in this process.
+ * EUNSUPPORTED: the partitions sit on more than one device. */
+int pppcsr_path_counts(pppcsr_t h, uint32_t start, uint32_t *levels, double *sigma, double *device_ms);
+int pppcsr_betweenness(pppcsr_t h, const uint32_t *sources, uint64_t k, double *bc, double *device_ms);
 /* ppcsr_triangles / ppcsr_common_neighbours over the GLOBAL vertex ids (tri: pppcsr_get_n entries), one device call over every
  * partition's array: a pair may have its two vertices in different partitions, and the results do not depend on the
  * partitioning.  Same contract as pppcsr_bfs.  EINVAL: as the single calls, or a partition not resident in this process.

@@ -73,6 +73,7 @@ EXPORTED = [
     "ppcsr_gather_neighbourhoods_device", "pppcsr_lookup_edges", "pppcsr_gather_neighbourhoods", "pppcsr_set_option",
     "pppcsr_bfs", "pppcsr_pagerank", "ppcsr_sssp", "ppcsr_components", "pppcsr_sssp", "pppcsr_components",
     "ppcsr_debug_chain_probe", "ppcsr_debug_isect_probe", "ppcsr_kcore", "pppcsr_kcore",
+    "ppcsr_path_counts", "ppcsr_betweenness", "pppcsr_path_counts", "pppcsr_betweenness",
     "ppcsr_triangles", "pppcsr_triangles", "ppcsr_common_neighbours", "ppcsr_common_neighbours_device", "pppcsr_common_neighbours",
 ]
 
@@ -142,6 +143,10 @@ def load_library(path=None):
         getattr(L, name).argtypes = [c_vp, c_u32, c_vp, ctypes.POINTER(ctypes.c_double)]
     for name in ("ppcsr_components", "pppcsr_components"):
         getattr(L, name).argtypes = [c_vp, c_vp, ctypes.POINTER(ctypes.c_double)]
+    for name in ("ppcsr_path_counts", "pppcsr_path_counts"):
+        getattr(L, name).argtypes = [c_vp, c_u32, c_vp, c_vp, ctypes.POINTER(ctypes.c_double)]
+    for name in ("ppcsr_betweenness", "pppcsr_betweenness"):
+        getattr(L, name).argtypes = [c_vp, c_vp, c_u64, c_vp, ctypes.POINTER(ctypes.c_double)]
     for name in ("ppcsr_kcore", "pppcsr_kcore"):
         getattr(L, name).argtypes = [c_vp, c_vp, ctypes.POINTER(c_u32), ctypes.POINTER(ctypes.c_double)]
     for name in ("ppcsr_triangles", "pppcsr_triangles"):
@@ -272,6 +277,21 @@ class _Consumers:
         """weakly connected components: the smallest vertex id of every vertex's component (uint32)"""
         out = np.empty(self.get_n(), np.uint32)
         ms = self._consumer("components", out.ctypes.data)
+        return (out, ms) if with_ms else out
+
+    def path_counts(self, start, with_ms=False):
+        """(levels, sigma[, ms]): BFS levels from `start` (uint32, 0xFFFFFFFF where unreachable) and the number of shortest
+        directed paths from `start` to every vertex (float64: exact below 2^53, 0 where unreachable)"""
+        levels, sigma = np.empty(self.get_n(), np.uint32), np.empty(self.get_n(), np.float64)
+        ms = self._consumer("path_counts", start, levels.ctypes.data, sigma.ctypes.data)
+        return (levels, sigma, ms) if with_ms else (levels, sigma)
+
+    def betweenness(self, sources, with_ms=False):
+        """Brandes' betweenness from `sources` (float64): directed, endpoints excluded, nothing halved or normalised;
+        range(n) as sources gives exact betweenness"""
+        q = _u32(sources)
+        out = np.empty(self.get_n(), np.float64)
+        ms = self._consumer("betweenness", q.ctypes.data if q.size else None, q.size, out.ctypes.data)
         return (out, ms) if with_ms else out
 
     def triangles(self, per_vertex=True, with_ms=False):

@@ -178,6 +178,19 @@ int ppcsr_components(ppcsr_t h, uint32_t *labels, double *device_ms) {
   const ppcsr::ConsumerRef self{h->e, 0};
   return ret(h->e, h->e->components_over(&self, 1, h->e->n(), labels, device_ms));
 }
+int ppcsr_path_counts(ppcsr_t h, uint32_t start, uint32_t *levels, double *sigma, double *device_ms) {
+  H_CHECK();
+  if (!levels && !sigma) return bad("path_counts: null outputs");
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->path_counts_over(&self, 1, h->e->n(), start, levels, sigma, device_ms));
+}
+int ppcsr_betweenness(ppcsr_t h, const uint32_t *sources, uint64_t k, double *bc, double *device_ms) {
+  H_CHECK();
+  if (!bc) return bad("betweenness: null output");
+  if (!sources && k > 0) return bad("betweenness: null sources");
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->betweenness_over(&self, 1, h->e->n(), sources, k, bc, device_ms));
+}
 int ppcsr_kcore(ppcsr_t h, uint32_t *core, uint32_t *kmax, double *device_ms) {
   H_CHECK();
   if (!core && !kmax) return bad("kcore: null outputs");
@@ -717,6 +730,24 @@ int pppcsr_components(pppcsr_t h, uint32_t *labels, double *device_ms) {
   PP_CHECK();
   if (!labels) return bad("components: null output");
   return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) { return ret(e, e->components_over(r, P, n, labels, device_ms)); });
+}
+int pppcsr_path_counts(pppcsr_t h, uint32_t start, uint32_t *levels, double *sigma, double *device_ms) {
+  PP_CHECK();
+  if (!levels && !sigma) return bad("path_counts: null outputs");
+  return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) {
+    if (start >= n) return bad("path_counts: start vertex out of range");
+    return ret(e, e->path_counts_over(r, P, n, start, levels, sigma, device_ms));
+  });
+}
+int pppcsr_betweenness(pppcsr_t h, const uint32_t *sources, uint64_t k, double *bc, double *device_ms) {
+  PP_CHECK();
+  if (!bc) return bad("betweenness: null output");
+  if (!sources && k > 0) return bad("betweenness: null sources");
+  return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) {
+    for (uint64_t i = 0; i < k; i++)
+      if (sources[i] >= n) return bad("betweenness: source vertex out of range");
+    return ret(e, e->betweenness_over(r, P, n, sources, k, bc, device_ms));
+  });
 }
 int pppcsr_kcore(pppcsr_t h, uint32_t *core, uint32_t *kmax, double *device_ms) {
   PP_CHECK();

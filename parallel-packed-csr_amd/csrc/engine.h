@@ -107,6 +107,14 @@ class Engine {
   // core numbers of the upper-orientation graph triangles counts in (pma_cores.h), in either regime: core (total_n entries,
   // may be null), *kmax (may be null): the largest core number
   int kcore_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t *core, uint32_t *kmax, double *device_ms);
+  // shortest-path counts and betweenness centrality (pma_centrality.h), in either regime.  path_counts: levels as bfs_over
+  // gives them and sigma[v] = number of fewest-edge paths from `start` to v, in fp64 (total_n entries each; either may be
+  // null, not both).  betweenness: bc[v] (total_n entries) = Brandes' dependency of the k sources on v, endpoints
+  // excluded, nothing halved or normalised; a source >= total_n is refused before the first launch.
+  int path_counts_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t start, uint32_t *levels, double *sigma,
+                       double *device_ms);
+  int betweenness_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const uint32_t *sources, uint64_t k, double *bc,
+                       double *device_ms);
   // consumers that intersect two neighbourhoods (pma_intersect.h).  triangles: upper orientation — {a, b}, a < b, is an edge
   // exactly when (a, b) is stored; tri (total_n entries, may be null): triangles through every vertex; *total (may be null):
   // triangles.  common_neighbours: counts[i] = stored dests < total_n shared by a[i] and b[i] (vertices >= total_n: 0); a, b,
@@ -166,6 +174,9 @@ class Engine {
   int scan_count(Engine *part, uint32_t *tile, uint64_t *ntiles);
   int intersect_regime(const ConsumerRef *parts, uint32_t P, const char *what, std::string *msg);
   int consumer_table(const ConsumerRef *parts, uint32_t P, uint32_t total_n, void **d_tab, uint64_t *slots);
+  // what path_counts_over and betweenness_over share: the forward phase from every source and, when bc is wanted, the backward sweep
+  int centrality_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const uint32_t *sources, uint64_t k, uint32_t *levels,
+                      double *sigma, double *bc, double *device_ms);
   void scan_write(Engine *part, uint32_t tile, uint64_t ntiles, unsigned long long *d_rows, int *d_dst, uint64_t cap, const float *d_values,
                   float *d_contrib, Op *d_triples, uint32_t src_base, uint32_t dest_bound);
 

@@ -1,4 +1,4 @@
-// Host drivers of the graph-algorithm consumers (kernels: pma_consumer.h, pma_scan.h, pma_paths.h, pma_cores.h,
+// Host drivers of the graph-algorithm consumers (kernels: pma_consumer.h, pma_scan.h, pma_paths.h, pma_cores.h, pma_centrality.h,
 // pma_intersect.h).  Included at the end of engine.cc: part of the engine's single translation unit, in the library
 // (csrc/ppcsr_hip.hip) and in the emulator (tests/hostsim/ppcsr_sim.cpp) alike.
 namespace ppcsr {
@@ -100,16 +100,19 @@ struct Engine::ConsumerScope {
   // (pass(step)) — its cost does not depend on hub degrees — and the list is rebuilt from d_key (levels / stamps: the
   // frontier is { v : key[v] == step }) only when the frontier becomes small again.  One host read per step.
   // reread_list: the pass's count is an upper bound (BFS counts claims), so the exact length is read back with the list;
-  // an exact count (SSSP: the stamp admits each vertex once) is not read again.
+  // an exact count (SSSP: the stamp admits each vertex once) is not read again.  sizes (may be null): the frontier size of
+  // every step is appended to it — exact where the count is.
+  static uint32_t hybrid_big(uint32_t nn) { return (uint32_t)std::max<uint64_t>(64, (uint64_t)nn / 256); }
   template <class Pass, class PerVertex>
   int hybrid(uint32_t nn, const uint32_t *d_key, uint32_t step, uint32_t *d_f0, uint32_t *d_f1, uint32_t *d_cnt, bool reread_list, Pass pass,
-             PerVertex per_vertex) {
+             PerVertex per_vertex, std::vector<uint32_t> *sizes = nullptr) {
     uint32_t nfront = 1;
     uint32_t *cur = d_f0, *nxt = d_f1;
     std::vector<uint32_t> h_cnt(kHybridCntWords, 0);
     bool have_list = true;
-    const uint32_t big = (uint32_t)std::max<uint64_t>(64, (uint64_t)nn / 256);  // frontier size from which the pass is cheaper
+    const uint32_t big = hybrid_big(nn);  // frontier size from which the pass is cheaper
     for (; nfront > 0; step++) {
+      if (sizes) sizes->push_back(nfront);
       GCHK(gpu::dset(d_cnt, 0, kHybridCntWords * sizeof(uint32_t), p.stream));
       if (nfront >= big) {
         pass(step);
@@ -140,6 +143,32 @@ struct Engine::ConsumerScope {
       }
       nfront = h_cnt[0];
       for (uint32_t k = 1; k <= kBfsStripes; k++) nfront += h_cnt[k * kBfsStripeWords];
+    }
+    return PPCSR_OK;
+  }
+
+  // The loop of a sweep BACK over levels whose sizes a hybrid() run recorded: from the last level but one down to level 0,
+  // the same choice per level.  A level of at least hybrid_big vertices takes one streaming pass (pass(level, false)); a
+  // smaller one is listed from d_key (k_bfs_collect) and handled one wave per vertex (per_vertex(list, count, level)), and if
+  // that launch left hubs behind (d_cnt[1]) one pass over those alone finishes the level (pass(level, true)).  One host read
+  // per small level.
+  template <class Pass, class PerVertex>
+  int sweep_back(uint32_t nn, const uint32_t *d_key, const std::vector<uint32_t> &sizes, uint32_t *d_list, uint32_t *d_cnt, Pass pass,
+                 PerVertex per_vertex) {
+    const uint32_t big = hybrid_big(nn);
+    uint32_t h_cnt[2] = {0, 0};
+    for (uint64_t level = sizes.size() - 1; level-- > 0;) {
+      if (sizes[level] >= big) {
+        pass((uint32_t)level, false);
+        continue;
+      }
+      GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), p.stream));
+      GPU_LAUNCH(p.stream, k_bfs_collect, grid_for(nn, 256), 256, d_key, nn, (uint32_t)level, d_list, d_cnt);
+      per_vertex((const uint32_t *)d_list, sizes[level], (uint32_t)level);
+      GCHK(gpu::d2h(h_cnt, d_cnt, 2 * sizeof(uint32_t), p.stream));
+      GCHK(gpu::sync(p.stream));
+      GCHK(gpu::last_error());
+      if (h_cnt[1]) pass((uint32_t)level, true);
     }
     return PPCSR_OK;
   }
@@ -252,6 +281,93 @@ int Engine::components_over(const ConsumerRef *parts, uint32_t P, uint32_t total
   cs.stop();
   if (nn) GCHK(gpu::d2h(labels, d_lab, (uint64_t)nn * sizeof(uint32_t), p.stream));
   return cs.done(device_ms);
+}
+
+// Shortest-path counts and betweenness centrality (pma_centrality.h).  Per source: the hybrid loop as in bfs_over, with the
+// claims counted exactly (reread_list = false) and the size of every level kept; then, for betweenness, sweep_back over those
+// levels and one launch that adds delta into bc.  The pass that finishes a per-vertex launch must not repeat what that launch
+// has added: the launch stamps the hubs it skips with its own number (d_hub, never reset: numbers are not reused within a
+// call) and the pass takes exactly those as its sources.  One host read per level forward, one per small level backward,
+// one D2H of the results at the end.
+int Engine::centrality_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const uint32_t *sources, uint64_t k, uint32_t *levels,
+                            double *sigma, double *bc, double *device_ms) {
+  const uint32_t nn = total_n;
+  ConsumerScope cs(this);
+  int rc = cs.open(parts, P, nn);
+  if (rc != PPCSR_OK) return rc;
+  Impl &p = *p_;
+  const ConsumerPart *tab = cs.table();
+  const uint64_t N = cs.slots();
+  const uint64_t words = std::max<uint64_t>(nn, 1);
+  const uint64_t bit_words = std::max<uint64_t>(((uint64_t)nn + 63) / 64 * 2, 2);  // source / placed bitmaps of the streaming passes
+  uint32_t *d_sb = cs.alloc<uint32_t>("d_sb", bit_words), *d_pb = cs.alloc<uint32_t>("d_pb", bit_words);
+  uint32_t *d_lv = cs.alloc<uint32_t>("d_lv", words), *d_hub = cs.alloc<uint32_t>("d_hub", words);
+  uint32_t *d_f0 = cs.alloc<uint32_t>("d_f0", words), *d_f1 = cs.alloc<uint32_t>("d_f1", words);
+  double *d_sigma = cs.alloc<double>("d_sigma", words);
+  double *d_delta = bc ? cs.alloc<double>("d_delta", words) : nullptr, *d_bc = bc ? cs.alloc<double>("d_bc", words) : nullptr;
+  uint32_t *d_cnt = cs.alloc<uint32_t>("d_cnt", kHybridCntWords);
+  if (cs.rc != PPCSR_OK) return cs.rc;
+  cs.start();
+  GCHK(gpu::dset(d_hub, 0xFF, words * sizeof(uint32_t), p.stream));  // (kBcNoStamp: no launch has this number)
+  if (bc) GCHK(gpu::dset(d_bc, 0, words * sizeof(double), p.stream));
+  uint32_t stamp = 0;  // number of the last per-vertex launch
+  std::vector<uint32_t> sizes;
+  const auto bits = [&](uint32_t level, bool hubs_only) {
+    GPU_LAUNCH(p.stream, k_bc_bits, grid_for(nn, 256, 4096), 256, (const uint32_t *)d_lv, (const uint32_t *)d_hub, nn, level,
+               hubs_only ? stamp : kBcNoStamp, d_sb, d_pb);
+  };
+  for (uint64_t i = 0; i < k; i++) {
+    const uint32_t s = sources[i];
+    GPU_LAUNCH(p.stream, k_bc_init, grid_for(nn, 256, 4096), 256, d_lv, d_sigma, d_delta, nn, s, d_f0);
+    sizes.clear();
+    uint32_t pv_level = kBcNoStamp;  // level of the last per-vertex launch: a pass for the same level finishes it
+    rc = cs.hybrid(
+        nn, d_lv, 0, d_f0, d_f1, d_cnt, false,
+        [&](uint32_t level) {
+          bits(level, level == pv_level);
+          GPU_LAUNCH(p.stream, k_bc_edges_forward, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, level, (const uint32_t *)d_sb,
+                     (const uint32_t *)d_pb, d_lv, d_sigma, d_cnt + kBfsStripeWords);
+        },
+        [&](const uint32_t *cur, uint32_t nfront, uint32_t level, uint32_t *nxt) {
+          pv_level = level;
+          stamp++;
+          GPU_LAUNCH(p.stream, k_bc_level, grid_for(nfront, 4, 16384), 256, tab, P, nn, cur, nfront, level, d_lv, d_sigma, d_hub, stamp, nxt,
+                     d_cnt);
+        },
+        &sizes);
+    if (rc != PPCSR_OK) return rc;
+    if (!bc) continue;
+    rc = cs.sweep_back(
+        nn, d_lv, sizes, d_f0, d_cnt,
+        [&](uint32_t level, bool hubs_only) {
+          bits(level, hubs_only);
+          GPU_LAUNCH(p.stream, k_bc_edges_backward, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, level, (const uint32_t *)d_sb,
+                     (const uint32_t *)d_lv, (const double *)d_sigma, d_delta);
+        },
+        [&](const uint32_t *list, uint32_t nlist, uint32_t level) {
+          stamp++;
+          GPU_LAUNCH(p.stream, k_bc_delta_vertex, grid_for(nlist, 4, 16384), 256, tab, P, nn, list, nlist, level, (const uint32_t *)d_lv,
+                     (const double *)d_sigma, d_delta, d_hub, stamp, d_cnt);
+        });
+    if (rc != PPCSR_OK) return rc;
+    GPU_LAUNCH(p.stream, k_bc_accumulate, grid_for(nn, 256, 4096), 256, d_bc, (const double *)d_delta, nn, s);
+  }
+  cs.stop();
+  if (levels && nn) GCHK(gpu::d2h(levels, d_lv, (uint64_t)nn * sizeof(uint32_t), p.stream));
+  if (sigma && nn) GCHK(gpu::d2h(sigma, d_sigma, (uint64_t)nn * sizeof(double), p.stream));
+  if (bc && nn) GCHK(gpu::d2h(bc, d_bc, (uint64_t)nn * sizeof(double), p.stream));
+  return cs.done(device_ms);
+}
+int Engine::path_counts_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t start, uint32_t *levels, double *sigma,
+                             double *device_ms) {
+  if (start >= total_n) return fail(PPCSR_EINVAL, "path_counts: start vertex out of range");
+  return centrality_over(parts, P, total_n, &start, 1, levels, sigma, nullptr, device_ms);
+}
+int Engine::betweenness_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const uint32_t *sources, uint64_t k, double *bc,
+                             double *device_ms) {
+  for (uint64_t i = 0; i < k; i++)
+    if (sources[i] >= total_n) return fail(PPCSR_EINVAL, "betweenness: source vertex out of range");
+  return centrality_over(parts, P, total_n, sources, k, nullptr, nullptr, bc, device_ms);
 }
 
 // Core numbers (pma_cores.h).  Stage 1 exports the upper-orientation graph as a compact symmetric adjacency (degree pass,
