@@ -185,6 +185,31 @@ int ppcsr_betweenness(ppcsr_t h, const uint32_t *sources, uint64_t k, double *bc
  * intersect sorted ranges, so — as components, and unlike triangles — it also answers in the sequential regime
  * (stats.narrow == 0).  EINVAL: null handle, core and kmax both NULL. */
 int ppcsr_kcore(ppcsr_t h, uint32_t *core, uint32_t *kmax, double *device_ms);
+/* Strongly connected components, over exactly the edge set ppcsr_bfs walks (live non-sentinel slots, slot N - 1 excluded, local
+ * src < n, destinations >= n skipped), taken as DIRECTED; the edge values play no part.  A self-loop is an ordinary stored edge
+ * that changes nothing: a vertex whose only cycle is its self-loop is an SCC of one vertex.
+ * scc — labels[v] = the smallest vertex id of v's SCC (n entries, may be NULL): the convention of ppcsr_components, so the two
+ *   label arrays compare directly and the SCC labels refine the WCC labels.  *count = the number of SCCs = the number of v with
+ *   labels[v] == v; 0 for n = 0 (may be NULL, not both).
+ * Both results are unique.  Same contract as components: synchronous on the engine's stream, sees every batch applied before
+ * it, writes nothing to the graph (state, stats, dirty tags and snapshot unchanged), device_ms may be NULL.  The call intersects
+ * nothing and takes every edge's source from the item itself, so — as components and kcore — it also answers in the
+ * sequential regime (stats.narrow == 0).  The number of passes over the array grows with the longest chain of the graph (a
+ * directed path of L vertices: about L / 2 trim sweeps; a cycle of L vertices: up to L passes).  EINVAL: null handle, labels
+ * and count both NULL. */
+int ppcsr_scc(ppcsr_t h, uint32_t *labels, uint64_t *count, double *device_ms);
+/* Debugging: what the last scc call on this engine did — for a pppcsr_scc call the engine that ran it, the first partition's
+ * (pppcsr_partition).  Kept on the host and always on: no launch, copy or synchronisation is added for it; all zeros before
+ * the first call.  The phases cover for each other (whatever trimming or the pivot leave, colouring still labels), so label
+ * parity alone cannot show that a phase works; these can.
+ *   out[0] vertices labelled by trimming            out[1] trim sweeps
+ *   out[2] the pivot's global id (UINT64_MAX when the forward-backward phase did not run)
+ *   out[3] vertices labelled by the forward-backward phase
+ *   out[4] colouring rounds                         out[5] vertices labelled by colouring
+ *   out[6] streaming passes over the arrays, all phases together
+ *   out[7] host reads (stream synchronisations inside the timed region)
+ * EINVAL: null handle or out. */
+int ppcsr_debug_scc_counters(ppcsr_t h, uint64_t out[8]);
 /* Two consumers that intersect two neighbourhoods, over the same edge set (live slots of every vertex's (beginning, end), slot
  * N - 1 excluded, destinations >= n skipped; a (src, dst) pair is stored at most once).  A vertex's live slots lie in
  * ascending destination order, so the neighbourhoods are intersected in place: no export, no sort.
@@ -371,6 +396,11 @@ int pppcsr_components(pppcsr_t h, uint32_t *labels, double *device_ms);
  * pppcsr_components; a partition in the sequential regime is answered.  EINVAL: null handle, core and kmax both NULL, or a
  * partition not resident in this process.  EUNSUPPORTED: the partitions sit on more than one device. */
 int pppcsr_kcore(pppcsr_t h, uint32_t *core, uint32_t *kmax, double *device_ms);
+/* ppcsr_scc over the GLOBAL vertex ids (labels: pppcsr_get_n entries), one device call over every partition's array: an SCC may
+ * span partitions, and the result does not depend on the partitioning.  Same contract as pppcsr_components; a partition in the
+ * sequential regime is answered.  EINVAL: null handle, labels and count both NULL, or a partition not resident in this
+ * process.  EUNSUPPORTED: the partitions sit on more than one device. */
+int pppcsr_scc(pppcsr_t h, uint32_t *labels, uint64_t *count, double *device_ms);
 /* ppcsr_path_counts / ppcsr_betweenness over the GLOBAL vertex ids (start, sources; levels, sigma, bc: pppcsr_get_n entries),
  * one device call over every partition's array: path_counts does not depend on the partitioning, betweenness only within its
  * error bound (the order of the sums differs).  Same contract as pppcsr_sssp; a partition in the sequential regime is

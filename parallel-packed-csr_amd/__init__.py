@@ -74,6 +74,7 @@ EXPORTED = [
     "pppcsr_bfs", "pppcsr_pagerank", "ppcsr_sssp", "ppcsr_components", "pppcsr_sssp", "pppcsr_components",
     "ppcsr_debug_chain_probe", "ppcsr_debug_isect_probe", "ppcsr_kcore", "pppcsr_kcore",
     "ppcsr_path_counts", "ppcsr_betweenness", "pppcsr_path_counts", "pppcsr_betweenness",
+    "ppcsr_scc", "pppcsr_scc", "ppcsr_debug_scc_counters",
     "ppcsr_triangles", "pppcsr_triangles", "ppcsr_common_neighbours", "ppcsr_common_neighbours_device", "pppcsr_common_neighbours",
 ]
 
@@ -149,6 +150,9 @@ def load_library(path=None):
         getattr(L, name).argtypes = [c_vp, c_vp, c_u64, c_vp, ctypes.POINTER(ctypes.c_double)]
     for name in ("ppcsr_kcore", "pppcsr_kcore"):
         getattr(L, name).argtypes = [c_vp, c_vp, ctypes.POINTER(c_u32), ctypes.POINTER(ctypes.c_double)]
+    for name in ("ppcsr_scc", "pppcsr_scc"):
+        getattr(L, name).argtypes = [c_vp, c_vp, ctypes.POINTER(c_u64), ctypes.POINTER(ctypes.c_double)]
+    L.ppcsr_debug_scc_counters.argtypes = [c_vp, c_vp]
     for name in ("ppcsr_triangles", "pppcsr_triangles"):
         getattr(L, name).argtypes = [c_vp, c_vp, ctypes.POINTER(c_u64), ctypes.POINTER(ctypes.c_double)]
     for name in ("ppcsr_common_neighbours", "ppcsr_common_neighbours_device", "pppcsr_common_neighbours"):
@@ -310,6 +314,14 @@ class _Consumers:
         ms = self._consumer("kcore", core.ctypes.data, ctypes.byref(kmax))
         return (core, kmax.value, ms) if with_ms else (core, kmax.value)
 
+    def scc(self, with_ms=False):
+        """(labels, count[, ms]): strongly connected components of the stored DIRECTED graph: the smallest vertex id of every
+        vertex's SCC (uint32, global ids: the convention of components()) and the number of SCCs"""
+        labels = np.empty(self.get_n(), np.uint32)
+        count = c_u64()
+        ms = self._consumer("scc", labels.ctypes.data, ctypes.byref(count))
+        return (labels, count.value, ms) if with_ms else (labels, count.value)
+
     def common_neighbours(self, a, b, with_ms=False):
         """counts[i] = stored destinations < n that a[i] and b[i] share (uint32; vertices >= n give 0)"""
         a, b = _u32(a), _u32(b)
@@ -470,6 +482,13 @@ class PCSR(_Consumers):
         out = np.zeros(6, np.uint64)
         self._chk(self.L.ppcsr_debug_snap_counters(self.h, out.ctypes.data))
         return dict(zip(("full_saves", "full_loads", "inc_commits", "inc_rollbacks", "leaves_copied", "nodes_copied"), (int(x) for x in out)))
+
+    def debug_scc_counters(self):
+        """Debugging (ppcsr_debug_scc_counters): uint64[8] of the last scc call on this engine — vertices trimmed, trim sweeps,
+        the pivot (2^64 - 1: none), vertices of its SCC, colouring rounds, vertices coloured, streaming passes, host reads"""
+        out = np.zeros(8, np.uint64)
+        self._chk(self.L.ppcsr_debug_scc_counters(self.h, out.ctypes.data))
+        return out
 
     def check_invariants(self):
         bad = c_u64()
@@ -644,6 +663,10 @@ class PPPCSR(_Consumers):
         out = c_vp()
         self._chk(self.L.pppcsr_partition(self.h, k, ctypes.byref(out)))
         return PCSR(0, lib=self.L, _handle=out.value)
+
+    def debug_scc_counters(self):
+        """the counters of the last scc call: kept by the engine that ran it, the first partition's"""
+        return self.partition(0).debug_scc_counters()
 
     def add_edge(self, s, d, v=1): self._chk(self.L.pppcsr_add_edge(self.h, s, d, v))
     def remove_edge(self, s, d): self._chk(self.L.pppcsr_remove_edge(self.h, s, d))

@@ -197,6 +197,13 @@ int ppcsr_kcore(ppcsr_t h, uint32_t *core, uint32_t *kmax, double *device_ms) {
   const ppcsr::ConsumerRef self{h->e, 0};
   return ret(h->e, h->e->kcore_over(&self, 1, h->e->n(), core, kmax, device_ms));
 }
+int ppcsr_scc(ppcsr_t h, uint32_t *labels, uint64_t *count, double *device_ms) {
+  H_CHECK();
+  if (!labels && !count) return bad("scc: null outputs");
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->scc_over(&self, 1, h->e->n(), labels, count, device_ms));
+}
+int ppcsr_debug_scc_counters(ppcsr_t h, uint64_t out[8]) { H_CHECK(); return ret(h->e, h->e->scc_counters(out)); }
 int ppcsr_triangles(ppcsr_t h, uint64_t *tri, uint64_t *total, double *device_ms) {
   H_CHECK();
   if (!tri && !total) return bad("triangles: null outputs");
@@ -753,6 +760,11 @@ int pppcsr_kcore(pppcsr_t h, uint32_t *core, uint32_t *kmax, double *device_ms) 
   PP_CHECK();
   if (!core && !kmax) return bad("kcore: null outputs");
   return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) { return ret(e, e->kcore_over(r, P, n, core, kmax, device_ms)); });
+}
+int pppcsr_scc(pppcsr_t h, uint32_t *labels, uint64_t *count, double *device_ms) {
+  PP_CHECK();
+  if (!labels && !count) return bad("scc: null outputs");
+  return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) { return ret(e, e->scc_over(r, P, n, labels, count, device_ms)); });
 }
 int pppcsr_triangles(pppcsr_t h, uint64_t *tri, uint64_t *total, double *device_ms) {
   PP_CHECK();

@@ -107,6 +107,11 @@ class Engine {
   // core numbers of the upper-orientation graph triangles counts in (pma_cores.h), in either regime: core (total_n entries,
   // may be null), *kmax (may be null): the largest core number
   int kcore_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t *core, uint32_t *kmax, double *device_ms);
+  // strongly connected components (pma_scc.h), in either regime: labels[v] = smallest vertex id of v's SCC (total_n entries, may
+  // be null), *count = number of SCCs (may be null).  scc_counters: what the last scc_over on this engine did
+  // (ppcsr_debug_scc_counters, include/ppcsr.h)
+  int scc_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t *labels, uint64_t *count, double *device_ms);
+  int scc_counters(uint64_t out[8]);
   // shortest-path counts and betweenness centrality (pma_centrality.h), in either regime.  path_counts: levels as bfs_over
   // gives them and sigma[v] = number of fewest-edge paths from `start` to v, in fp64 (total_n entries each; either may be
   // null, not both).  betweenness: bc[v] (total_n entries) = Brandes' dependency of the k sources on v, endpoints

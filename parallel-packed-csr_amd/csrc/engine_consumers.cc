@@ -1,5 +1,5 @@
 // Host drivers of the graph-algorithm consumers (kernels: pma_consumer.h, pma_scan.h, pma_paths.h, pma_cores.h, pma_centrality.h,
-// pma_intersect.h).  Included at the end of engine.cc: part of the engine's single translation unit, in the library
+// pma_scc.h, pma_intersect.h).  Included at the end of engine.cc: part of the engine's single translation unit, in the library
 // (csrc/ppcsr_hip.hip) and in the emulator (tests/hostsim/ppcsr_sim.cpp) alike.
 namespace ppcsr {
 
@@ -447,6 +447,169 @@ int Engine::kcore_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, u
   if (core && nn) GCHK(gpu::d2h(core, d_core, (uint64_t)nn * sizeof(uint32_t), p.stream));
   if (kmax) *kmax = top;
   return cs.done(device_ms);
+}
+
+// Strongly connected components (pma_scc.h): trim to a fixpoint, forward-backward reach from one pivot, then colouring rounds
+// while anything is live, the trim again after each.  Every streaming pass costs one host read of the striped counters (the
+// loop conditions); the counters of ppcsr_debug_scc_counters are kept on the host from those same reads.  Every loop is
+// bounded by what it retires or marks, so a pass count beyond the vertex count is reported as an error instead of spinning.
+int Engine::scc_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t *labels, uint64_t *count, double *device_ms) {
+  const uint32_t nn = total_n;
+  ConsumerScope cs(this);
+  const int rc = cs.open(parts, P, nn);
+  if (rc != PPCSR_OK) return rc;
+  Impl &p = *p_;
+  const ConsumerPart *tab = cs.table();
+  const uint64_t N = cs.slots();
+  const uint64_t words = std::max<uint64_t>(nn, 1);
+  const uint64_t bit_words = std::max<uint64_t>(((uint64_t)nn + 63) / 64 * 2, 2);
+  constexpr uint32_t cnt_words = kBfsStripes * kSccStripeWords;
+  uint32_t *d_scc = cs.alloc<uint32_t>("d_scc", words), *d_col = cs.alloc<uint32_t>("d_col", words), *d_live = cs.alloc<uint32_t>("d_live", bit_words);
+  uint8_t *d_out = cs.alloc<uint8_t>("d_out", words), *d_in = cs.alloc<uint8_t>("d_in", words);  // has_out / has_in of a trim sweep
+  uint8_t *d_fw = cs.alloc<uint8_t>("d_fw", words), *d_bw = cs.alloc<uint8_t>("d_bw", words);    // marks of a reach
+  unsigned long long *d_cnt = cs.alloc<unsigned long long>("d_cnt", cnt_words);
+  unsigned long long *d_aux = cs.alloc<unsigned long long>("d_aux", 2);  // [0]: the pivot's key, [1]: the label of its SCC (low word)
+  if (cs.rc != PPCSR_OK) return cs.rc;
+  std::vector<unsigned long long> h_cnt(cnt_words, 0);
+  uint64_t ctr[8] = {0, 0, UINT64_MAX, 0, 0, 0, 0, 0};
+  uint64_t &passes = ctr[6], &reads = ctr[7];
+  uint64_t live = nn, sccs = 0;
+  const uint32_t pass_grid = grid_for((N + 255) / 256, 4, 8192), vert_grid = grid_for(nn, 256, 4096);
+  // the striped count of the launches since zero(): low and high halves summed apart (k_scc_reach_*)
+  const auto zero = [&]() { return gpu::dset(d_cnt, 0, cnt_words * sizeof(unsigned long long), p.stream); };
+  const auto read = [&](uint64_t *lo, uint64_t *hi) {
+    GCHK(gpu::d2h(h_cnt.data(), d_cnt, cnt_words * sizeof(unsigned long long), p.stream));
+    GCHK(gpu::sync(p.stream));
+    GCHK(gpu::last_error());
+    reads++;
+    *lo = *hi = 0;
+    for (uint32_t k = 0; k < kBfsStripes; k++) {
+      *lo += h_cnt[(uint64_t)k * kSccStripeWords] & 0xFFFFFFFFull;
+      *hi += h_cnt[(uint64_t)k * kSccStripeWords] >> 32;
+    }
+    return (int)PPCSR_OK;
+  };
+  const auto spinning = [&]() { return fail(PPCSR_EHIP, "scc: a loop made more passes than the graph has vertices"); };
+  const auto trim = [&]() {
+    for (uint64_t sweep = 0, got = 1, hi = 0; live > 0 && got > 0; sweep++) {
+      if (sweep > (uint64_t)nn + 1) return spinning();
+      GCHK(zero());
+      GPU_LAUNCH(p.stream, k_scc_trim_edges, pass_grid, 256, tab, P, nn, (const uint32_t *)d_live, d_out, d_in);
+      GPU_LAUNCH(p.stream, k_scc_trim_retire, vert_grid, 256, d_scc, nn, d_out, d_in, d_live, d_cnt);
+      passes++;
+      ctr[1]++;
+      const int e = read(&got, &hi);
+      if (e != PPCSR_OK) return e;
+      ctr[0] += got;
+      live -= got;
+    }
+    return (int)PPCSR_OK;
+  };
+  cs.start();
+  if (nn) {
+    GCHK(gpu::dset(d_scc, 0xFF, words * sizeof(uint32_t), p.stream));
+    GCHK(gpu::dset(d_live, 0xFF, bit_words * sizeof(uint32_t), p.stream));
+    GCHK(gpu::dset(d_out, 0, words, p.stream));
+    GCHK(gpu::dset(d_in, 0, words, p.stream));
+    int e = trim();
+    if (e != PPCSR_OK) return e;
+    if (live > 0) {  // forward-backward from the pivot
+      unsigned long long h_aux[2] = {0, 0xFFFFFFFFull};
+      GCHK(gpu::h2d(d_aux, h_aux, sizeof(h_aux), p.stream));
+      GPU_LAUNCH(p.stream, k_scc_pivot, grid_for(nn, 256, 512), 256, tab, P, nn, (const uint32_t *)d_live, d_aux);
+      GPU_LAUNCH(p.stream, k_scc_marks, vert_grid, 256, (const uint32_t *)d_scc, nn, (const uint32_t *)nullptr, d_fw, d_bw);
+      GCHK(gpu::d2h(h_aux, d_aux, sizeof(unsigned long long), p.stream));
+      GCHK(gpu::sync(p.stream));
+      GCHK(gpu::last_error());
+      reads++;
+      const uint32_t pivot = 0xFFFFFFFFu - (uint32_t)h_aux[0];
+      if (h_aux[0] == 0 || pivot >= nn) return fail(PPCSR_EHIP, "scc: no pivot among the live vertices");
+      ctr[2] = pivot;
+      const uint8_t marked = kSccMarked;
+      GCHK(gpu::h2d(d_fw + pivot, &marked, 1, p.stream));
+      GCHK(gpu::h2d(d_bw + pivot, &marked, 1, p.stream));
+      bool fw_open = true, bw_open = true;
+      for (uint64_t it = 0; fw_open || bw_open; it++) {
+        if (it > (uint64_t)nn + 1) return spinning();
+        GCHK(zero());
+        if (fw_open && bw_open)
+          GPU_LAUNCH(p.stream, k_scc_reach_both, pass_grid, 256, tab, P, nn, d_fw, d_bw, d_cnt);
+        else if (fw_open)
+          GPU_LAUNCH(p.stream, k_scc_reach_fw, pass_grid, 256, tab, P, nn, d_fw, d_cnt);
+        else
+          GPU_LAUNCH(p.stream, k_scc_reach_bw, pass_grid, 256, tab, P, nn, d_bw, d_cnt);
+        passes++;
+        uint64_t f = 0, b = 0;
+        e = read(&f, &b);
+        if (e != PPCSR_OK) return e;
+        fw_open = fw_open && f > 0;
+        bw_open = bw_open && b > 0;
+      }
+      GCHK(zero());
+      GPU_LAUNCH(p.stream, k_scc_min, grid_for(nn, 256, 512), 256, (const uint8_t *)d_fw, (const uint8_t *)d_bw, nn, (uint32_t *)(d_aux + 1));
+      GPU_LAUNCH(p.stream, k_scc_assign, vert_grid, 256, (const uint8_t *)d_fw, (const uint8_t *)d_bw, nn, (const uint32_t *)nullptr,
+                 (const uint32_t *)(d_aux + 1), d_scc, d_live, d_cnt);
+      uint64_t got = 0, hi = 0;
+      e = read(&got, &hi);
+      if (e != PPCSR_OK) return e;
+      if (got == 0 || got > live) return fail(PPCSR_EHIP, "scc: the pivot's component came out empty");
+      ctr[3] = got;
+      live -= got;
+      e = trim();
+      if (e != PPCSR_OK) return e;
+    }
+    while (live > 0) {  // one colouring round
+      ctr[4]++;
+      GPU_LAUNCH(p.stream, k_scc_colour_init, vert_grid, 256, (const uint32_t *)d_scc, nn, d_col);
+      for (uint64_t it = 0, got = 1, hi = 0; got > 0; it++) {
+        if (it > (uint64_t)nn + 1) return spinning();
+        GCHK(zero());
+        GPU_LAUNCH(p.stream, k_scc_colour_prop, pass_grid, 256, tab, P, nn, (const uint32_t *)d_live, d_col, d_cnt);
+        passes++;
+        e = read(&got, &hi);
+        if (e != PPCSR_OK) return e;
+      }
+      GPU_LAUNCH(p.stream, k_scc_marks, vert_grid, 256, (const uint32_t *)d_scc, nn, (const uint32_t *)d_col, (uint8_t *)nullptr, d_bw);
+      for (uint64_t it = 0, lo = 0, got = 1; got > 0; it++) {
+        if (it > (uint64_t)nn + 1) return spinning();
+        GCHK(zero());
+        GPU_LAUNCH(p.stream, k_scc_reach_colour, pass_grid, 256, tab, P, nn, (const uint32_t *)d_col, d_bw, d_cnt);
+        passes++;
+        e = read(&lo, &got);
+        if (e != PPCSR_OK) return e;
+      }
+      GCHK(zero());
+      GPU_LAUNCH(p.stream, k_scc_assign, vert_grid, 256, (const uint8_t *)nullptr, (const uint8_t *)d_bw, nn, (const uint32_t *)d_col,
+                 (const uint32_t *)nullptr, d_scc, d_live, d_cnt);
+      uint64_t got = 0, hi = 0;
+      e = read(&got, &hi);
+      if (e != PPCSR_OK) return e;
+      if (got == 0 || got > live) return fail(PPCSR_EHIP, "scc: a colouring round retired nothing");
+      ctr[5] += got;
+      live -= got;
+      e = trim();
+      if (e != PPCSR_OK) return e;
+    }
+    if (count) {
+      GCHK(zero());
+      GPU_LAUNCH(p.stream, k_scc_count, vert_grid, 256, (const uint32_t *)d_scc, nn, d_cnt);
+      uint64_t hi = 0;
+      e = read(&sccs, &hi);
+      if (e != PPCSR_OK) return e;
+    }
+  }
+  cs.stop();
+  if (labels && nn) GCHK(gpu::d2h(labels, d_scc, (uint64_t)nn * sizeof(uint32_t), p.stream));
+  const int done = cs.done(device_ms);
+  if (done != PPCSR_OK) return done;
+  if (count) *count = sccs;
+  for (int i = 0; i < 8; i++) p.scc_ctr[i] = ctr[i];
+  return PPCSR_OK;
+}
+int Engine::scc_counters(uint64_t out[8]) {
+  if (!out) return fail(PPCSR_EINVAL, "scc counters: no output");
+  for (int i = 0; i < 8; i++) out[i] = p_->scc_ctr[i];
+  return PPCSR_OK;
 }
 
 // Triangle counts (pma_intersect.h): one pass over every chunk, then the chunks that hold an edge with a long range again
