@@ -210,6 +210,35 @@ int ppcsr_scc(ppcsr_t h, uint32_t *labels, uint64_t *count, double *device_ms);
  *   out[7] host reads (stream synchronisations inside the timed region)
  * EINVAL: null handle or out. */
 int ppcsr_debug_scc_counters(ppcsr_t h, uint64_t out[8]);
+/* Minimum spanning forest over the edge VALUES, over the edge set ppcsr_components hooks (live non-sentinel slots, slot N - 1
+ * excluded, local src < n, destinations >= n skipped; self-loops play no part).  Every stored pair (a, b), a != b, with value w
+ * is one edge {a, b} of weight w of an undirected MULTIGRAPH: if (a, b) and (b, a) are both stored they are two parallel edges,
+ * whose weights may differ.  The weight is the stored value, in [1, 2^32 - 2]; a duplicate add has overwritten it (last add wins).
+ * The key of an edge is (w, lo, hi), lo = min(a, b), hi = max(a, b), compared lexicographically; two edges with the same key are
+ * the two directions of one pair stored with equal values and count as one.  Under this strict order the minimum spanning
+ * forest is UNIQUE as a set of keys, and so is everything returned.
+ * msf — edges: the forest's edges as (src = lo, dest = hi, value = w), ascending by (lo, hi); at most cap are written and ERANGE
+ *   is returned when edges != NULL and cap < *count (as ppcsr_scan_all), the other outputs still delivered (may be NULL).
+ *   *count = the number of forest edges = n - (number of components) (may be NULL).  *weight = the sum of the forest's weights,
+ *   64-bit: (n - 1)(2^32 - 2) < 2^64, nothing saturates (may be NULL).  labels[v] = the smallest vertex id of v's tree, n
+ *   entries: exactly what ppcsr_components returns (may be NULL).  Not all four may be NULL.  n = 0 or no edges: count = 0,
+ *   weight = 0.
+ * Same contract as components / kcore / scc: synchronous on the engine's stream, sees every batch applied before it, writes
+ * nothing to the graph (state, stats, dirty tags and snapshot unchanged), device_ms may be NULL.  The call intersects nothing and
+ * takes every edge's source from the item itself, so it also answers in the sequential regime (stats.narrow == 0).  Boruvka
+ * rounds over the arrays in place: at most floor(log2 n) + 1 rounds of two streaming passes.  EINVAL: null handle, all four
+ * outputs NULL. */
+int ppcsr_msf(ppcsr_t h, ppcsr_edge *edges, uint64_t cap, uint64_t *count, uint64_t *weight, uint32_t *labels, double *device_ms);
+/* Debugging: what the last msf call on this engine did — for a pppcsr_msf call the engine that ran it, the first partition's
+ * (pppcsr_partition).  Kept on the host from the reads the loop makes anyway and always on; all zeros before the first call.
+ *   out[0] rounds: a round is one search for every component's lightest cut edge; the last round finds none
+ *   out[1] streaming passes over the arrays: 2 * out[0] - 1 for n > 0 (the last round makes the first of its two passes only)
+ *   out[2] pointer-jump launches, all rounds together          out[3] the most pointer-jump launches in one round
+ *   out[4] components hooked in the first round                out[5] forest edges = the sum of hooks over all rounds
+ *   out[6] components at the end
+ *   out[7] host reads (stream synchronisations inside the timed region)
+ * EINVAL: null handle or out. */
+int ppcsr_debug_msf_counters(ppcsr_t h, uint64_t out[8]);
 /* Two consumers that intersect two neighbourhoods, over the same edge set (live slots of every vertex's (beginning, end), slot
  * N - 1 excluded, destinations >= n skipped; a (src, dst) pair is stored at most once).  A vertex's live slots lie in
  * ascending destination order, so the neighbourhoods are intersected in place: no export, no sort.
@@ -401,6 +430,11 @@ int pppcsr_kcore(pppcsr_t h, uint32_t *core, uint32_t *kmax, double *device_ms);
  * sequential regime is answered.  EINVAL: null handle, labels and count both NULL, or a partition not resident in this
  * process.  EUNSUPPORTED: the partitions sit on more than one device. */
 int pppcsr_scc(pppcsr_t h, uint32_t *labels, uint64_t *count, double *device_ms);
+/* ppcsr_msf over the GLOBAL vertex ids (edges' src / dest; labels: pppcsr_get_n entries), one device call over every partition's
+ * array: a forest edge may join two partitions, and NO output depends on the partitioning.  Same contract as
+ * pppcsr_components; a partition in the sequential regime is answered.  EINVAL: null handle, all four outputs NULL, or a
+ * partition not resident in this process.  EUNSUPPORTED: the partitions sit on more than one device. */
+int pppcsr_msf(pppcsr_t h, ppcsr_edge *edges, uint64_t cap, uint64_t *count, uint64_t *weight, uint32_t *labels, double *device_ms);
 /* ppcsr_path_counts / ppcsr_betweenness over the GLOBAL vertex ids (start, sources; levels, sigma, bc: pppcsr_get_n entries),
  * one device call over every partition's array: path_counts does not depend on the partitioning, betweenness only within its
  * error bound (the order of the sums differs).  Same contract as pppcsr_sssp; a partition in the sequential regime is

@@ -75,6 +75,7 @@ EXPORTED = [
     "ppcsr_debug_chain_probe", "ppcsr_debug_isect_probe", "ppcsr_kcore", "pppcsr_kcore",
     "ppcsr_path_counts", "ppcsr_betweenness", "pppcsr_path_counts", "pppcsr_betweenness",
     "ppcsr_scc", "pppcsr_scc", "ppcsr_debug_scc_counters",
+    "ppcsr_msf", "pppcsr_msf", "ppcsr_debug_msf_counters",
     "ppcsr_triangles", "pppcsr_triangles", "ppcsr_common_neighbours", "ppcsr_common_neighbours_device", "pppcsr_common_neighbours",
 ]
 
@@ -153,6 +154,9 @@ def load_library(path=None):
     for name in ("ppcsr_scc", "pppcsr_scc"):
         getattr(L, name).argtypes = [c_vp, c_vp, ctypes.POINTER(c_u64), ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_debug_scc_counters.argtypes = [c_vp, c_vp]
+    for name in ("ppcsr_msf", "pppcsr_msf"):
+        getattr(L, name).argtypes = [c_vp, c_vp, c_u64, ctypes.POINTER(c_u64), ctypes.POINTER(c_u64), c_vp, ctypes.POINTER(ctypes.c_double)]
+    L.ppcsr_debug_msf_counters.argtypes = [c_vp, c_vp]
     for name in ("ppcsr_triangles", "pppcsr_triangles"):
         getattr(L, name).argtypes = [c_vp, c_vp, ctypes.POINTER(c_u64), ctypes.POINTER(ctypes.c_double)]
     for name in ("ppcsr_common_neighbours", "ppcsr_common_neighbours_device", "pppcsr_common_neighbours"):
@@ -322,6 +326,18 @@ class _Consumers:
         ms = self._consumer("scc", labels.ctypes.data, ctypes.byref(count))
         return (labels, count.value, ms) if with_ms else (labels, count.value)
 
+    def msf(self, with_ms=False):
+        """(edges, weight, labels[, ms]): the minimum spanning forest over the edge values, every stored pair an undirected
+        edge: edges[count, 3] uint32 rows (lo, hi, w) ascending by (lo, hi), the sum of their weights (a Python int), and the
+        smallest vertex id of every vertex's tree (uint32: what components() returns)"""
+        n = self.get_n()
+        edges = np.empty((max(n, 1) - 1, 3), np.uint32)  # (a forest has at most n - 1 edges)
+        labels = np.empty(n, np.uint32)
+        count, weight = c_u64(), c_u64()
+        ms = self._consumer("msf", edges.ctypes.data, len(edges), ctypes.byref(count), ctypes.byref(weight), labels.ctypes.data)
+        edges = edges[: count.value]
+        return (edges, weight.value, labels, ms) if with_ms else (edges, weight.value, labels)
+
     def common_neighbours(self, a, b, with_ms=False):
         """counts[i] = stored destinations < n that a[i] and b[i] share (uint32; vertices >= n give 0)"""
         a, b = _u32(a), _u32(b)
@@ -488,6 +504,13 @@ class PCSR(_Consumers):
         the pivot (2^64 - 1: none), vertices of its SCC, colouring rounds, vertices coloured, streaming passes, host reads"""
         out = np.zeros(8, np.uint64)
         self._chk(self.L.ppcsr_debug_scc_counters(self.h, out.ctypes.data))
+        return out
+
+    def debug_msf_counters(self):
+        """Debugging (ppcsr_debug_msf_counters): uint64[8] of the last msf call on this engine — rounds, streaming passes,
+        pointer-jump launches, the most of them in one round, first-round hooks, forest edges, components, host reads"""
+        out = np.zeros(8, np.uint64)
+        self._chk(self.L.ppcsr_debug_msf_counters(self.h, out.ctypes.data))
         return out
 
     def check_invariants(self):
@@ -667,6 +690,10 @@ class PPPCSR(_Consumers):
     def debug_scc_counters(self):
         """the counters of the last scc call: kept by the engine that ran it, the first partition's"""
         return self.partition(0).debug_scc_counters()
+
+    def debug_msf_counters(self):
+        """the counters of the last msf call: kept by the engine that ran it, the first partition's"""
+        return self.partition(0).debug_msf_counters()
 
     def add_edge(self, s, d, v=1): self._chk(self.L.pppcsr_add_edge(self.h, s, d, v))
     def remove_edge(self, s, d): self._chk(self.L.pppcsr_remove_edge(self.h, s, d))

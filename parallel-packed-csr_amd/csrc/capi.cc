@@ -204,6 +204,13 @@ int ppcsr_scc(ppcsr_t h, uint32_t *labels, uint64_t *count, double *device_ms) {
   return ret(h->e, h->e->scc_over(&self, 1, h->e->n(), labels, count, device_ms));
 }
 int ppcsr_debug_scc_counters(ppcsr_t h, uint64_t out[8]) { H_CHECK(); return ret(h->e, h->e->scc_counters(out)); }
+int ppcsr_msf(ppcsr_t h, ppcsr_edge *edges, uint64_t cap, uint64_t *count, uint64_t *weight, uint32_t *labels, double *device_ms) {
+  H_CHECK();
+  if (!edges && !count && !weight && !labels) return bad("msf: null outputs");
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->msf_over(&self, 1, h->e->n(), reinterpret_cast<ppcsr::Edge *>(edges), cap, count, weight, labels, device_ms));
+}
+int ppcsr_debug_msf_counters(ppcsr_t h, uint64_t out[8]) { H_CHECK(); return ret(h->e, h->e->msf_counters(out)); }
 int ppcsr_triangles(ppcsr_t h, uint64_t *tri, uint64_t *total, double *device_ms) {
   H_CHECK();
   if (!tri && !total) return bad("triangles: null outputs");
@@ -765,6 +772,13 @@ int pppcsr_scc(pppcsr_t h, uint32_t *labels, uint64_t *count, double *device_ms)
   PP_CHECK();
   if (!labels && !count) return bad("scc: null outputs");
   return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) { return ret(e, e->scc_over(r, P, n, labels, count, device_ms)); });
+}
+int pppcsr_msf(pppcsr_t h, ppcsr_edge *edges, uint64_t cap, uint64_t *count, uint64_t *weight, uint32_t *labels, double *device_ms) {
+  PP_CHECK();
+  if (!edges && !count && !weight && !labels) return bad("msf: null outputs");
+  return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) {
+    return ret(e, e->msf_over(r, P, n, reinterpret_cast<ppcsr::Edge *>(edges), cap, count, weight, labels, device_ms));
+  });
 }
 int pppcsr_triangles(pppcsr_t h, uint64_t *tri, uint64_t *total, double *device_ms) {
   PP_CHECK();

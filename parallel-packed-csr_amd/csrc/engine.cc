@@ -97,6 +97,7 @@ struct Engine::Impl {
   unsigned long long *d_snapcnt = nullptr;
   // what the last scc_over on this engine did (ppcsr_debug_scc_counters): kept on the host from the reads the call makes anyway
   uint64_t scc_ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t msf_ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the same for msf_over (ppcsr_debug_msf_counters)
   // dirty tags: writers stamp View::ldirty / vdirty with `serial`; every snapshot synchronisation advances it
   uint32_t serial = 1;
   uint64_t array_gen = 1;

@@ -112,6 +112,13 @@ class Engine {
   // (ppcsr_debug_scc_counters, include/ppcsr.h)
   int scc_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t *labels, uint64_t *count, double *device_ms);
   int scc_counters(uint64_t out[8]);
+  // minimum spanning forest over the edge values (pma_msf.h), in either regime: edges (at most cap, ascending by (src, dest) =
+  // (lo, hi), may be null), *count = forest edges, *weight = their sum, labels as components_over gives them (total_n entries);
+  // each may be null.  PPCSR_ERANGE when edges != null and cap < *count, everything else delivered.  msf_counters: what the last
+  // msf_over on this engine did (ppcsr_debug_msf_counters, include/ppcsr.h)
+  int msf_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, Edge *edges, uint64_t cap, uint64_t *count, uint64_t *weight,
+               uint32_t *labels, double *device_ms);
+  int msf_counters(uint64_t out[8]);
   // shortest-path counts and betweenness centrality (pma_centrality.h), in either regime.  path_counts: levels as bfs_over
   // gives them and sigma[v] = number of fewest-edge paths from `start` to v, in fp64 (total_n entries each; either may be
   // null, not both).  betweenness: bc[v] (total_n entries) = Brandes' dependency of the k sources on v, endpoints

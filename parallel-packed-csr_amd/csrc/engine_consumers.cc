@@ -1,5 +1,5 @@
 // Host drivers of the graph-algorithm consumers (kernels: pma_consumer.h, pma_scan.h, pma_paths.h, pma_cores.h, pma_centrality.h,
-// pma_scc.h, pma_intersect.h).  Included at the end of engine.cc: part of the engine's single translation unit, in the library
+// pma_scc.h, pma_msf.h, pma_intersect.h).  Included at the end of engine.cc: part of the engine's single translation unit, in the library
 // (csrc/ppcsr_hip.hip) and in the emulator (tests/hostsim/ppcsr_sim.cpp) alike.
 namespace ppcsr {
 
@@ -609,6 +609,139 @@ int Engine::scc_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uin
 int Engine::scc_counters(uint64_t out[8]) {
   if (!out) return fail(PPCSR_EINVAL, "scc counters: no output");
   for (int i = 0; i < 8; i++) out[i] = p_->scc_ctr[i];
+  return PPCSR_OK;
+}
+
+// Minimum spanning forest (pma_msf.h): Boruvka rounds.  A round is the lightest-weight pass and one host read of its count of
+// cut edges — none ends the loop — then the lightest-pair pass, the hook launch and pointer doubling, one host read per jump
+// launch (the first of them brings the round's hooks along), then the reset.  So passes = 2 * rounds - 1: the last round makes
+// the first pass only.  The striped counters are cleared once and read as running totals.  Every component with a cut edge
+// merges, so more than floor(log2 n) + 2 rounds, a round that hooks nothing or a doubling of more than 34 launches is reported
+// as an error instead of spinning.  The edge list is sorted by lo << 32 | hi on the device (rocPRIM; std::sort in the emulator).
+int Engine::msf_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, Edge *edges, uint64_t cap, uint64_t *count, uint64_t *weight,
+                     uint32_t *labels, double *device_ms) {
+  const uint32_t nn = total_n;
+  ConsumerScope cs(this);
+  const int rc = cs.open(parts, P, nn);
+  if (rc != PPCSR_OK) return rc;
+  Impl &p = *p_;
+  const ConsumerPart *tab = cs.table();
+  const uint64_t N = cs.slots();
+  const uint64_t words = std::max<uint64_t>(nn, 1);
+  constexpr uint32_t cnt_words = kBfsStripes * kMsfStripeWords;
+  uint32_t *d_comp = cs.alloc<uint32_t>("d_comp", words), *d_par = cs.alloc<uint32_t>("d_par", words), *d_bw = cs.alloc<uint32_t>("d_bw", words);
+  unsigned long long *d_bp = cs.alloc<unsigned long long>("d_bp", words);
+  unsigned long long *d_k0 = cs.alloc<unsigned long long>("d_k0", words), *d_k1 = cs.alloc<unsigned long long>("d_k1", words);  // the list: keys
+  uint32_t *d_w0 = cs.alloc<uint32_t>("d_w0", words), *d_w1 = cs.alloc<uint32_t>("d_w1", words);                                  // and weights
+  Edge *d_out = edges ? cs.alloc<Edge>("d_out", words) : nullptr;
+  unsigned long long *d_cnt = cs.alloc<unsigned long long>("d_cnt", cnt_words);
+  uint32_t *d_ne = cs.alloc<uint32_t>("d_ne", 2);  // the length of the list
+  if (cs.rc != PPCSR_OK) return cs.rc;
+  std::vector<unsigned long long> h_cnt(cnt_words, 0);
+  uint64_t ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t &rounds = ctr[0], &passes = ctr[1], &reads = ctr[7];
+  uint64_t tot[3] = {0, 0, 0};  // running totals of the three counter words, as of the last read
+  uint64_t m = 0;
+  const uint32_t pass_grid = grid_for((N + 255) / 256, 4, 8192), vert_grid = grid_for(nn, 256, 4096);
+  // the counters' growth since the last read: [0] cut edges / pointers moved, [1] hooks, [2] weight
+  const auto read = [&](uint64_t grew[3]) {
+    GCHK(gpu::d2h(h_cnt.data(), d_cnt, cnt_words * sizeof(unsigned long long), p.stream));
+    GCHK(gpu::sync(p.stream));
+    GCHK(gpu::last_error());
+    reads++;
+    for (uint32_t w = 0; w < 3; w++) {
+      uint64_t now = 0;
+      for (uint32_t k = 0; k < kBfsStripes; k++) now += h_cnt[(uint64_t)k * kMsfStripeWords + w];
+      grew[w] = now - tot[w];
+      tot[w] = now;
+    }
+    return (int)PPCSR_OK;
+  };
+  uint32_t max_rounds = 2;  // floor(log2 n) + 2
+  while (((uint64_t)nn >> (max_rounds - 1)) != 0) max_rounds++;
+  cs.start();
+  if (nn) {
+    GCHK(gpu::dset(d_cnt, 0, cnt_words * sizeof(unsigned long long), p.stream));
+    GCHK(gpu::dset(d_ne, 0, 2 * sizeof(uint32_t), p.stream));
+    GPU_LAUNCH(p.stream, k_cc_init, vert_grid, 256, d_par, nn);
+    GPU_LAUNCH(p.stream, k_msf_reset, vert_grid, 256, d_comp, (const uint32_t *)d_par, d_bw, d_bp, nn);
+    for (;;) {
+      if (rounds >= max_rounds) return fail(PPCSR_EHIP, "msf: more rounds than halving the components allows");
+      uint64_t grew[3];
+      GPU_LAUNCH(p.stream, k_msf_weight, pass_grid, 256, tab, P, nn, (const uint32_t *)d_comp, d_bw, d_cnt);
+      passes++;
+      rounds++;
+      int e = read(grew);
+      if (e != PPCSR_OK) return e;
+      if (grew[0] == 0) break;
+      GPU_LAUNCH(p.stream, k_msf_pair, pass_grid, 256, tab, P, nn, (const uint32_t *)d_comp, d_bw, d_bp);
+      passes++;
+      GPU_LAUNCH(p.stream, k_msf_hook, vert_grid, 256, (const uint32_t *)d_comp, d_par, (const uint32_t *)d_bw, (const unsigned long long *)d_bp, nn,
+                 d_k0, d_w0, d_ne, d_cnt);
+      uint64_t hooks = 0, jumps = 0;
+      for (uint64_t moved = 1; moved > 0;) {
+        if (jumps > 34) return fail(PPCSR_EHIP, "msf: pointer doubling did not end");
+        GPU_LAUNCH(p.stream, k_msf_jump, vert_grid, 256, d_par, nn, d_cnt);
+        jumps++;
+        e = read(grew);
+        if (e != PPCSR_OK) return e;
+        moved = grew[0];
+        hooks += grew[1];
+      }
+      if (hooks == 0 || ctr[5] + hooks >= nn) return fail(PPCSR_EHIP, "msf: a round with cut edges hooked nothing, or too much");
+      ctr[2] += jumps;
+      ctr[3] = std::max(ctr[3], jumps);
+      if (rounds == 1) ctr[4] = hooks;
+      ctr[5] += hooks;
+      GPU_LAUNCH(p.stream, k_msf_reset, vert_grid, 256, d_comp, (const uint32_t *)d_par, d_bw, d_bp, nn);
+    }
+    // finish: labels (d_bw is all kMax: the last reset, and a pass without cut edges stores nothing), the length, the sort
+    GPU_LAUNCH(p.stream, k_msf_label_min, vert_grid, 256, (const uint32_t *)d_comp, d_bw, nn);
+    GPU_LAUNCH(p.stream, k_msf_label_assign, vert_grid, 256, (const uint32_t *)d_comp, (const uint32_t *)d_bw, d_par, nn);
+    uint32_t h_ne = 0;
+    GCHK(gpu::d2h(&h_ne, d_ne, sizeof(uint32_t), p.stream));
+    GCHK(gpu::sync(p.stream));
+    GCHK(gpu::last_error());
+    reads++;
+    m = h_ne;
+    if (m != ctr[5]) return fail(PPCSR_EHIP, "msf: the edge list and the hook counts disagree");
+    if (edges && m) {
+#if defined(PPCSR_SIM)
+      std::vector<uint64_t> idx(m);
+      for (uint64_t i = 0; i < m; i++) idx[i] = i;
+      std::sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) { return d_k0[a] < d_k0[b]; });
+      for (uint64_t i = 0; i < m; i++) {
+        d_k1[i] = d_k0[idx[i]];
+        d_w1[i] = d_w0[idx[i]];
+      }
+#else
+      unsigned bits = 33;  // keys are below n << 32
+      while (bits < 64 && ((uint64_t)nn >> (bits - 32)) != 0) bits++;
+      size_t tmp_bytes = 0;
+      if (rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_k0, d_k1, d_w0, d_w1, (size_t)m, 0u, bits, p.stream) != hipSuccess)
+        return fail(PPCSR_EHIP, "msf: device sort failed");
+      uint8_t *d_tmp = cs.alloc<uint8_t>("d_tmp", std::max<uint64_t>(tmp_bytes, 1));
+      if (cs.rc != PPCSR_OK) return cs.rc;
+      if (rocprim::radix_sort_pairs(d_tmp, tmp_bytes, d_k0, d_k1, d_w0, d_w1, (size_t)m, 0u, bits, p.stream) != hipSuccess)
+        return fail(PPCSR_EHIP, "msf: device sort failed");
+#endif
+      GPU_LAUNCH(p.stream, k_msf_pack, grid_for(m, 256, 4096), 256, (const unsigned long long *)d_k1, (const uint32_t *)d_w1, m, d_out);
+    }
+  }
+  cs.stop();
+  if (edges && m && cap) GCHK(gpu::d2h(edges, d_out, std::min<uint64_t>(cap, m) * sizeof(Edge), p.stream));
+  if (labels && nn) GCHK(gpu::d2h(labels, d_par, (uint64_t)nn * sizeof(uint32_t), p.stream));
+  const int done = cs.done(device_ms);
+  if (done != PPCSR_OK) return done;
+  if (count) *count = m;
+  if (weight) *weight = tot[2];
+  ctr[6] = (uint64_t)nn - m;
+  for (int i = 0; i < 8; i++) p.msf_ctr[i] = ctr[i];
+  return (edges && cap < m) ? PPCSR_ERANGE : PPCSR_OK;
+}
+int Engine::msf_counters(uint64_t out[8]) {
+  if (!out) return fail(PPCSR_EINVAL, "msf counters: no output");
+  for (int i = 0; i < 8; i++) out[i] = p_->msf_ctr[i];
   return PPCSR_OK;
 }
 

@@ -9,6 +9,7 @@
 //   pma_cores.h        core numbers (k-core decomposition): symmetric adjacency export, peeling in sub-rounds
 //   pma_centrality.h   shortest-path counts and betweenness centrality: forward levels with fp64 counts, backward sweep
 //   pma_scc.h          strongly connected components: trimming, forward-backward reach from a pivot, colouring
+//   pma_msf.h          minimum spanning forest over the edge values: Boruvka rounds of two streaming passes, hook, pointer doubling
 //   pma_intersect.h    triangle counts and common-neighbour counts: sorted intersection of two gapped vertex ranges
 //   pma_isect_probe.h  debugging probe of the intersection routines (ppcsr_debug_isect_probe)
 //   pma_query.h        batched reads: edge lookups with values, neighbourhood gathers
@@ -24,6 +25,7 @@
 #include "pma_cores.h"
 #include "pma_centrality.h"
 #include "pma_scc.h"
+#include "pma_msf.h"
 #include "pma_intersect.h"
 #include "pma_isect_probe.h"
 #include "pma_query.h"
