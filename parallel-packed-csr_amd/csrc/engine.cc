@@ -2066,11 +2066,16 @@ int Engine::export_triples_device(uint32_t src_base, Op *d_out, uint64_t cap, ui
 }
 
 // ---- bulk build (kernels k_bb_*) -----------------------------------------------------------------------
-static int sort_edges_stable(gpu::stream_t st, unsigned long long *kin, unsigned long long *kout, uint32_t *vin, uint32_t *vout,
-                             uint64_t m, unsigned bits) {
+// Stable sort of (key, value) pairs by the low `bits` bits of the key: rocPRIM's radix sort on the device, std::stable_sort on
+// an index in the CPU emulator.  tmp(bytes) hands out the device sort's temporary storage (null: none to be had) and keeps
+// owning it; the emulator needs none and never asks.  0: sorted (the sort is in flight on `st`), 2: no temporary storage,
+// 3: the sort failed.
+template <class K, class V, class Tmp>
+static int sort_pairs_stable(gpu::stream_t st, K *kin, K *kout, V *vin, V *vout, uint64_t m, unsigned bits, Tmp tmp) {
 #if defined(PPCSR_SIM)
   (void)st;
   (void)bits;
+  (void)tmp;
   std::vector<uint64_t> idx(m);
   for (uint64_t i = 0; i < m; i++) idx[i] = i;
   std::stable_sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) { return kin[a] < kin[b]; });
@@ -2082,13 +2087,21 @@ static int sort_edges_stable(gpu::stream_t st, unsigned long long *kin, unsigned
 #else
   size_t tmp_bytes = 0;
   if (rocprim::radix_sort_pairs(nullptr, tmp_bytes, kin, kout, vin, vout, (size_t)m, 0u, bits, st) != hipSuccess) return 3;
-  void *tmp = nullptr;
-  if (hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 1) != hipSuccess) return 2;
-  const hipError_t e = rocprim::radix_sort_pairs(tmp, tmp_bytes, kin, kout, vin, vout, (size_t)m, 0u, bits, st);
-  (void)hipStreamSynchronize(st);
-  (void)hipFree(tmp);
-  return e == hipSuccess ? 0 : 3;
+  void *t = tmp(tmp_bytes);
+  if (!t) return 2;
+  return rocprim::radix_sort_pairs(t, tmp_bytes, kin, kout, vin, vout, (size_t)m, 0u, bits, st) == hipSuccess ? 0 : 3;
 #endif
+}
+// the same with temporary storage of its own, freed once the sort has run
+template <class K, class V>
+static int sort_pairs_stable(gpu::stream_t st, K *kin, K *kout, V *vin, V *vout, uint64_t m, unsigned bits) {
+  void *t = nullptr;
+  const int rc = sort_pairs_stable(st, kin, kout, vin, vout, m, bits, [&](size_t bytes) { return gpu::dmalloc(&t, bytes) == 0 ? t : nullptr; });
+  if (t) {
+    (void)gpu::sync(st);
+    (void)gpu::dfree(t);
+  }
+  return rc;
 }
 
 int Engine::bulk_build(const Op *host_ops, uint64_t m, double *device_ms) { return bulk_build_from(host_ops, false, m, device_ms); }
@@ -2126,7 +2139,7 @@ int Engine::bulk_build_from(const Op *in_ops, bool on_device, uint64_t m, double
     GPU_LAUNCH(p.stream, k_bb_keys, grid_for(m, 256), 256, src_ops, m, nn, d_k0, d_v0);
     unsigned bits = 1;  // the source half of the key never exceeds n (entries to ignore carry src = n)
     while (bits < 32 && ((uint64_t)nn >> bits) != 0) bits++;
-    int rc = sort_edges_stable(p.stream, d_k0, d_k1, d_v0, d_v1, m, 32u + bits);
+    int rc = sort_pairs_stable(p.stream, d_k0, d_k1, d_v0, d_v1, m, 32u + bits);
     if (rc != 0) return fail(rc == 2 ? PPCSR_ENOMEM : PPCSR_EHIP, "bulk_build: device sort failed");
     GPU_LAUNCH(p.stream, k_bb_flags, grid_for(m, 256), 256, (const unsigned long long *)d_k1, m, nn, d_flags);
     rc = rank_scan(d_flags, m, false, 0, 0);

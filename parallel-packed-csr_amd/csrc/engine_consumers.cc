@@ -39,19 +39,17 @@ int Engine::intersect_regime(const ConsumerRef *parts, uint32_t P, const char *w
   return PPCSR_OK;
 }
 
-// counter block of the hybrid loop: [0] vertices found, [1] a hub was left to the streaming pass, [kBfsStripeWords...] the
-// streaming pass's striped count
-constexpr uint32_t kHybridCntWords = (kBfsStripes + 1) * kBfsStripeWords;
-
 // One consumer call: what every *_over does before and after its own launches.  open() selects the device, refuses the
 // sequential regime for a consumer that intersects, and builds the table; alloc() hands out the call's device buffers, all of
-// which are freed on every exit path; start() / stop() / done() run the timer and hand device_ms out.
+// which are freed on every exit path; stream() and the three grids are what the call's launches go out with; read_back() is a
+// host read in the middle of the call; start() / stop() / done() run the timer and hand device_ms out.
 struct Engine::ConsumerScope {
   Engine &eng;
   Impl &p;
   std::vector<void *> bufs;
   const ConsumerPart *tab_ = nullptr;
   uint64_t slots_ = 0;
+  uint32_t n_ = 0;
   int rc = PPCSR_OK;  // the first allocation that failed (later ones are not tried)
 
   explicit ConsumerScope(Engine *e) : eng(*e), p(*e->p_) {}
@@ -65,6 +63,7 @@ struct Engine::ConsumerScope {
     GCHK(gpu::set_device(eng.device_));
     std::string msg;
     if (intersects && eng.intersect_regime(parts, P, intersects, &msg) != PPCSR_OK) return fail(PPCSR_EUNSUPPORTED, msg);
+    n_ = total_n;
     void *d_tab = nullptr;
     const int e = eng.consumer_table(parts, P, total_n, device_table ? &d_tab : nullptr, &slots_);
     if (d_tab) bufs.push_back(d_tab);
@@ -73,6 +72,13 @@ struct Engine::ConsumerScope {
   }
   const ConsumerPart *table() const { return tab_; }
   uint64_t slots() const { return slots_; }  // slots of all arrays: what one streaming pass reads
+  uint64_t words() const { return std::max<uint64_t>(n_, 1); }  // length of a per-vertex buffer (never an empty allocation)
+  gpu::stream_t stream() const { return p.stream; }
+  // a streaming pass (cp_stream: a wave per four 64-slot chunks, four waves per workgroup), a per-vertex launch (a thread per
+  // vertex), a launch with a wave per entry of a list
+  uint32_t pass_grid() const { return grid_for((slots_ + 255) / 256, 4, 8192); }
+  uint32_t vert_grid() const { return grid_for(n_, 256, 4096); }
+  uint32_t list_grid(uint64_t count) const { return grid_for(count, 4, 16384); }
   template <class T>
   T *alloc(const char *what, uint64_t count) {
     void *b = nullptr;
@@ -85,6 +91,13 @@ struct Engine::ConsumerScope {
     bufs.push_back(b);
     return static_cast<T *>(b);
   }
+  // a host read in the middle of the call: the copy, the wait for it, and whatever error a launch before it has left
+  int read_back(void *dst, const void *src, uint64_t bytes) {
+    GCHK(gpu::d2h(dst, src, bytes, p.stream));
+    GCHK(gpu::sync(p.stream));
+    GCHK(gpu::last_error());
+    return PPCSR_OK;
+  }
   void start() { p.timer.start(p.stream); }
   void stop() { p.timer.stop(p.stream); }
   int done(double *device_ms) {
@@ -93,6 +106,31 @@ struct Engine::ConsumerScope {
     if (device_ms) *device_ms = p.timer.ms();
     return PPCSR_OK;
   }
+
+  // The striped counters of a call (cp_striped_add): kBfsStripes stripes, kWords words of T apart, word w of every stripe one
+  // counter — behind kLead words of the call's own.  The device block (one allocation, made where the object is constructed)
+  // and its host mirror: zero() clears the block, read() is ONE host read of all of it, sum(w) adds counter w up from the
+  // mirror and lead(i) is word i of the leading ones.
+  template <class T, uint32_t kWords, uint32_t kLead = 0>
+  struct Striped {
+    static constexpr uint32_t kCount = kLead + kBfsStripes * kWords;
+    ConsumerScope &cs;
+    T *dev;
+    std::vector<T> host;
+    Striped(ConsumerScope &scope, const char *what) : cs(scope), dev(scope.alloc<T>(what, kCount)), host(kCount, 0) {}
+    T *stripes() const { return dev + kLead; }
+    int zero() { return gpu::dset(dev, 0, kCount * sizeof(T), cs.p.stream); }
+    int read() { return cs.read_back(host.data(), dev, kCount * sizeof(T)); }
+    T lead(uint32_t i) const { return host[i]; }
+    uint64_t sum(uint32_t w = 0) const {
+      uint64_t all = 0;
+      for (uint32_t k = 0; k < kBfsStripes; k++) all += host[kLead + (uint64_t)k * kWords + w];
+      return all;
+    }
+  };
+  // counter block of the hybrid loop: [0] vertices found, [1] a hub was left to the streaming pass, then the streaming pass's
+  // striped count
+  typedef Striped<uint32_t, kBfsStripeWords, kBfsStripeWords> HybridCounters;
 
   // The hybrid loop of bfs_over and sssp_over, from a frontier of one vertex (in d_f0) at step `step` until a step finds
   // nothing.  A small frontier is expanded one wave per vertex (per_vertex(cur, nfront, step, nxt): builds the next frontier
@@ -104,16 +142,16 @@ struct Engine::ConsumerScope {
   // every step is appended to it — exact where the count is.
   static uint32_t hybrid_big(uint32_t nn) { return (uint32_t)std::max<uint64_t>(64, (uint64_t)nn / 256); }
   template <class Pass, class PerVertex>
-  int hybrid(uint32_t nn, const uint32_t *d_key, uint32_t step, uint32_t *d_f0, uint32_t *d_f1, uint32_t *d_cnt, bool reread_list, Pass pass,
+  int hybrid(uint32_t nn, const uint32_t *d_key, uint32_t step, uint32_t *d_f0, uint32_t *d_f1, HybridCounters &cnt, bool reread_list, Pass pass,
              PerVertex per_vertex, std::vector<uint32_t> *sizes = nullptr) {
     uint32_t nfront = 1;
     uint32_t *cur = d_f0, *nxt = d_f1;
-    std::vector<uint32_t> h_cnt(kHybridCntWords, 0);
+    uint32_t *const d_cnt = cnt.dev;
     bool have_list = true;
     const uint32_t big = hybrid_big(nn);  // frontier size from which the pass is cheaper
     for (; nfront > 0; step++) {
       if (sizes) sizes->push_back(nfront);
-      GCHK(gpu::dset(d_cnt, 0, kHybridCntWords * sizeof(uint32_t), p.stream));
+      GCHK(cnt.zero());
       if (nfront >= big) {
         pass(step);
         have_list = false;
@@ -121,9 +159,9 @@ struct Engine::ConsumerScope {
         if (!have_list) {
           GPU_LAUNCH(p.stream, k_bfs_collect, grid_for(nn, 256), 256, d_key, nn, step, cur, d_cnt);
           if (reread_list) {
-            GCHK(gpu::d2h(h_cnt.data(), d_cnt, sizeof(uint32_t), p.stream));
+            GCHK(gpu::d2h(cnt.host.data(), d_cnt, sizeof(uint32_t), p.stream));
             GCHK(gpu::sync(p.stream));
-            nfront = h_cnt[0];
+            nfront = cnt.lead(0);
           }
           GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), p.stream));
         }
@@ -131,18 +169,15 @@ struct Engine::ConsumerScope {
         have_list = true;
         std::swap(cur, nxt);
       }
-      GCHK(gpu::d2h(h_cnt.data(), d_cnt, kHybridCntWords * sizeof(uint32_t), p.stream));
-      GCHK(gpu::sync(p.stream));
-      GCHK(gpu::last_error());
-      if (h_cnt[1]) {  // hubs of this step were skipped by the per-vertex kernel: one pass finishes the step
+      int e = cnt.read();
+      if (e != PPCSR_OK) return e;
+      if (cnt.lead(1)) {  // hubs of this step were skipped by the per-vertex kernel: one pass finishes the step
         pass(step);
-        GCHK(gpu::d2h(h_cnt.data(), d_cnt, kHybridCntWords * sizeof(uint32_t), p.stream));
-        GCHK(gpu::sync(p.stream));
-        GCHK(gpu::last_error());
+        e = cnt.read();
+        if (e != PPCSR_OK) return e;
         have_list = false;
       }
-      nfront = h_cnt[0];
-      for (uint32_t k = 1; k <= kBfsStripes; k++) nfront += h_cnt[k * kBfsStripeWords];
+      nfront = cnt.lead(0) + (uint32_t)cnt.sum();
     }
     return PPCSR_OK;
   }
@@ -165,9 +200,8 @@ struct Engine::ConsumerScope {
       GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), p.stream));
       GPU_LAUNCH(p.stream, k_bfs_collect, grid_for(nn, 256), 256, d_key, nn, (uint32_t)level, d_list, d_cnt);
       per_vertex((const uint32_t *)d_list, sizes[level], (uint32_t)level);
-      GCHK(gpu::d2h(h_cnt, d_cnt, 2 * sizeof(uint32_t), p.stream));
-      GCHK(gpu::sync(p.stream));
-      GCHK(gpu::last_error());
+      const int e = read_back(h_cnt, d_cnt, 2 * sizeof(uint32_t));
+      if (e != PPCSR_OK) return e;
       if (h_cnt[1]) pass((uint32_t)level, true);
     }
     return PPCSR_OK;
@@ -181,32 +215,31 @@ int Engine::bfs_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uin
   ConsumerScope cs(this);
   int rc = cs.open(parts, P, nn);
   if (rc != PPCSR_OK) return rc;
-  Impl &p = *p_;
   const ConsumerPart *tab = cs.table();
-  const uint64_t N = cs.slots();
   const uint64_t bit_words = ((uint64_t)nn + 63) / 64 * 2;  // frontier / visited bitmaps of the streaming levels
   uint32_t *d_fb = cs.alloc<uint32_t>("d_fb", bit_words), *d_vb = cs.alloc<uint32_t>("d_vb", bit_words);
   uint32_t *d_lv = cs.alloc<uint32_t>("d_lv", nn), *d_f0 = cs.alloc<uint32_t>("d_f0", nn), *d_f1 = cs.alloc<uint32_t>("d_f1", nn);
-  uint32_t *d_cnt = cs.alloc<uint32_t>("d_cnt", kHybridCntWords);
+  ConsumerScope::HybridCounters cnt(cs, "d_cnt");
+  uint32_t *const d_cnt = cnt.dev, *const d_found = cnt.stripes();  // (a launch's arguments are plain pointers)
   if (cs.rc != PPCSR_OK) return cs.rc;
   cs.start();
-  GCHK(gpu::dset(d_lv, 0xFF, (uint64_t)nn * sizeof(uint32_t), p.stream));
+  GCHK(gpu::dset(d_lv, 0xFF, (uint64_t)nn * sizeof(uint32_t), cs.stream()));
   const uint32_t zero = 0;
-  GCHK(gpu::h2d(d_lv + start, &zero, sizeof(uint32_t), p.stream));
-  GCHK(gpu::h2d(d_f0, &start, sizeof(uint32_t), p.stream));
+  GCHK(gpu::h2d(d_lv + start, &zero, sizeof(uint32_t), cs.stream()));
+  GCHK(gpu::h2d(d_f0, &start, sizeof(uint32_t), cs.stream()));
   rc = cs.hybrid(
-      nn, d_lv, 0, d_f0, d_f1, d_cnt, true,
+      nn, d_lv, 0, d_f0, d_f1, cnt, true,
       [&](uint32_t level) {
-        GPU_LAUNCH(p.stream, k_bfs_bits, grid_for(nn, 256, 4096), 256, (const uint32_t *)d_lv, nn, level, d_fb, d_vb);
-        GPU_LAUNCH(p.stream, k_bfs_edges_bits, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, level, (const uint32_t *)d_fb,
-                   (const uint32_t *)d_vb, d_lv, d_cnt + kBfsStripeWords);
+        GPU_LAUNCH(cs.stream(), k_bfs_bits, cs.vert_grid(), 256, (const uint32_t *)d_lv, nn, level, d_fb, d_vb);
+        GPU_LAUNCH(cs.stream(), k_bfs_edges_bits, cs.pass_grid(), 256, tab, P, nn, level, (const uint32_t *)d_fb, (const uint32_t *)d_vb, d_lv,
+                   d_found);
       },
       [&](const uint32_t *cur, uint32_t nfront, uint32_t level, uint32_t *nxt) {
-        GPU_LAUNCH(p.stream, k_bfs_level, grid_for(nfront, 4, 16384), 256, tab, P, nn, cur, nfront, level, d_lv, nxt, d_cnt);
+        GPU_LAUNCH(cs.stream(), k_bfs_level, cs.list_grid(nfront), 256, tab, P, nn, cur, nfront, level, d_lv, nxt, d_cnt);
       });
   if (rc != PPCSR_OK) return rc;
   cs.stop();
-  GCHK(gpu::d2h(levels, d_lv, (uint64_t)nn * sizeof(uint32_t), p.stream));
+  GCHK(gpu::d2h(levels, d_lv, (uint64_t)nn * sizeof(uint32_t), cs.stream()));
   return cs.done(device_ms);
 }
 
@@ -219,36 +252,34 @@ int Engine::sssp_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, ui
   ConsumerScope cs(this);
   int rc = cs.open(parts, P, nn);
   if (rc != PPCSR_OK) return rc;
-  Impl &p = *p_;
   const ConsumerPart *tab = cs.table();
-  const uint64_t N = cs.slots();
   const uint64_t bit_words = ((uint64_t)nn + 63) / 64 * 2;  // active bitmap of the streaming rounds (d_vb: k_bfs_bits' second output, unused)
   uint32_t *d_ab = cs.alloc<uint32_t>("d_ab", bit_words), *d_vb = cs.alloc<uint32_t>("d_vb", bit_words);
   unsigned long long *d_dist = cs.alloc<unsigned long long>("d_dist", nn);
   uint32_t *d_st = cs.alloc<uint32_t>("d_st", nn), *d_f0 = cs.alloc<uint32_t>("d_f0", nn), *d_f1 = cs.alloc<uint32_t>("d_f1", nn);
-  uint32_t *d_cnt = cs.alloc<uint32_t>("d_cnt", kHybridCntWords);
+  ConsumerScope::HybridCounters cnt(cs, "d_cnt");
+  uint32_t *const d_cnt = cnt.dev, *const d_found = cnt.stripes();  // (a launch's arguments are plain pointers)
   if (cs.rc != PPCSR_OK) return cs.rc;
   cs.start();
-  GCHK(gpu::dset(d_dist, 0xFF, (uint64_t)nn * sizeof(unsigned long long), p.stream));
-  GCHK(gpu::dset(d_st, 0, (uint64_t)nn * sizeof(uint32_t), p.stream));
+  GCHK(gpu::dset(d_dist, 0xFF, (uint64_t)nn * sizeof(unsigned long long), cs.stream()));
+  GCHK(gpu::dset(d_st, 0, (uint64_t)nn * sizeof(uint32_t), cs.stream()));
   const unsigned long long zero = 0;
   const uint32_t round0 = 1;  // (stamp 0: never active)
-  GCHK(gpu::h2d(d_dist + start, &zero, sizeof(zero), p.stream));
-  GCHK(gpu::h2d(d_st + start, &round0, sizeof(uint32_t), p.stream));
-  GCHK(gpu::h2d(d_f0, &start, sizeof(uint32_t), p.stream));
+  GCHK(gpu::h2d(d_dist + start, &zero, sizeof(zero), cs.stream()));
+  GCHK(gpu::h2d(d_st + start, &round0, sizeof(uint32_t), cs.stream()));
+  GCHK(gpu::h2d(d_f0, &start, sizeof(uint32_t), cs.stream()));
   rc = cs.hybrid(
-      nn, d_st, round0, d_f0, d_f1, d_cnt, false,
+      nn, d_st, round0, d_f0, d_f1, cnt, false,
       [&](uint32_t round) {
-        GPU_LAUNCH(p.stream, k_bfs_bits, grid_for(nn, 256, 4096), 256, (const uint32_t *)d_st, nn, round, d_ab, d_vb);
-        GPU_LAUNCH(p.stream, k_sssp_edges, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, round, (const uint32_t *)d_ab, d_dist, d_st,
-                   d_cnt + kBfsStripeWords);
+        GPU_LAUNCH(cs.stream(), k_bfs_bits, cs.vert_grid(), 256, (const uint32_t *)d_st, nn, round, d_ab, d_vb);
+        GPU_LAUNCH(cs.stream(), k_sssp_edges, cs.pass_grid(), 256, tab, P, nn, round, (const uint32_t *)d_ab, d_dist, d_st, d_found);
       },
       [&](const uint32_t *cur, uint32_t nact, uint32_t round, uint32_t *nxt) {
-        GPU_LAUNCH(p.stream, k_sssp_relax, grid_for(nact, 4, 16384), 256, tab, P, nn, cur, nact, round, d_dist, d_st, nxt, d_cnt);
+        GPU_LAUNCH(cs.stream(), k_sssp_relax, cs.list_grid(nact), 256, tab, P, nn, cur, nact, round, d_dist, d_st, nxt, d_cnt);
       });
   if (rc != PPCSR_OK) return rc;
   cs.stop();
-  GCHK(gpu::d2h(dist, d_dist, (uint64_t)nn * sizeof(unsigned long long), p.stream));
+  GCHK(gpu::d2h(dist, d_dist, (uint64_t)nn * sizeof(unsigned long long), cs.stream()));
   return cs.done(device_ms);
 }
 
@@ -259,27 +290,23 @@ int Engine::components_over(const ConsumerRef *parts, uint32_t P, uint32_t total
   ConsumerScope cs(this);
   const int rc = cs.open(parts, P, nn);
   if (rc != PPCSR_OK) return rc;
-  Impl &p = *p_;
+  uint32_t *d_lab = cs.alloc<uint32_t>("d_lab", cs.words());
+  ConsumerScope::Striped<uint32_t, kBfsStripeWords> cnt(cs, "d_cnt");
   const ConsumerPart *tab = cs.table();
-  const uint64_t N = cs.slots();
-  constexpr uint32_t cnt_words = kBfsStripes * kBfsStripeWords;
-  uint32_t *d_lab = cs.alloc<uint32_t>("d_lab", std::max<uint64_t>(nn, 1)), *d_cnt = cs.alloc<uint32_t>("d_cnt", cnt_words);
+  uint32_t *const d_cnt = cnt.dev;
   if (cs.rc != PPCSR_OK) return cs.rc;
-  std::vector<uint32_t> h_cnt(cnt_words, 0);
   cs.start();
-  if (nn) GPU_LAUNCH(p.stream, k_cc_init, grid_for(nn, 256, 4096), 256, d_lab, nn);
+  if (nn) GPU_LAUNCH(cs.stream(), k_cc_init, cs.vert_grid(), 256, d_lab, nn);
   for (bool more = nn != 0; more;) {
-    GCHK(gpu::dset(d_cnt, 0, cnt_words * sizeof(uint32_t), p.stream));
-    GPU_LAUNCH(p.stream, k_cc_hook, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, d_lab, d_cnt);
-    GPU_LAUNCH(p.stream, k_cc_jump, grid_for(nn, 256, 4096), 256, d_lab, nn);
-    GCHK(gpu::d2h(h_cnt.data(), d_cnt, cnt_words * sizeof(uint32_t), p.stream));
-    GCHK(gpu::sync(p.stream));
-    GCHK(gpu::last_error());
-    more = false;
-    for (uint32_t k = 0; k < kBfsStripes; k++) more = more || h_cnt[k * kBfsStripeWords] != 0;
+    GCHK(cnt.zero());
+    GPU_LAUNCH(cs.stream(), k_cc_hook, cs.pass_grid(), 256, tab, P, nn, d_lab, d_cnt);
+    GPU_LAUNCH(cs.stream(), k_cc_jump, cs.vert_grid(), 256, d_lab, nn);
+    const int e = cnt.read();
+    if (e != PPCSR_OK) return e;
+    more = cnt.sum() != 0;
   }
   cs.stop();
-  if (nn) GCHK(gpu::d2h(labels, d_lab, (uint64_t)nn * sizeof(uint32_t), p.stream));
+  if (nn) GCHK(gpu::d2h(labels, d_lab, (uint64_t)nn * sizeof(uint32_t), cs.stream()));
   return cs.done(device_ms);
 }
 
@@ -295,43 +322,42 @@ int Engine::centrality_over(const ConsumerRef *parts, uint32_t P, uint32_t total
   ConsumerScope cs(this);
   int rc = cs.open(parts, P, nn);
   if (rc != PPCSR_OK) return rc;
-  Impl &p = *p_;
   const ConsumerPart *tab = cs.table();
-  const uint64_t N = cs.slots();
-  const uint64_t words = std::max<uint64_t>(nn, 1);
+  const uint64_t words = cs.words();
   const uint64_t bit_words = std::max<uint64_t>(((uint64_t)nn + 63) / 64 * 2, 2);  // source / placed bitmaps of the streaming passes
   uint32_t *d_sb = cs.alloc<uint32_t>("d_sb", bit_words), *d_pb = cs.alloc<uint32_t>("d_pb", bit_words);
   uint32_t *d_lv = cs.alloc<uint32_t>("d_lv", words), *d_hub = cs.alloc<uint32_t>("d_hub", words);
   uint32_t *d_f0 = cs.alloc<uint32_t>("d_f0", words), *d_f1 = cs.alloc<uint32_t>("d_f1", words);
   double *d_sigma = cs.alloc<double>("d_sigma", words);
   double *d_delta = bc ? cs.alloc<double>("d_delta", words) : nullptr, *d_bc = bc ? cs.alloc<double>("d_bc", words) : nullptr;
-  uint32_t *d_cnt = cs.alloc<uint32_t>("d_cnt", kHybridCntWords);
+  ConsumerScope::HybridCounters cnt(cs, "d_cnt");
+  uint32_t *const d_cnt = cnt.dev, *const d_found = cnt.stripes();  // (a launch's arguments are plain pointers)
   if (cs.rc != PPCSR_OK) return cs.rc;
   cs.start();
-  GCHK(gpu::dset(d_hub, 0xFF, words * sizeof(uint32_t), p.stream));  // (kBcNoStamp: no launch has this number)
-  if (bc) GCHK(gpu::dset(d_bc, 0, words * sizeof(double), p.stream));
+  GCHK(gpu::dset(d_hub, 0xFF, words * sizeof(uint32_t), cs.stream()));  // (kBcNoStamp: no launch has this number)
+  if (bc) GCHK(gpu::dset(d_bc, 0, words * sizeof(double), cs.stream()));
   uint32_t stamp = 0;  // number of the last per-vertex launch
   std::vector<uint32_t> sizes;
   const auto bits = [&](uint32_t level, bool hubs_only) {
-    GPU_LAUNCH(p.stream, k_bc_bits, grid_for(nn, 256, 4096), 256, (const uint32_t *)d_lv, (const uint32_t *)d_hub, nn, level,
+    GPU_LAUNCH(cs.stream(), k_bc_bits, cs.vert_grid(), 256, (const uint32_t *)d_lv, (const uint32_t *)d_hub, nn, level,
                hubs_only ? stamp : kBcNoStamp, d_sb, d_pb);
   };
   for (uint64_t i = 0; i < k; i++) {
     const uint32_t s = sources[i];
-    GPU_LAUNCH(p.stream, k_bc_init, grid_for(nn, 256, 4096), 256, d_lv, d_sigma, d_delta, nn, s, d_f0);
+    GPU_LAUNCH(cs.stream(), k_bc_init, cs.vert_grid(), 256, d_lv, d_sigma, d_delta, nn, s, d_f0);
     sizes.clear();
     uint32_t pv_level = kBcNoStamp;  // level of the last per-vertex launch: a pass for the same level finishes it
     rc = cs.hybrid(
-        nn, d_lv, 0, d_f0, d_f1, d_cnt, false,
+        nn, d_lv, 0, d_f0, d_f1, cnt, false,
         [&](uint32_t level) {
           bits(level, level == pv_level);
-          GPU_LAUNCH(p.stream, k_bc_edges_forward, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, level, (const uint32_t *)d_sb,
-                     (const uint32_t *)d_pb, d_lv, d_sigma, d_cnt + kBfsStripeWords);
+          GPU_LAUNCH(cs.stream(), k_bc_edges_forward, cs.pass_grid(), 256, tab, P, nn, level, (const uint32_t *)d_sb,
+                     (const uint32_t *)d_pb, d_lv, d_sigma, d_found);
         },
         [&](const uint32_t *cur, uint32_t nfront, uint32_t level, uint32_t *nxt) {
           pv_level = level;
           stamp++;
-          GPU_LAUNCH(p.stream, k_bc_level, grid_for(nfront, 4, 16384), 256, tab, P, nn, cur, nfront, level, d_lv, d_sigma, d_hub, stamp, nxt,
+          GPU_LAUNCH(cs.stream(), k_bc_level, cs.list_grid(nfront), 256, tab, P, nn, cur, nfront, level, d_lv, d_sigma, d_hub, stamp, nxt,
                      d_cnt);
         },
         &sizes);
@@ -341,21 +367,21 @@ int Engine::centrality_over(const ConsumerRef *parts, uint32_t P, uint32_t total
         nn, d_lv, sizes, d_f0, d_cnt,
         [&](uint32_t level, bool hubs_only) {
           bits(level, hubs_only);
-          GPU_LAUNCH(p.stream, k_bc_edges_backward, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, level, (const uint32_t *)d_sb,
+          GPU_LAUNCH(cs.stream(), k_bc_edges_backward, cs.pass_grid(), 256, tab, P, nn, level, (const uint32_t *)d_sb,
                      (const uint32_t *)d_lv, (const double *)d_sigma, d_delta);
         },
         [&](const uint32_t *list, uint32_t nlist, uint32_t level) {
           stamp++;
-          GPU_LAUNCH(p.stream, k_bc_delta_vertex, grid_for(nlist, 4, 16384), 256, tab, P, nn, list, nlist, level, (const uint32_t *)d_lv,
+          GPU_LAUNCH(cs.stream(), k_bc_delta_vertex, cs.list_grid(nlist), 256, tab, P, nn, list, nlist, level, (const uint32_t *)d_lv,
                      (const double *)d_sigma, d_delta, d_hub, stamp, d_cnt);
         });
     if (rc != PPCSR_OK) return rc;
-    GPU_LAUNCH(p.stream, k_bc_accumulate, grid_for(nn, 256, 4096), 256, d_bc, (const double *)d_delta, nn, s);
+    GPU_LAUNCH(cs.stream(), k_bc_accumulate, cs.vert_grid(), 256, d_bc, (const double *)d_delta, nn, s);
   }
   cs.stop();
-  if (levels && nn) GCHK(gpu::d2h(levels, d_lv, (uint64_t)nn * sizeof(uint32_t), p.stream));
-  if (sigma && nn) GCHK(gpu::d2h(sigma, d_sigma, (uint64_t)nn * sizeof(double), p.stream));
-  if (bc && nn) GCHK(gpu::d2h(bc, d_bc, (uint64_t)nn * sizeof(double), p.stream));
+  if (levels && nn) GCHK(gpu::d2h(levels, d_lv, (uint64_t)nn * sizeof(uint32_t), cs.stream()));
+  if (sigma && nn) GCHK(gpu::d2h(sigma, d_sigma, (uint64_t)nn * sizeof(double), cs.stream()));
+  if (bc && nn) GCHK(gpu::d2h(bc, d_bc, (uint64_t)nn * sizeof(double), cs.stream()));
   return cs.done(device_ms);
 }
 int Engine::path_counts_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t start, uint32_t *levels, double *sigma,
@@ -380,10 +406,8 @@ int Engine::kcore_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, u
   ConsumerScope cs(this);
   const int rc = cs.open(parts, P, nn);
   if (rc != PPCSR_OK) return rc;
-  Impl &p = *p_;
   const ConsumerPart *tab = cs.table();
-  const uint64_t N = cs.slots();
-  const uint64_t words = std::max<uint64_t>(nn, 1);
+  const uint64_t words = cs.words();
   const uint32_t ntiles = (uint32_t)(((uint64_t)nn + kKcTile - 1) / kKcTile);
   uint32_t *d_deg = cs.alloc<uint32_t>("d_deg", words), *d_core = cs.alloc<uint32_t>("d_core", words), *d_fill = cs.alloc<uint32_t>("d_fill", words);
   uint32_t *d_f0 = cs.alloc<uint32_t>("d_f0", words), *d_f1 = cs.alloc<uint32_t>("d_f1", words);  // (a vertex enters one frontier once: no list exceeds n)
@@ -395,48 +419,44 @@ int Engine::kcore_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, u
   cs.start();
   if (nn) {
     // stage 1: deg[], off[] (off[nn] = 2 |E(G)|), adj[]
-    GCHK(gpu::dset(d_deg, 0, words * sizeof(uint32_t), p.stream));
-    GCHK(gpu::dset(d_fill, 0, words * sizeof(uint32_t), p.stream));
-    GPU_LAUNCH(p.stream, k_kc_init, grid_for(nn, 256, 4096), 256, d_core, nn);
-    GPU_LAUNCH(p.stream, k_kc_degree, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, d_deg);
-    GPU_LAUNCH(p.stream, k_kc_tile_sums, grid_for(ntiles, 1, 65536), 256, (const uint32_t *)d_deg, nn, ntiles, d_tiles);
-    GPU_LAUNCH(p.stream, k_kc_scan_tiles, 1, 64, d_tiles, ntiles, d_off + nn);
-    GPU_LAUNCH(p.stream, k_kc_scan_write, grid_for(ntiles, 1, 65536), 256, (const uint32_t *)d_deg, nn, ntiles, (const unsigned long long *)d_tiles, d_off);
+    GCHK(gpu::dset(d_deg, 0, words * sizeof(uint32_t), cs.stream()));
+    GCHK(gpu::dset(d_fill, 0, words * sizeof(uint32_t), cs.stream()));
+    GPU_LAUNCH(cs.stream(), k_kc_init, cs.vert_grid(), 256, d_core, nn);
+    GPU_LAUNCH(cs.stream(), k_kc_degree, cs.pass_grid(), 256, tab, P, nn, d_deg);
+    GPU_LAUNCH(cs.stream(), k_kc_tile_sums, grid_for(ntiles, 1, 65536), 256, (const uint32_t *)d_deg, nn, ntiles, d_tiles);
+    GPU_LAUNCH(cs.stream(), k_kc_scan_tiles, 1, 64, d_tiles, ntiles, d_off + nn);
+    GPU_LAUNCH(cs.stream(), k_kc_scan_write, grid_for(ntiles, 1, 65536), 256, (const uint32_t *)d_deg, nn, ntiles, (const unsigned long long *)d_tiles, d_off);
     unsigned long long entries = 0;
-    GCHK(gpu::d2h(&entries, d_off + nn, sizeof(entries), p.stream));
-    GCHK(gpu::sync(p.stream));
-    GCHK(gpu::last_error());
+    int e = cs.read_back(&entries, d_off + nn, sizeof(entries));
+    if (e != PPCSR_OK) return e;
     uint32_t *d_adj = cs.alloc<uint32_t>("d_adj", std::max<uint64_t>(entries, 1));
     if (cs.rc != PPCSR_OK) return cs.rc;
-    GPU_LAUNCH(p.stream, k_kc_fill, grid_for((N + 255) / 256, 4, 8192), 256, tab, P, nn, (const unsigned long long *)d_off, d_fill, d_adj);
+    GPU_LAUNCH(cs.stream(), k_kc_fill, cs.pass_grid(), 256, tab, P, nn, (const unsigned long long *)d_off, d_fill, d_adj);
     // stage 2
     uint32_t h_cnt[4] = {0, 0, 0, 0};  // (host copy of the three words of the counter block that are in use, padded to 16 bytes)
     uint32_t *cur = d_f0, *nxt = d_f1;
     for (;;) {
-      GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), p.stream));
-      GCHK(gpu::dset(d_cnt + 2, 0xFF, sizeof(uint32_t), p.stream));
-      GPU_LAUNCH(p.stream, k_kc_min, grid_for(nn, 256, 1024), 256, (const uint32_t *)d_deg, (const uint32_t *)d_core, nn, d_cnt);
-      GPU_LAUNCH(p.stream, k_kc_collect, grid_for(nn, 256), 256, (const uint32_t *)d_deg, d_core, nn, cur, d_cnt);
-      GCHK(gpu::d2h(h_cnt, d_cnt, 3 * sizeof(uint32_t), p.stream));
-      GCHK(gpu::sync(p.stream));
-      GCHK(gpu::last_error());
+      GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), cs.stream()));
+      GCHK(gpu::dset(d_cnt + 2, 0xFF, sizeof(uint32_t), cs.stream()));
+      GPU_LAUNCH(cs.stream(), k_kc_min, grid_for(nn, 256, 1024), 256, (const uint32_t *)d_deg, (const uint32_t *)d_core, nn, d_cnt);
+      GPU_LAUNCH(cs.stream(), k_kc_collect, grid_for(nn, 256), 256, (const uint32_t *)d_deg, d_core, nn, cur, d_cnt);
+      e = cs.read_back(h_cnt, d_cnt, 3 * sizeof(uint32_t));
+      if (e != PPCSR_OK) return e;
       uint32_t nfront = h_cnt[0];
       const uint32_t k = h_cnt[2];
       if (nfront == 0) break;  // (k == kMax: every vertex is assigned)
       top = k;
       while (nfront > 0) {
-        GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), p.stream));
-        GPU_LAUNCH(p.stream, k_kc_peel, grid_for(nfront, 4, 16384), 256, (const unsigned long long *)d_off, (const uint32_t *)d_adj, (const uint32_t *)cur,
+        GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), cs.stream()));
+        GPU_LAUNCH(cs.stream(), k_kc_peel, cs.list_grid(nfront), 256, (const unsigned long long *)d_off, (const uint32_t *)d_adj, (const uint32_t *)cur,
                    nfront, k, d_deg, d_core, nxt, d_long, d_cnt);
-        GCHK(gpu::d2h(h_cnt, d_cnt, 2 * sizeof(uint32_t), p.stream));
-        GCHK(gpu::sync(p.stream));
-        GCHK(gpu::last_error());
+        e = cs.read_back(h_cnt, d_cnt, 2 * sizeof(uint32_t));
+        if (e != PPCSR_OK) return e;
         if (h_cnt[1]) {  // lists beyond one wave's reach: a second launch splits them over waves and appends to the same frontier
-          GPU_LAUNCH(p.stream, k_kc_peel_long, grid_for((uint64_t)h_cnt[1] * 16, 4, 4096), 256, (const unsigned long long *)d_off, (const uint32_t *)d_adj,
+          GPU_LAUNCH(cs.stream(), k_kc_peel_long, grid_for((uint64_t)h_cnt[1] * 16, 4, 4096), 256, (const unsigned long long *)d_off, (const uint32_t *)d_adj,
                      (const uint32_t *)d_long, h_cnt[1], k, d_deg, d_core, nxt, d_cnt);
-          GCHK(gpu::d2h(h_cnt, d_cnt, sizeof(uint32_t), p.stream));
-          GCHK(gpu::sync(p.stream));
-          GCHK(gpu::last_error());
+          e = cs.read_back(h_cnt, d_cnt, sizeof(uint32_t));
+          if (e != PPCSR_OK) return e;
         }
         nfront = h_cnt[0];
         std::swap(cur, nxt);
@@ -444,7 +464,7 @@ int Engine::kcore_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, u
     }
   }
   cs.stop();
-  if (core && nn) GCHK(gpu::d2h(core, d_core, (uint64_t)nn * sizeof(uint32_t), p.stream));
+  if (core && nn) GCHK(gpu::d2h(core, d_core, (uint64_t)nn * sizeof(uint32_t), cs.stream()));
   if (kmax) *kmax = top;
   return cs.done(device_ms);
 }
@@ -458,35 +478,31 @@ int Engine::scc_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uin
   ConsumerScope cs(this);
   const int rc = cs.open(parts, P, nn);
   if (rc != PPCSR_OK) return rc;
-  Impl &p = *p_;
   const ConsumerPart *tab = cs.table();
-  const uint64_t N = cs.slots();
-  const uint64_t words = std::max<uint64_t>(nn, 1);
+  const uint64_t words = cs.words();
   const uint64_t bit_words = std::max<uint64_t>(((uint64_t)nn + 63) / 64 * 2, 2);
-  constexpr uint32_t cnt_words = kBfsStripes * kSccStripeWords;
   uint32_t *d_scc = cs.alloc<uint32_t>("d_scc", words), *d_col = cs.alloc<uint32_t>("d_col", words), *d_live = cs.alloc<uint32_t>("d_live", bit_words);
   uint8_t *d_out = cs.alloc<uint8_t>("d_out", words), *d_in = cs.alloc<uint8_t>("d_in", words);  // has_out / has_in of a trim sweep
   uint8_t *d_fw = cs.alloc<uint8_t>("d_fw", words), *d_bw = cs.alloc<uint8_t>("d_bw", words);    // marks of a reach
-  unsigned long long *d_cnt = cs.alloc<unsigned long long>("d_cnt", cnt_words);
+  ConsumerScope::Striped<unsigned long long, kSccStripeWords> cnt(cs, "d_cnt");
+  unsigned long long *const d_cnt = cnt.dev;
   unsigned long long *d_aux = cs.alloc<unsigned long long>("d_aux", 2);  // [0]: the pivot's key, [1]: the label of its SCC (low word)
   if (cs.rc != PPCSR_OK) return cs.rc;
-  std::vector<unsigned long long> h_cnt(cnt_words, 0);
   uint64_t ctr[8] = {0, 0, UINT64_MAX, 0, 0, 0, 0, 0};
   uint64_t &passes = ctr[6], &reads = ctr[7];
   uint64_t live = nn, sccs = 0;
-  const uint32_t pass_grid = grid_for((N + 255) / 256, 4, 8192), vert_grid = grid_for(nn, 256, 4096);
-  // the striped count of the launches since zero(): low and high halves summed apart (k_scc_reach_*)
-  const auto zero = [&]() { return gpu::dset(d_cnt, 0, cnt_words * sizeof(unsigned long long), p.stream); };
+  const uint32_t pass_grid = cs.pass_grid(), vert_grid = cs.vert_grid();
+  // the striped count of the launches since zero(): its low and high halves.  (k_scc_reach_*: a pass makes fewer than 2^32
+  // stores per direction — the bound the kernels' own 64-bit adds rest on — so the stripes' sum carries nothing from the low
+  // half into the high one either.)
+  const auto zero = [&]() { return cnt.zero(); };
   const auto read = [&](uint64_t *lo, uint64_t *hi) {
-    GCHK(gpu::d2h(h_cnt.data(), d_cnt, cnt_words * sizeof(unsigned long long), p.stream));
-    GCHK(gpu::sync(p.stream));
-    GCHK(gpu::last_error());
+    const int e = cnt.read();
+    if (e != PPCSR_OK) return e;
     reads++;
-    *lo = *hi = 0;
-    for (uint32_t k = 0; k < kBfsStripes; k++) {
-      *lo += h_cnt[(uint64_t)k * kSccStripeWords] & 0xFFFFFFFFull;
-      *hi += h_cnt[(uint64_t)k * kSccStripeWords] >> 32;
-    }
+    const uint64_t all = cnt.sum();
+    *lo = all & 0xFFFFFFFFull;
+    *hi = all >> 32;
     return (int)PPCSR_OK;
   };
   const auto spinning = [&]() { return fail(PPCSR_EHIP, "scc: a loop made more passes than the graph has vertices"); };
@@ -494,8 +510,8 @@ int Engine::scc_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uin
     for (uint64_t sweep = 0, got = 1, hi = 0; live > 0 && got > 0; sweep++) {
       if (sweep > (uint64_t)nn + 1) return spinning();
       GCHK(zero());
-      GPU_LAUNCH(p.stream, k_scc_trim_edges, pass_grid, 256, tab, P, nn, (const uint32_t *)d_live, d_out, d_in);
-      GPU_LAUNCH(p.stream, k_scc_trim_retire, vert_grid, 256, d_scc, nn, d_out, d_in, d_live, d_cnt);
+      GPU_LAUNCH(cs.stream(), k_scc_trim_edges, pass_grid, 256, tab, P, nn, (const uint32_t *)d_live, d_out, d_in);
+      GPU_LAUNCH(cs.stream(), k_scc_trim_retire, vert_grid, 256, d_scc, nn, d_out, d_in, d_live, d_cnt);
       passes++;
       ctr[1]++;
       const int e = read(&got, &hi);
@@ -507,37 +523,36 @@ int Engine::scc_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uin
   };
   cs.start();
   if (nn) {
-    GCHK(gpu::dset(d_scc, 0xFF, words * sizeof(uint32_t), p.stream));
-    GCHK(gpu::dset(d_live, 0xFF, bit_words * sizeof(uint32_t), p.stream));
-    GCHK(gpu::dset(d_out, 0, words, p.stream));
-    GCHK(gpu::dset(d_in, 0, words, p.stream));
+    GCHK(gpu::dset(d_scc, 0xFF, words * sizeof(uint32_t), cs.stream()));
+    GCHK(gpu::dset(d_live, 0xFF, bit_words * sizeof(uint32_t), cs.stream()));
+    GCHK(gpu::dset(d_out, 0, words, cs.stream()));
+    GCHK(gpu::dset(d_in, 0, words, cs.stream()));
     int e = trim();
     if (e != PPCSR_OK) return e;
     if (live > 0) {  // forward-backward from the pivot
       unsigned long long h_aux[2] = {0, 0xFFFFFFFFull};
-      GCHK(gpu::h2d(d_aux, h_aux, sizeof(h_aux), p.stream));
-      GPU_LAUNCH(p.stream, k_scc_pivot, grid_for(nn, 256, 512), 256, tab, P, nn, (const uint32_t *)d_live, d_aux);
-      GPU_LAUNCH(p.stream, k_scc_marks, vert_grid, 256, (const uint32_t *)d_scc, nn, (const uint32_t *)nullptr, d_fw, d_bw);
-      GCHK(gpu::d2h(h_aux, d_aux, sizeof(unsigned long long), p.stream));
-      GCHK(gpu::sync(p.stream));
-      GCHK(gpu::last_error());
+      GCHK(gpu::h2d(d_aux, h_aux, sizeof(h_aux), cs.stream()));
+      GPU_LAUNCH(cs.stream(), k_scc_pivot, grid_for(nn, 256, 512), 256, tab, P, nn, (const uint32_t *)d_live, d_aux);
+      GPU_LAUNCH(cs.stream(), k_scc_marks, vert_grid, 256, (const uint32_t *)d_scc, nn, (const uint32_t *)nullptr, d_fw, d_bw);
+      e = cs.read_back(h_aux, d_aux, sizeof(unsigned long long));
+      if (e != PPCSR_OK) return e;
       reads++;
       const uint32_t pivot = 0xFFFFFFFFu - (uint32_t)h_aux[0];
       if (h_aux[0] == 0 || pivot >= nn) return fail(PPCSR_EHIP, "scc: no pivot among the live vertices");
       ctr[2] = pivot;
       const uint8_t marked = kSccMarked;
-      GCHK(gpu::h2d(d_fw + pivot, &marked, 1, p.stream));
-      GCHK(gpu::h2d(d_bw + pivot, &marked, 1, p.stream));
+      GCHK(gpu::h2d(d_fw + pivot, &marked, 1, cs.stream()));
+      GCHK(gpu::h2d(d_bw + pivot, &marked, 1, cs.stream()));
       bool fw_open = true, bw_open = true;
       for (uint64_t it = 0; fw_open || bw_open; it++) {
         if (it > (uint64_t)nn + 1) return spinning();
         GCHK(zero());
         if (fw_open && bw_open)
-          GPU_LAUNCH(p.stream, k_scc_reach_both, pass_grid, 256, tab, P, nn, d_fw, d_bw, d_cnt);
+          GPU_LAUNCH(cs.stream(), k_scc_reach_both, pass_grid, 256, tab, P, nn, d_fw, d_bw, d_cnt);
         else if (fw_open)
-          GPU_LAUNCH(p.stream, k_scc_reach_fw, pass_grid, 256, tab, P, nn, d_fw, d_cnt);
+          GPU_LAUNCH(cs.stream(), k_scc_reach_fw, pass_grid, 256, tab, P, nn, d_fw, d_cnt);
         else
-          GPU_LAUNCH(p.stream, k_scc_reach_bw, pass_grid, 256, tab, P, nn, d_bw, d_cnt);
+          GPU_LAUNCH(cs.stream(), k_scc_reach_bw, pass_grid, 256, tab, P, nn, d_bw, d_cnt);
         passes++;
         uint64_t f = 0, b = 0;
         e = read(&f, &b);
@@ -546,8 +561,8 @@ int Engine::scc_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uin
         bw_open = bw_open && b > 0;
       }
       GCHK(zero());
-      GPU_LAUNCH(p.stream, k_scc_min, grid_for(nn, 256, 512), 256, (const uint8_t *)d_fw, (const uint8_t *)d_bw, nn, (uint32_t *)(d_aux + 1));
-      GPU_LAUNCH(p.stream, k_scc_assign, vert_grid, 256, (const uint8_t *)d_fw, (const uint8_t *)d_bw, nn, (const uint32_t *)nullptr,
+      GPU_LAUNCH(cs.stream(), k_scc_min, grid_for(nn, 256, 512), 256, (const uint8_t *)d_fw, (const uint8_t *)d_bw, nn, (uint32_t *)(d_aux + 1));
+      GPU_LAUNCH(cs.stream(), k_scc_assign, vert_grid, 256, (const uint8_t *)d_fw, (const uint8_t *)d_bw, nn, (const uint32_t *)nullptr,
                  (const uint32_t *)(d_aux + 1), d_scc, d_live, d_cnt);
       uint64_t got = 0, hi = 0;
       e = read(&got, &hi);
@@ -560,26 +575,26 @@ int Engine::scc_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uin
     }
     while (live > 0) {  // one colouring round
       ctr[4]++;
-      GPU_LAUNCH(p.stream, k_scc_colour_init, vert_grid, 256, (const uint32_t *)d_scc, nn, d_col);
+      GPU_LAUNCH(cs.stream(), k_scc_colour_init, vert_grid, 256, (const uint32_t *)d_scc, nn, d_col);
       for (uint64_t it = 0, got = 1, hi = 0; got > 0; it++) {
         if (it > (uint64_t)nn + 1) return spinning();
         GCHK(zero());
-        GPU_LAUNCH(p.stream, k_scc_colour_prop, pass_grid, 256, tab, P, nn, (const uint32_t *)d_live, d_col, d_cnt);
+        GPU_LAUNCH(cs.stream(), k_scc_colour_prop, pass_grid, 256, tab, P, nn, (const uint32_t *)d_live, d_col, d_cnt);
         passes++;
         e = read(&got, &hi);
         if (e != PPCSR_OK) return e;
       }
-      GPU_LAUNCH(p.stream, k_scc_marks, vert_grid, 256, (const uint32_t *)d_scc, nn, (const uint32_t *)d_col, (uint8_t *)nullptr, d_bw);
+      GPU_LAUNCH(cs.stream(), k_scc_marks, vert_grid, 256, (const uint32_t *)d_scc, nn, (const uint32_t *)d_col, (uint8_t *)nullptr, d_bw);
       for (uint64_t it = 0, lo = 0, got = 1; got > 0; it++) {
         if (it > (uint64_t)nn + 1) return spinning();
         GCHK(zero());
-        GPU_LAUNCH(p.stream, k_scc_reach_colour, pass_grid, 256, tab, P, nn, (const uint32_t *)d_col, d_bw, d_cnt);
+        GPU_LAUNCH(cs.stream(), k_scc_reach_colour, pass_grid, 256, tab, P, nn, (const uint32_t *)d_col, d_bw, d_cnt);
         passes++;
         e = read(&lo, &got);
         if (e != PPCSR_OK) return e;
       }
       GCHK(zero());
-      GPU_LAUNCH(p.stream, k_scc_assign, vert_grid, 256, (const uint8_t *)nullptr, (const uint8_t *)d_bw, nn, (const uint32_t *)d_col,
+      GPU_LAUNCH(cs.stream(), k_scc_assign, vert_grid, 256, (const uint8_t *)nullptr, (const uint8_t *)d_bw, nn, (const uint32_t *)d_col,
                  (const uint32_t *)nullptr, d_scc, d_live, d_cnt);
       uint64_t got = 0, hi = 0;
       e = read(&got, &hi);
@@ -592,18 +607,18 @@ int Engine::scc_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uin
     }
     if (count) {
       GCHK(zero());
-      GPU_LAUNCH(p.stream, k_scc_count, vert_grid, 256, (const uint32_t *)d_scc, nn, d_cnt);
+      GPU_LAUNCH(cs.stream(), k_scc_count, vert_grid, 256, (const uint32_t *)d_scc, nn, d_cnt);
       uint64_t hi = 0;
       e = read(&sccs, &hi);
       if (e != PPCSR_OK) return e;
     }
   }
   cs.stop();
-  if (labels && nn) GCHK(gpu::d2h(labels, d_scc, (uint64_t)nn * sizeof(uint32_t), p.stream));
+  if (labels && nn) GCHK(gpu::d2h(labels, d_scc, (uint64_t)nn * sizeof(uint32_t), cs.stream()));
   const int done = cs.done(device_ms);
   if (done != PPCSR_OK) return done;
   if (count) *count = sccs;
-  for (int i = 0; i < 8; i++) p.scc_ctr[i] = ctr[i];
+  for (int i = 0; i < 8; i++) p_->scc_ctr[i] = ctr[i];
   return PPCSR_OK;
 }
 int Engine::scc_counters(uint64_t out[8]) {
@@ -617,41 +632,36 @@ int Engine::scc_counters(uint64_t out[8]) {
 // launch (the first of them brings the round's hooks along), then the reset.  So passes = 2 * rounds - 1: the last round makes
 // the first pass only.  The striped counters are cleared once and read as running totals.  Every component with a cut edge
 // merges, so more than floor(log2 n) + 2 rounds, a round that hooks nothing or a doubling of more than 34 launches is reported
-// as an error instead of spinning.  The edge list is sorted by lo << 32 | hi on the device (rocPRIM; std::sort in the emulator).
+// as an error instead of spinning.  The edge list is sorted by lo << 32 | hi on the device (sort_pairs_stable: the keys are unique).
 int Engine::msf_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, Edge *edges, uint64_t cap, uint64_t *count, uint64_t *weight,
                      uint32_t *labels, double *device_ms) {
   const uint32_t nn = total_n;
   ConsumerScope cs(this);
   const int rc = cs.open(parts, P, nn);
   if (rc != PPCSR_OK) return rc;
-  Impl &p = *p_;
   const ConsumerPart *tab = cs.table();
-  const uint64_t N = cs.slots();
-  const uint64_t words = std::max<uint64_t>(nn, 1);
-  constexpr uint32_t cnt_words = kBfsStripes * kMsfStripeWords;
+  const uint64_t words = cs.words();
   uint32_t *d_comp = cs.alloc<uint32_t>("d_comp", words), *d_par = cs.alloc<uint32_t>("d_par", words), *d_bw = cs.alloc<uint32_t>("d_bw", words);
   unsigned long long *d_bp = cs.alloc<unsigned long long>("d_bp", words);
   unsigned long long *d_k0 = cs.alloc<unsigned long long>("d_k0", words), *d_k1 = cs.alloc<unsigned long long>("d_k1", words);  // the list: keys
   uint32_t *d_w0 = cs.alloc<uint32_t>("d_w0", words), *d_w1 = cs.alloc<uint32_t>("d_w1", words);                                  // and weights
   Edge *d_out = edges ? cs.alloc<Edge>("d_out", words) : nullptr;
-  unsigned long long *d_cnt = cs.alloc<unsigned long long>("d_cnt", cnt_words);
+  ConsumerScope::Striped<unsigned long long, kMsfStripeWords> cnt(cs, "d_cnt");
+  unsigned long long *const d_cnt = cnt.dev;
   uint32_t *d_ne = cs.alloc<uint32_t>("d_ne", 2);  // the length of the list
   if (cs.rc != PPCSR_OK) return cs.rc;
-  std::vector<unsigned long long> h_cnt(cnt_words, 0);
   uint64_t ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t &rounds = ctr[0], &passes = ctr[1], &reads = ctr[7];
   uint64_t tot[3] = {0, 0, 0};  // running totals of the three counter words, as of the last read
   uint64_t m = 0;
-  const uint32_t pass_grid = grid_for((N + 255) / 256, 4, 8192), vert_grid = grid_for(nn, 256, 4096);
+  const uint32_t pass_grid = cs.pass_grid(), vert_grid = cs.vert_grid();
   // the counters' growth since the last read: [0] cut edges / pointers moved, [1] hooks, [2] weight
   const auto read = [&](uint64_t grew[3]) {
-    GCHK(gpu::d2h(h_cnt.data(), d_cnt, cnt_words * sizeof(unsigned long long), p.stream));
-    GCHK(gpu::sync(p.stream));
-    GCHK(gpu::last_error());
+    const int e = cnt.read();
+    if (e != PPCSR_OK) return e;
     reads++;
     for (uint32_t w = 0; w < 3; w++) {
-      uint64_t now = 0;
-      for (uint32_t k = 0; k < kBfsStripes; k++) now += h_cnt[(uint64_t)k * kMsfStripeWords + w];
+      const uint64_t now = cnt.sum(w);
       grew[w] = now - tot[w];
       tot[w] = now;
     }
@@ -661,27 +671,27 @@ int Engine::msf_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, Edg
   while (((uint64_t)nn >> (max_rounds - 1)) != 0) max_rounds++;
   cs.start();
   if (nn) {
-    GCHK(gpu::dset(d_cnt, 0, cnt_words * sizeof(unsigned long long), p.stream));
-    GCHK(gpu::dset(d_ne, 0, 2 * sizeof(uint32_t), p.stream));
-    GPU_LAUNCH(p.stream, k_cc_init, vert_grid, 256, d_par, nn);
-    GPU_LAUNCH(p.stream, k_msf_reset, vert_grid, 256, d_comp, (const uint32_t *)d_par, d_bw, d_bp, nn);
+    GCHK(cnt.zero());
+    GCHK(gpu::dset(d_ne, 0, 2 * sizeof(uint32_t), cs.stream()));
+    GPU_LAUNCH(cs.stream(), k_cc_init, vert_grid, 256, d_par, nn);
+    GPU_LAUNCH(cs.stream(), k_msf_reset, vert_grid, 256, d_comp, (const uint32_t *)d_par, d_bw, d_bp, nn);
     for (;;) {
       if (rounds >= max_rounds) return fail(PPCSR_EHIP, "msf: more rounds than halving the components allows");
       uint64_t grew[3];
-      GPU_LAUNCH(p.stream, k_msf_weight, pass_grid, 256, tab, P, nn, (const uint32_t *)d_comp, d_bw, d_cnt);
+      GPU_LAUNCH(cs.stream(), k_msf_weight, pass_grid, 256, tab, P, nn, (const uint32_t *)d_comp, d_bw, d_cnt);
       passes++;
       rounds++;
       int e = read(grew);
       if (e != PPCSR_OK) return e;
       if (grew[0] == 0) break;
-      GPU_LAUNCH(p.stream, k_msf_pair, pass_grid, 256, tab, P, nn, (const uint32_t *)d_comp, d_bw, d_bp);
+      GPU_LAUNCH(cs.stream(), k_msf_pair, pass_grid, 256, tab, P, nn, (const uint32_t *)d_comp, d_bw, d_bp);
       passes++;
-      GPU_LAUNCH(p.stream, k_msf_hook, vert_grid, 256, (const uint32_t *)d_comp, d_par, (const uint32_t *)d_bw, (const unsigned long long *)d_bp, nn,
+      GPU_LAUNCH(cs.stream(), k_msf_hook, vert_grid, 256, (const uint32_t *)d_comp, d_par, (const uint32_t *)d_bw, (const unsigned long long *)d_bp, nn,
                  d_k0, d_w0, d_ne, d_cnt);
       uint64_t hooks = 0, jumps = 0;
       for (uint64_t moved = 1; moved > 0;) {
         if (jumps > 34) return fail(PPCSR_EHIP, "msf: pointer doubling did not end");
-        GPU_LAUNCH(p.stream, k_msf_jump, vert_grid, 256, d_par, nn, d_cnt);
+        GPU_LAUNCH(cs.stream(), k_msf_jump, vert_grid, 256, d_par, nn, d_cnt);
         jumps++;
         e = read(grew);
         if (e != PPCSR_OK) return e;
@@ -693,50 +703,36 @@ int Engine::msf_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, Edg
       ctr[3] = std::max(ctr[3], jumps);
       if (rounds == 1) ctr[4] = hooks;
       ctr[5] += hooks;
-      GPU_LAUNCH(p.stream, k_msf_reset, vert_grid, 256, d_comp, (const uint32_t *)d_par, d_bw, d_bp, nn);
+      GPU_LAUNCH(cs.stream(), k_msf_reset, vert_grid, 256, d_comp, (const uint32_t *)d_par, d_bw, d_bp, nn);
     }
     // finish: labels (d_bw is all kMax: the last reset, and a pass without cut edges stores nothing), the length, the sort
-    GPU_LAUNCH(p.stream, k_msf_label_min, vert_grid, 256, (const uint32_t *)d_comp, d_bw, nn);
-    GPU_LAUNCH(p.stream, k_msf_label_assign, vert_grid, 256, (const uint32_t *)d_comp, (const uint32_t *)d_bw, d_par, nn);
+    GPU_LAUNCH(cs.stream(), k_msf_label_min, vert_grid, 256, (const uint32_t *)d_comp, d_bw, nn);
+    GPU_LAUNCH(cs.stream(), k_msf_label_assign, vert_grid, 256, (const uint32_t *)d_comp, (const uint32_t *)d_bw, d_par, nn);
     uint32_t h_ne = 0;
-    GCHK(gpu::d2h(&h_ne, d_ne, sizeof(uint32_t), p.stream));
-    GCHK(gpu::sync(p.stream));
-    GCHK(gpu::last_error());
+    const int e = cs.read_back(&h_ne, d_ne, sizeof(uint32_t));
+    if (e != PPCSR_OK) return e;
     reads++;
     m = h_ne;
     if (m != ctr[5]) return fail(PPCSR_EHIP, "msf: the edge list and the hook counts disagree");
     if (edges && m) {
-#if defined(PPCSR_SIM)
-      std::vector<uint64_t> idx(m);
-      for (uint64_t i = 0; i < m; i++) idx[i] = i;
-      std::sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) { return d_k0[a] < d_k0[b]; });
-      for (uint64_t i = 0; i < m; i++) {
-        d_k1[i] = d_k0[idx[i]];
-        d_w1[i] = d_w0[idx[i]];
-      }
-#else
       unsigned bits = 33;  // keys are below n << 32
       while (bits < 64 && ((uint64_t)nn >> (bits - 32)) != 0) bits++;
-      size_t tmp_bytes = 0;
-      if (rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_k0, d_k1, d_w0, d_w1, (size_t)m, 0u, bits, p.stream) != hipSuccess)
-        return fail(PPCSR_EHIP, "msf: device sort failed");
-      uint8_t *d_tmp = cs.alloc<uint8_t>("d_tmp", std::max<uint64_t>(tmp_bytes, 1));
-      if (cs.rc != PPCSR_OK) return cs.rc;
-      if (rocprim::radix_sort_pairs(d_tmp, tmp_bytes, d_k0, d_k1, d_w0, d_w1, (size_t)m, 0u, bits, p.stream) != hipSuccess)
-        return fail(PPCSR_EHIP, "msf: device sort failed");
-#endif
-      GPU_LAUNCH(p.stream, k_msf_pack, grid_for(m, 256, 4096), 256, (const unsigned long long *)d_k1, (const uint32_t *)d_w1, m, d_out);
+      const int sorted = sort_pairs_stable(cs.stream(), d_k0, d_k1, d_w0, d_w1, m, bits,
+                                           [&](size_t bytes) { return cs.alloc<uint8_t>("d_tmp", std::max<uint64_t>(bytes, 1)); });
+      if (sorted == 2) return cs.rc;
+      if (sorted != 0) return fail(PPCSR_EHIP, "msf: device sort failed");
+      GPU_LAUNCH(cs.stream(), k_msf_pack, grid_for(m, 256, 4096), 256, (const unsigned long long *)d_k1, (const uint32_t *)d_w1, m, d_out);
     }
   }
   cs.stop();
-  if (edges && m && cap) GCHK(gpu::d2h(edges, d_out, std::min<uint64_t>(cap, m) * sizeof(Edge), p.stream));
-  if (labels && nn) GCHK(gpu::d2h(labels, d_par, (uint64_t)nn * sizeof(uint32_t), p.stream));
+  if (edges && m && cap) GCHK(gpu::d2h(edges, d_out, std::min<uint64_t>(cap, m) * sizeof(Edge), cs.stream()));
+  if (labels && nn) GCHK(gpu::d2h(labels, d_par, (uint64_t)nn * sizeof(uint32_t), cs.stream()));
   const int done = cs.done(device_ms);
   if (done != PPCSR_OK) return done;
   if (count) *count = m;
   if (weight) *weight = tot[2];
   ctr[6] = (uint64_t)nn - m;
-  for (int i = 0; i < 8; i++) p.msf_ctr[i] = ctr[i];
+  for (int i = 0; i < 8; i++) p_->msf_ctr[i] = ctr[i];
   return (edges && cap < m) ? PPCSR_ERANGE : PPCSR_OK;
 }
 int Engine::msf_counters(uint64_t out[8]) {
@@ -751,36 +747,30 @@ int Engine::triangles_over(const ConsumerRef *parts, uint32_t P, uint32_t total_
   ConsumerScope cs(this);
   int rc = cs.open(parts, P, nn, "triangles");
   if (rc != PPCSR_OK) return rc;
-  Impl &p = *p_;
   const ConsumerPart *tab = cs.table();
   uint64_t chunks = 0;
   for (uint32_t k = 0; k < P; k++) chunks += (parts[k].e->N() + 63) / 64;
   if (chunks >= (1ull << 32)) return fail(PPCSR_EUNSUPPORTED, "triangles: more than 2^32 chunks");
-  constexpr uint32_t tot_words = kBfsStripes * kTriStripeWords;
-  unsigned long long *d_tri = tri ? cs.alloc<unsigned long long>("d_tri", std::max<uint64_t>(nn, 1)) : nullptr;
-  unsigned long long *d_tot = cs.alloc<unsigned long long>("d_tot", tot_words);
+  unsigned long long *d_tri = tri ? cs.alloc<unsigned long long>("d_tri", cs.words()) : nullptr;
+  ConsumerScope::Striped<unsigned long long, kTriStripeWords> tot(cs, "d_tot");
+  unsigned long long *const d_tot = tot.dev;
   uint32_t *d_list = cs.alloc<uint32_t>("d_list", std::max<uint64_t>(chunks, 1));  // chunks that hold an edge with a long range
   uint32_t *d_cnt = cs.alloc<uint32_t>("d_cnt", 32);
   if (cs.rc != PPCSR_OK) return cs.rc;
   cs.start();
-  if (tri) GCHK(gpu::dset(d_tri, 0, std::max<uint64_t>(nn, 1) * sizeof(unsigned long long), p.stream));
-  GCHK(gpu::dset(d_tot, 0, tot_words * sizeof(unsigned long long), p.stream));
-  GCHK(gpu::dset(d_cnt, 0, 32 * sizeof(uint32_t), p.stream));
-  GPU_LAUNCH(p.stream, k_tri_edges, grid_for(chunks, 4, 8192), 256, tab, P, nn, d_tri, d_tot, d_list, d_cnt);
+  if (tri) GCHK(gpu::dset(d_tri, 0, cs.words() * sizeof(unsigned long long), cs.stream()));
+  GCHK(tot.zero());
+  GCHK(gpu::dset(d_cnt, 0, 32 * sizeof(uint32_t), cs.stream()));
+  GPU_LAUNCH(cs.stream(), k_tri_edges, grid_for(chunks, 4, 8192), 256, tab, P, nn, d_tri, d_tot, d_list, d_cnt);
   uint32_t ndefer = 0;
-  GCHK(gpu::d2h(&ndefer, d_cnt, sizeof(uint32_t), p.stream));
-  GCHK(gpu::sync(p.stream));
-  GCHK(gpu::last_error());
-  if (ndefer) GPU_LAUNCH(p.stream, k_tri_long, grid_for((uint64_t)ndefer * 4, 1, 16384), 256, tab, P, nn, d_tri, d_tot, (const uint32_t *)d_list, ndefer);
+  rc = cs.read_back(&ndefer, d_cnt, sizeof(uint32_t));
+  if (rc != PPCSR_OK) return rc;
+  if (ndefer) GPU_LAUNCH(cs.stream(), k_tri_long, grid_for((uint64_t)ndefer * 4, 1, 16384), 256, tab, P, nn, d_tri, d_tot, (const uint32_t *)d_list, ndefer);
   cs.stop();
-  std::vector<unsigned long long> h_tot(tot_words, 0);
-  GCHK(gpu::d2h(h_tot.data(), d_tot, tot_words * sizeof(unsigned long long), p.stream));
-  if (tri && nn) GCHK(gpu::d2h(tri, d_tri, (uint64_t)nn * sizeof(unsigned long long), p.stream));
+  GCHK(gpu::d2h(tot.host.data(), d_tot, sizeof(unsigned long long) * tot.kCount, cs.stream()));  // (waited for by done(), with the counts)
+  if (tri && nn) GCHK(gpu::d2h(tri, d_tri, (uint64_t)nn * sizeof(unsigned long long), cs.stream()));
   rc = cs.done(device_ms);
-  if (rc == PPCSR_OK && total) {
-    *total = 0;
-    for (uint32_t k = 0; k < kBfsStripes; k++) *total += h_tot[(uint64_t)k * kTriStripeWords];
-  }
+  if (rc == PPCSR_OK && total) *total = tot.sum();
   return rc;
 }
 
@@ -823,31 +813,6 @@ int Engine::common_neighbours_over(const ConsumerRef *parts, uint32_t P, uint32_
     if (device_ms) *device_ms += p.timer.ms();
   }
   return cs.done(nullptr);
-}
-
-// stable sort of (key, value) pairs by key: rocPRIM's radix sort on the device, std::stable_sort in the CPU emulator
-static int sort_pairs_stable(gpu::stream_t st, uint32_t *kin, uint32_t *kout, float *vin, float *vout, uint64_t m, unsigned bits) {
-#if defined(PPCSR_SIM)
-  (void)st;
-  (void)bits;
-  std::vector<uint64_t> idx(m);
-  for (uint64_t i = 0; i < m; i++) idx[i] = i;
-  std::stable_sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) { return kin[a] < kin[b]; });
-  for (uint64_t i = 0; i < m; i++) {
-    kout[i] = kin[idx[i]];
-    vout[i] = vin[idx[i]];
-  }
-  return 0;
-#else
-  size_t tmp_bytes = 0;
-  if (rocprim::radix_sort_pairs(nullptr, tmp_bytes, kin, kout, vin, vout, (size_t)m, 0u, bits, st) != hipSuccess) return 3;
-  void *tmp = nullptr;
-  if (hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 1) != hipSuccess) return 2;
-  const hipError_t e = rocprim::radix_sort_pairs(tmp, tmp_bytes, kin, kout, vin, vout, (size_t)m, 0u, bits, st);
-  (void)hipStreamSynchronize(st);
-  (void)hipFree(tmp);
-  return e == hipSuccess ? 0 : 3;
-#endif
 }
 
 // pagerank.h:15-29: out[d] = sum over edges (s, d), in ascending s, of node_values[s] / num_neighbors(s).  The bulk scan

@@ -22,10 +22,9 @@ PMA_DEV void bc_atomic_add(double *p, double v) {
 #endif
 }
 PMA_DEV double bc_shfl(double v, int src) {
-  uint64_t b;
+  unsigned long long b;
   __builtin_memcpy(&b, &v, 8);
-  const uint32_t lo = wv::shfl((uint32_t)b, src), hi = wv::shfl((uint32_t)(b >> 32), src);
-  b = ((uint64_t)hi << 32) | lo;
+  b = cp_shfl(b, src);
   __builtin_memcpy(&v, &b, 8);
   return v;
 }
@@ -34,7 +33,6 @@ PMA_DEV double bc_reduce(double v, int lane) {
   for (int d = 1; d < 64; d <<= 1) v += bc_shfl(v, lane ^ d);
   return v;
 }
-PMA_DEV bool bc_bit(const uint32_t *bits, uint32_t v) { return ((bits[v >> 5] >> (v & 31u)) & 1u) != 0u; }
 
 constexpr uint32_t kBcNoStamp = 0xFFFFFFFFu;
 
@@ -61,11 +59,8 @@ PMA_KERNEL void k_bc_bits(const uint32_t *levels, const uint32_t *hub_stamp, uin
     const uint64_t u = base + (uint64_t)lane;
     const uint32_t lv = u < n ? levels[u] : kMax;
     const bool is_src = stamp == kBcNoStamp ? lv == level : (u < n && hub_stamp[u] == stamp);
-    const uint64_t ms = wv::ballot(u < n && is_src), mp = wv::ballot(u < n && lv <= level);
-    if (lane < 2) {
-      src_bits[(base >> 5) + lane] = (uint32_t)(ms >> (32 * lane));
-      placed_bits[(base >> 5) + lane] = (uint32_t)(mp >> (32 * lane));
-    }
+    cp_store_bits(src_bits, base, wv::ballot(u < n && is_src), lane);
+    cp_store_bits(placed_bits, base, wv::ballot(u < n && lv <= level), lane);
   }
 }
 
@@ -86,56 +81,34 @@ PMA_DEV bool bc_forward_edge(double sv, uint32_t dst, uint32_t level, uint32_t l
 PMA_KERNEL void k_bc_level(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, const uint32_t *front, uint32_t nfront, uint32_t level,
                            uint32_t *levels, double *sigma, uint32_t *hub_stamp, uint32_t stamp, uint32_t *next, uint32_t *next_count) {
   const int lane = wv::lane();
-  const uint64_t wstride = cp_waves();
-  const Edge *const items0 = tab[0].items;
-  const Node *const nodes0 = tab[0].nodes;
-  for (uint64_t f = cp_wave(); f < nfront; f += wstride) {
-    const uint32_t u = wv::uni(front[f]);
-    const Edge *items;
-    Node nd;
-    if (!cp_frontier_vertex(tab, P, items0, nodes0, u, lane, &next_count[1], items, nd)) {  // (k_bc_edges_forward)
-      if (lane == 0) hub_stamp[u] = stamp;
-      continue;
-    }
-    const double su = sigma[u];
-    for (uint64_t base = (uint64_t)nd.beginning + 1; base < (uint64_t)nd.end; base += 64) {
-      const uint64_t s = base + (uint64_t)lane;
-      uint32_t val = 0, dst = 0;
-      if (s < (uint64_t)nd.end) {
-        val = items[s].value;
-        dst = items[s].dest;
-      }
-      bool won = false;
-      if (val != 0 && dst < n) won = bc_forward_edge(su, dst, level, levels[dst], levels, sigma);
-      cp_append(won, dst, next, next_count, lane);
-    }
-  }
+  cp_walk_vertices(
+      tab, P, front, nfront, &next_count[1], lane,
+      [&](uint32_t u) {  // (a hub: k_bc_edges_forward)
+        if (lane == 0) hub_stamp[u] = stamp;
+      },
+      [&](uint32_t u, const Edge *items, const Node &nd) {
+        const double su = sigma[u];
+        cp_walk_slots(items, nd, lane, [&](uint32_t val, uint32_t dst) {
+          bool won = false;
+          if (val != 0 && dst < n) won = bc_forward_edge(su, dst, level, levels[dst], levels, sigma);
+          cp_append(won, dst, next, next_count, lane);
+        });
+      });
 }
 // Large frontier, or the hubs a per-vertex launch left: one streaming pass (k_bfs_edges_bits).  `found` counts the claims.
 PMA_KERNEL void k_bc_edges_forward(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, uint32_t level,
                                    const uint32_t *__restrict__ src_bits, const uint32_t *__restrict__ placed_bits, uint32_t *levels,
                                    double *sigma, uint32_t *found) {
   PMA_SHARED uint32_t red[4];
-  const int lane = wv::lane();
-  const uint64_t nchunks = tab[P].chunk0;
-  const uint64_t wstride = cp_waves();
-  const Edge *const items0 = tab[0].items;
-  const uint64_t N0 = tab[0].N;
-  const uint32_t n0 = tab[0].n;
   uint32_t mine = 0;
   constexpr int kB = 4;
-  for (uint64_t ch0 = wv::uni(cp_wave() * kB); ch0 < nchunks; ch0 += wstride * kB) {
-    Edge e[kB];
-    uint32_t src[kB];
-    bool hit[kB];
-    cp_load_chunks<kB>(tab, P, n, items0, N0, n0, ch0, nchunks, lane, e, src, hit);
-    // phases over all kB chunks, so that the kB gathers of a phase are in flight together (k_bfs_edges_bits)
+  cp_stream<kB>(tab, P, n, [&](Edge(&e)[kB], uint32_t(&src)[kB], bool(&hit)[kB], int) {
     uint32_t lw[kB];
     double sv[kB];
 #pragma unroll
-    for (int b = 0; b < kB; b++) hit[b] = hit[b] && bc_bit(src_bits, src[b]);
+    for (int b = 0; b < kB; b++) hit[b] = hit[b] && cp_bit(src_bits, src[b]);
 #pragma unroll
-    for (int b = 0; b < kB; b++) hit[b] = hit[b] && !bc_bit(placed_bits, e[b].dest);
+    for (int b = 0; b < kB; b++) hit[b] = hit[b] && !cp_bit(placed_bits, e[b].dest);
 #pragma unroll
     for (int b = 0; b < kB; b++) {
       lw[b] = hit[b] ? levels[e[b].dest] : 0u;
@@ -144,7 +117,7 @@ PMA_KERNEL void k_bc_edges_forward(const ConsumerPart *__restrict__ tab, uint32_
 #pragma unroll
     for (int b = 0; b < kB; b++)
       if (hit[b] && bc_forward_edge(sv[b], e[b].dest, level, lw[b], levels, sigma)) mine++;
-  }
+  });
   cp_striped_add<uint32_t, kBfsStripeWords>(found, wv::reduce_add(mine), red);
 }
 
@@ -158,55 +131,34 @@ PMA_KERNEL void k_bc_delta_vertex(const ConsumerPart *__restrict__ tab, uint32_t
                                   uint32_t stamp, uint32_t *count) {
   const int lane = wv::lane();
   if (count[0] < nlist) nlist = count[0];  // (count: [0] the list's length as k_bfs_collect left it, [1] the hub flag)
-  const uint64_t wstride = cp_waves();
-  const Edge *const items0 = tab[0].items;
-  const Node *const nodes0 = tab[0].nodes;
-  for (uint64_t f = cp_wave(); f < nlist; f += wstride) {
-    const uint32_t u = wv::uni(list[f]);
-    const Edge *items;
-    Node nd;
-    if (!cp_frontier_vertex(tab, P, items0, nodes0, u, lane, &count[1], items, nd)) {  // (k_bc_edges_backward)
-      if (lane == 0) hub_stamp[u] = stamp;
-      continue;
-    }
-    const double su = sigma[u];
-    double acc = 0.0;
-    for (uint64_t base = (uint64_t)nd.beginning + 1; base < (uint64_t)nd.end; base += 64) {
-      const uint64_t s = base + (uint64_t)lane;
-      uint32_t val = 0, dst = 0;
-      if (s < (uint64_t)nd.end) {
-        val = items[s].value;
-        dst = items[s].dest;
-      }
-      if (val != 0 && dst < n && levels[dst] == level + 1u) acc += bc_term(su, sigma[dst], delta[dst]);
-    }
-    acc = bc_reduce(acc, lane);
-    if (lane == 0) delta[u] = acc;
-  }
+  cp_walk_vertices(
+      tab, P, list, nlist, &count[1], lane,
+      [&](uint32_t u) {  // (a hub: k_bc_edges_backward)
+        if (lane == 0) hub_stamp[u] = stamp;
+      },
+      [&](uint32_t u, const Edge *items, const Node &nd) {
+        const double su = sigma[u];
+        double acc = 0.0;
+        cp_walk_slots(items, nd, lane, [&](uint32_t val, uint32_t dst) {
+          if (val != 0 && dst < n && levels[dst] == level + 1u) acc += bc_term(su, sigma[dst], delta[dst]);
+        });
+        acc = bc_reduce(acc, lane);
+        if (lane == 0) delta[u] = acc;
+      });
 }
 // Large level, or the hubs a per-vertex launch left: one streaming pass; the edges with the source among src_bits and the
 // destination one level further add their term into delta[src].  A vertex's slots are contiguous, so the lanes of a wave
-// share few sources: the runs at the two ends of the wave's pending lanes — a run that fills the wave is both — are summed
-// in the wave and one lane issues the add (k_cc_hook); the other lanes add their own.
+// share few sources: their runs are summed in the wave and one lane issues the add (cp_combine_runs); the other lanes add
+// their own.
 constexpr int kBcRunLanes = 8;  // lanes of a wave on one source from which its run is reduced before the atomic
 PMA_KERNEL void k_bc_edges_backward(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, uint32_t level,
                                     const uint32_t *__restrict__ src_bits, const uint32_t *__restrict__ levels,
                                     const double *__restrict__ sigma, double *delta) {
-  const int lane = wv::lane();
-  const uint64_t nchunks = tab[P].chunk0;
-  const uint64_t wstride = cp_waves();
-  const Edge *const items0 = tab[0].items;
-  const uint64_t N0 = tab[0].N;
-  const uint32_t n0 = tab[0].n;
   constexpr int kB = 4;
-  for (uint64_t ch0 = wv::uni(cp_wave() * kB); ch0 < nchunks; ch0 += wstride * kB) {
-    Edge e[kB];
-    uint32_t src[kB];
-    bool hit[kB];
-    cp_load_chunks<kB>(tab, P, n, items0, N0, n0, ch0, nchunks, lane, e, src, hit);
+  cp_stream<kB>(tab, P, n, [&](Edge(&e)[kB], uint32_t(&src)[kB], bool(&hit)[kB], int lane) {
     double sv[kB], sw[kB], dw[kB];
 #pragma unroll
-    for (int b = 0; b < kB; b++) hit[b] = hit[b] && bc_bit(src_bits, src[b]);
+    for (int b = 0; b < kB; b++) hit[b] = hit[b] && cp_bit(src_bits, src[b]);
 #pragma unroll
     for (int b = 0; b < kB; b++) hit[b] = hit[b] && levels[e[b].dest] == level + 1u;
 #pragma unroll
@@ -218,25 +170,10 @@ PMA_KERNEL void k_bc_edges_backward(const ConsumerPart *__restrict__ tab, uint32
 #pragma unroll
     for (int b = 0; b < kB; b++) {
       double term = hit[b] ? bc_term(sv[b], sw[b], dw[b]) : 0.0;
-      bool issue = hit[b];
-      const uint64_t pend = wv::ballot(issue);
-      if (pend) {
-        const int ends[2] = {wv::ctz64(pend), 63 - wv::clz64(pend)};
-        for (int t = 0; t < 2; t++) {
-          const uint32_t key = wv::bcast(src[b], ends[t]);
-          const bool in = issue && src[b] == key;
-          const uint64_t grp = wv::ballot(in);
-          if (wv::popc64(grp) < kBcRunLanes) continue;
-          const double sum = bc_reduce(in ? term : 0.0, lane);
-          if (in) {
-            term = sum;
-            issue = lane == wv::ctz64(grp);
-          }
-        }
-      }
-      if (issue) bc_atomic_add(&delta[src[b]], term);
+      if (cp_combine_runs<kBcRunLanes>(hit[b], src[b], term, 0.0, lane, [](double x, int l) { return bc_reduce(x, l); }))
+        bc_atomic_add(&delta[src[b]], term);
     }
-  }
+  });
 }
 
 // bc[v] += delta[v] for every vertex but the source (endpoints are excluded)

@@ -56,47 +56,27 @@ constexpr uint32_t kKcTile = 1024;  // degrees per workgroup of the scan: 4 wave
 // (32 bytes, a sector of its own), and the host reads the first two or three of them.
 constexpr uint32_t kKcCntWords = 8;
 
-// Lanes of a wave that hold an upper edge of ONE source: the runs at the two ends of the wave's pending lanes (a run that
-// fills the wave is both), from kCcRunLanes lanes on.  Out: lead — this lane issues for cnt edges; rank — this lane's place
-// among them; leader — the lane that issues for this one (itself when not part of a reduced run).  Holds whatever the order
-// of sources in the wave is: a run is "all pending lanes with this key".
+// Lanes of a wave that hold an upper edge of ONE source: the runs of cp_end_runs, from kCcRunLanes lanes on.  Out: lead — this
+// lane issues for cnt edges; rank — this lane's place among them; leader — the lane that issues for this one (itself when not
+// part of a reduced run).
 PMA_DEV void kc_source_runs(bool up, uint32_t src, int lane, bool &lead, uint32_t &cnt, uint32_t &rank, int &leader) {
-  lead = up;
   cnt = 1;
   rank = 0;
   leader = lane;
-  const uint64_t pend = wv::ballot(up);
-  if (!pend) return;
-  const int ends[2] = {wv::ctz64(pend), 63 - wv::clz64(pend)};
-  for (int t = 0; t < 2; t++) {
-    const uint32_t key = wv::bcast(src, ends[t]);
-    const bool in = up && lead && cnt == 1u && src == key;
-    const uint64_t grp = wv::ballot(in);
-    if (wv::popc64(grp) < kCcRunLanes) continue;
+  lead = cp_end_runs<kCcRunLanes>(up, src, lane, [&](bool in, uint64_t grp) {
     if (in) {
       cnt = (uint32_t)wv::popc64(grp);
       rank = dev::lanemask_lt_count(grp, lane);
       leader = wv::ctz64(grp);
-      lead = lane == leader;
     }
-  }
+  });
 }
 
 // ---- stage 1: the symmetric adjacency of G ---------------------------------------------------------------------------------------------
 // (both passes: the streaming load, then per chunk the upper edges of G and their source runs)
 PMA_KERNEL void k_kc_degree(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, uint32_t *deg) {
-  const int lane = wv::lane();
-  const uint64_t nchunks = tab[P].chunk0;
-  const uint64_t wstride = cp_waves();
-  const Edge *const items0 = tab[0].items;
-  const uint64_t N0 = tab[0].N;
-  const uint32_t n0 = tab[0].n;
   constexpr int kB = 4;
-  for (uint64_t ch0 = wv::uni(cp_wave() * kB); ch0 < nchunks; ch0 += wstride * kB) {
-    Edge e[kB];
-    uint32_t a[kB];
-    bool up[kB];
-    cp_load_chunks<kB>(tab, P, n, items0, N0, n0, ch0, nchunks, lane, e, a, up);
+  cp_stream<kB>(tab, P, n, [&](Edge(&e)[kB], uint32_t(&a)[kB], bool(&up)[kB], int lane) {
 #pragma unroll
     for (int b = 0; b < kB; b++) {
       bool lead;
@@ -107,23 +87,13 @@ PMA_KERNEL void k_kc_degree(const ConsumerPart *__restrict__ tab, uint32_t P, ui
       if (lead) wv::atomic_add_u32(&deg[a[b]], cnt);
       if (up[b]) wv::atomic_add_u32(&deg[e[b].dest], 1u);
     }
-  }
+  });
 }
 // fill[v]: entries of v's list written so far (ends at deg[v]); a reduced run takes its places with one atomic
 PMA_KERNEL void k_kc_fill(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, const unsigned long long *__restrict__ off,
                           uint32_t *fill, uint32_t *adj) {
-  const int lane = wv::lane();
-  const uint64_t nchunks = tab[P].chunk0;
-  const uint64_t wstride = cp_waves();
-  const Edge *const items0 = tab[0].items;
-  const uint64_t N0 = tab[0].N;
-  const uint32_t n0 = tab[0].n;
   constexpr int kB = 4;
-  for (uint64_t ch0 = wv::uni(cp_wave() * kB); ch0 < nchunks; ch0 += wstride * kB) {
-    Edge e[kB];
-    uint32_t a[kB];
-    bool up[kB];
-    cp_load_chunks<kB>(tab, P, n, items0, N0, n0, ch0, nchunks, lane, e, a, up);
+  cp_stream<kB>(tab, P, n, [&](Edge(&e)[kB], uint32_t(&a)[kB], bool(&up)[kB], int lane) {
 #pragma unroll
     for (int b = 0; b < kB; b++) {
       bool lead;
@@ -139,18 +109,14 @@ PMA_KERNEL void k_kc_fill(const ConsumerPart *__restrict__ tab, uint32_t P, uint
         adj[off[e[b].dest] + wv::atomic_add_u32(&fill[e[b].dest], 1u)] = a[b];
       }
     }
-  }
+  });
 }
 
 // Exclusive scan of the degrees into 64-bit offsets: tile sums, one wave over the tile sums, the tiles again.  (Not a hot
 // path: n words, three launches per call.)
-PMA_DEV unsigned long long kc_shfl_u64(unsigned long long v, int src) {
-  const uint32_t lo = wv::shfl((uint32_t)v, src), hi = wv::shfl((uint32_t)(v >> 32), src);
-  return ((unsigned long long)hi << 32) | lo;
-}
 PMA_DEV unsigned long long kc_wave_scan(unsigned long long v, int lane) {  // inclusive
   for (int d = 1; d < 64; d <<= 1) {
-    const unsigned long long o = kc_shfl_u64(v, lane >= d ? lane - d : lane);
+    const unsigned long long o = cp_shfl(v, lane >= d ? lane - d : lane);
     if (lane >= d) v += o;
   }
   return v;
@@ -165,7 +131,7 @@ PMA_KERNEL void k_kc_tile_sums(const uint32_t *__restrict__ deg, uint32_t n, uin
       const uint64_t i = base + (uint64_t)j * 64 + (uint64_t)lane;
       if (i < n) sum += deg[i];
     }
-    sum = kc_shfl_u64(kc_wave_scan(sum, lane), 63);
+    sum = cp_shfl(kc_wave_scan(sum, lane), 63);
     if (lane == 0) ws[w] = sum;
     wv::block_sync();
     if (wv::thread_idx() == 0) tilesum[t] = ws[0] + ws[1] + ws[2] + ws[3];
@@ -180,7 +146,7 @@ PMA_KERNEL void k_kc_scan_tiles(unsigned long long *tilesum, uint32_t ntiles, un
     const unsigned long long v = i < ntiles ? tilesum[i] : 0ull;
     const unsigned long long s = kc_wave_scan(v, lane);
     if (i < ntiles) tilesum[i] = carry + s - v;
-    carry += kc_shfl_u64(s, 63);
+    carry += cp_shfl(s, 63);
   }
   if (lane == 0) *total = carry;
 }
@@ -195,7 +161,7 @@ PMA_KERNEL void k_kc_scan_write(const uint32_t *__restrict__ deg, uint32_t n, ui
       const uint64_t i = base + (uint64_t)j * 64 + (uint64_t)lane;
       x[j] = i < n ? deg[i] : 0u;
       s[j] = kc_wave_scan(x[j], lane);
-      sum += kc_shfl_u64(s[j], 63);
+      sum += cp_shfl(s[j], 63);
     }
     if (lane == 0) ws[w] = sum;
     wv::block_sync();
@@ -204,7 +170,7 @@ PMA_KERNEL void k_kc_scan_write(const uint32_t *__restrict__ deg, uint32_t n, ui
     for (int j = 0; j < 4; j++) {
       const uint64_t i = base + (uint64_t)j * 64 + (uint64_t)lane;
       if (i < n) off[i] = run + s[j] - x[j];
-      run += kc_shfl_u64(s[j], 63);
+      run += cp_shfl(s[j], 63);
     }
     wv::block_sync();
   }
@@ -223,10 +189,7 @@ PMA_KERNEL void k_kc_min(const uint32_t *__restrict__ deg, const uint32_t *__res
   uint32_t m = kMax;
   for (uint64_t v = (uint64_t)wv::block_idx() * wv::block_dim() + wv::thread_idx(); v < n; v += stride)
     if (core[v] == kMax && deg[v] < m) m = deg[v];
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = wv::shfl(m, lane ^ d);
-    m = o < m ? o : m;
-  }
+  m = cp_wave_min(m, lane);
   if (lane == 0) red[wv::wave_in_block()] = m;
   wv::block_sync();
   if (wv::thread_idx() == 0) {

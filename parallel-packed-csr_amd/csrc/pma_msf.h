@@ -53,44 +53,19 @@ constexpr uint32_t kMsfCntHooks = 1;   // word 1: hooks
 constexpr uint32_t kMsfCntWeight = 2;  // word 2: the sum of the emitted weights
 constexpr unsigned long long kMsfNoPair = 0xFFFFFFFFFFFFFFFFull;
 
-PMA_DEV uint32_t msf_shfl(uint32_t v, int src) { return wv::shfl(v, src); }
-PMA_DEV unsigned long long msf_shfl(unsigned long long v, int src) {
-  return ((unsigned long long)wv::shfl((uint32_t)(v >> 32), src) << 32) | wv::shfl((uint32_t)v, src);
-}
 PMA_DEV void msf_atomic_min(uint32_t *p, uint32_t v) { wv::atomic_min_u32(p, v); }
 PMA_DEV void msf_atomic_min(unsigned long long *p, unsigned long long v) { wv::atomic_min_u64(p, v); }
 PMA_DEV unsigned long long msf_reduce_add(unsigned long long v, int lane) {
-  for (int d = 1; d < 64; d <<= 1) v += msf_shfl(v, lane ^ d);
+  for (int d = 1; d < 64; d <<= 1) v += cp_shfl(v, lane ^ d);
   return v;
 }
 
-// The lanes with `want` lower best[c] to at most v (called by the whole wave).  Lanes on one target word are served one after
-// the other, and a hub's run — or, from the second round on, the giant component — fills whole waves with one target: as in
-// k_cc_hook, the groups of the first and the last pending lane (a group that fills the wave is both) are reduced to their
-// minimum when they have kCcRunLanes lanes or more, and one lane issues it.
+// The lanes with `want` lower best[c] to at most v (called by the whole wave).  A hub's run — or, from the second round on, the
+// giant component — fills whole waves with one target: runs of kCcRunLanes lanes or more are reduced to their minimum and one
+// lane issues it (cp_combine_runs).
 template <class T>
 PMA_DEV void msf_lower(bool want, uint32_t c, T v, T *best, int lane) {
-  bool issue = want;
-  const uint64_t pend = wv::ballot(want);
-  if (pend) {
-    const int ends[2] = {wv::ctz64(pend), 63 - wv::clz64(pend)};
-    for (int t = 0; t < 2; t++) {
-      const uint32_t key = wv::bcast(c, ends[t]);
-      const bool in = want && issue && c == key;
-      const uint64_t grp = wv::ballot(in);
-      if (wv::popc64(grp) < kCcRunLanes) continue;
-      T m = in ? v : (T) ~(T)0;
-      for (int d = 1; d < 64; d <<= 1) {
-        const T o = msf_shfl(m, lane ^ d);
-        m = o < m ? o : m;
-      }
-      if (in) {
-        v = m;
-        issue = lane == wv::ctz64(grp);
-      }
-    }
-  }
-  if (issue) msf_atomic_min(&best[c], v);
+  if (cp_combine_runs<kCcRunLanes>(want, c, v, (T) ~(T)0, lane, [](T m, int l) { return cp_wave_min(m, l); })) msf_atomic_min(&best[c], v);
 }
 
 // ---- steps 1 and 2: the two streaming passes -------------------------------------------------------------------------------------
@@ -100,20 +75,9 @@ PMA_DEV void msf_lower(bool want, uint32_t c, T v, T *best, int lane) {
 template <bool kPair>
 PMA_DEV void msf_pass(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, const uint32_t *__restrict__ comp, uint32_t *best_w,
                       unsigned long long *best_pair, unsigned long long *cnt, unsigned long long *red) {
-  const int lane = wv::lane();
-  const uint64_t nchunks = tab[P].chunk0;
-  const uint64_t wstride = cp_waves();
-  const Edge *const items0 = tab[0].items;
-  const uint64_t N0 = tab[0].N;
-  const uint32_t n0 = tab[0].n;
   uint32_t mine = 0;
   constexpr int kB = 4;
-  for (uint64_t ch0 = wv::uni(cp_wave() * kB); ch0 < nchunks; ch0 += wstride * kB) {
-    Edge e[kB];
-    uint32_t src[kB];
-    bool cut[kB];
-    cp_load_chunks<kB>(tab, P, n, items0, N0, n0, ch0, nchunks, lane, e, src, cut);
-    // phases over all kB chunks, so that the kB gathers of a phase are in flight together (k_bfs_edges_bits)
+  cp_stream<kB>(tab, P, n, [&](Edge(&e)[kB], uint32_t(&src)[kB], bool(&cut)[kB], int lane) {
     uint32_t cu[kB], cd[kB], bu[kB], bd[kB];
 #pragma unroll
     for (int b = 0; b < kB; b++) cut[b] = cut[b] && src[b] != e[b].dest;
@@ -154,7 +118,7 @@ PMA_DEV void msf_pass(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t
         msf_lower<unsigned long long>(hd[b] && pair < pd[b], cd[b], pair, best_pair, lane);
       }
     }
-  }
+  });
   if (!kPair) cp_striped_add<unsigned long long, kMsfStripeWords>(cnt + kMsfCntWork, (unsigned long long)wv::reduce_add(mine), red);
 }
 PMA_KERNEL void k_msf_weight(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, const uint32_t *__restrict__ comp, uint32_t *best_w,
@@ -168,21 +132,14 @@ PMA_KERNEL void k_msf_pair(const ConsumerPart *__restrict__ tab, uint32_t P, uin
 }
 
 // ---- step 3: hook -----------------------------------------------------------------------------------------------------------------
-// cp_append with a key and a weight per entry: one ballot, one atomic per wave, the lanes write behind it — never beyond the
-// list's `cap` entries (a forest has fewer than n edges; the host compares the length with its hook counts)
+// cp_append with a key and a weight per entry — never beyond the list's `cap` entries (a forest has fewer than n edges; the host
+// compares the length with its hook counts)
 PMA_DEV void msf_append(bool in, unsigned long long key, uint32_t w, unsigned long long *keys, uint32_t *wts, uint32_t *count, uint32_t cap,
                         int lane) {
-  const uint64_t m = wv::ballot(in);
-  if (m == 0) return;
-  uint32_t b = 0;
-  if (lane == 0) b = wv::atomic_add_u32(count, (uint32_t)wv::popc64(m));
-  b = wv::shfl(b, 0);
-  if (in) {
-    const uint32_t at = b + dev::lanemask_lt_count(m, lane);
-    if (at < cap) {
-      keys[at] = key;
-      wts[at] = w;
-    }
+  const uint32_t at = cp_append_at(in, count, lane);
+  if (in && at < cap) {
+    keys[at] = key;
+    wts[at] = w;
   }
 }
 // One thread per vertex, one wave per 64 consecutive vertices; a root with a chosen key hooks (header: step 3).  comp[], best_w[]

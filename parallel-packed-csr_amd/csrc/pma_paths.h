@@ -30,27 +30,16 @@ PMA_DEV bool sssp_relax_edge(unsigned long long nd, uint32_t dst, uint32_t round
 PMA_KERNEL void k_sssp_relax(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, const uint32_t *front, uint32_t nfront,
                              uint32_t round, unsigned long long *dist, uint32_t *stamp, uint32_t *next, uint32_t *next_count) {
   const int lane = wv::lane();
-  const uint64_t wstride = cp_waves();
-  const Edge *const items0 = tab[0].items;
-  const Node *const nodes0 = tab[0].nodes;
-  for (uint64_t f = cp_wave(); f < nfront; f += wstride) {
-    const uint32_t u = wv::uni(front[f]);
-    const Edge *items;
-    Node nd;
-    if (!cp_frontier_vertex(tab, P, items0, nodes0, u, lane, &next_count[1], items, nd)) continue;  // (k_sssp_edges)
-    const unsigned long long du = dist[u];
-    for (uint64_t base = (uint64_t)nd.beginning + 1; base < (uint64_t)nd.end; base += 64) {
-      const uint64_t s = base + (uint64_t)lane;
-      uint32_t val = 0, dst = 0;
-      if (s < (uint64_t)nd.end) {
-        val = items[s].value;
-        dst = items[s].dest;
-      }
-      bool won = false;
-      if (val != 0 && dst < n && du + val < dist[dst]) won = sssp_relax_edge(du + val, dst, round, dist, stamp);
-      cp_append(won, dst, next, next_count, lane);
-    }
-  }
+  cp_walk_vertices(
+      tab, P, front, nfront, &next_count[1], lane, [](uint32_t) {},  // (a hub: k_sssp_edges)
+      [&](uint32_t u, const Edge *items, const Node &nd) {
+        const unsigned long long du = dist[u];
+        cp_walk_slots(items, nd, lane, [&](uint32_t val, uint32_t dst) {
+          bool won = false;
+          if (val != 0 && dst < n && du + val < dist[dst]) won = sssp_relax_edge(du + val, dst, round, dist, stamp);
+          cp_append(won, dst, next, next_count, lane);
+        });
+      });
 }
 // Large active set (or hubs left over): one streaming pass over the concatenated chunk space, four 64-slot chunks in flight
 // per wave; the source is tested against the round's active bitmap (n / 8 bytes: L2-resident), dist[src] is gathered only
@@ -59,23 +48,12 @@ PMA_KERNEL void k_sssp_relax(const ConsumerPart *__restrict__ tab, uint32_t P, u
 PMA_KERNEL void k_sssp_edges(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, uint32_t round,
                              const uint32_t *__restrict__ active_bits, unsigned long long *dist, uint32_t *stamp, uint32_t *found) {
   PMA_SHARED uint32_t red[4];
-  const int lane = wv::lane();
-  const uint64_t nchunks = tab[P].chunk0;
-  const uint64_t wstride = cp_waves();
-  const Edge *const items0 = tab[0].items;
-  const uint64_t N0 = tab[0].N;
-  const uint32_t n0 = tab[0].n;
   uint32_t mine = 0;
   constexpr int kB = 4;
-  for (uint64_t ch0 = wv::uni(cp_wave() * kB); ch0 < nchunks; ch0 += wstride * kB) {
-    Edge e[kB];
-    uint32_t src[kB];
-    bool hit[kB];
-    cp_load_chunks<kB>(tab, P, n, items0, N0, n0, ch0, nchunks, lane, e, src, hit);
-    // phases over all kB chunks, so that the kB gathers of a phase are in flight together (k_bfs_edges_bits)
+  cp_stream<kB>(tab, P, n, [&](Edge(&e)[kB], uint32_t(&src)[kB], bool(&hit)[kB], int) {
     unsigned long long nd[kB], dd[kB];
 #pragma unroll
-    for (int b = 0; b < kB; b++) hit[b] = hit[b] && ((active_bits[src[b] >> 5] >> (src[b] & 31u)) & 1u);
+    for (int b = 0; b < kB; b++) hit[b] = hit[b] && cp_bit(active_bits, src[b]);
 #pragma unroll
     for (int b = 0; b < kB; b++) {
       nd[b] = hit[b] ? dist[src[b]] + e[b].value : kNoPath;
@@ -84,7 +62,7 @@ PMA_KERNEL void k_sssp_edges(const ConsumerPart *__restrict__ tab, uint32_t P, u
 #pragma unroll
     for (int b = 0; b < kB; b++)
       if (nd[b] < dd[b] && sssp_relax_edge(nd[b], e[b].dest, round, dist, stamp)) mine++;
-  }
+  });
   cp_striped_add<uint32_t, kBfsStripeWords>(found, wv::reduce_add(mine), red);
 }
 
@@ -99,6 +77,9 @@ PMA_KERNEL void k_cc_init(uint32_t *labels, uint32_t n) {
 // One streaming pass: an edge whose ends carry different labels lowers the end with the larger label, and the entry of that
 // larger label itself (the vertex it pointed to — this is what merges whole trees instead of single vertices, so a long chain
 // finishes in few rounds).  Loads may be stale (too large): the atomic min decides.  `found` counts the edges that differed.
+// This kernel keeps the pass loop of cp_stream and the run combiner of cp_combine_runs WRITTEN OUT: over the shared pieces it
+// compiles to other code (54 SGPRs for 56), with which components over 8 partitions of a scale-18 graph took 3-6 % longer
+// (0.90 -> 0.93 ms; one array was 1.5 % faster) — DESIGN 4c.  What is written here is what those two pieces say.
 constexpr int kCcRunLanes = 8;  // lanes of a wave on one source from which its run is reduced before the atomic
 PMA_KERNEL void k_cc_hook(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, uint32_t *labels, uint32_t *found) {
   PMA_SHARED uint32_t red[4];
@@ -129,10 +110,9 @@ PMA_KERNEL void k_cc_hook(const ConsumerPart *__restrict__ tab, uint32_t P, uint
       uint32_t lo = lu[b] < lv[b] ? lu[b] : lv[b];
       const uint32_t hi = lu[b] < lv[b] ? lv[b] : lu[b];
       const uint32_t x = lu[b] < lv[b] ? e[b].dest : src[b];
-      // Lanes that lower THEIR SOURCE share the target with their neighbours (a vertex's slots are contiguous): 64 atomics on
-      // one word are served one after the other, and a hub's run fills whole waves.  The runs at the two ends of the wave's
-      // pending lanes — a run that fills the wave is both — are reduced to their smallest label and one lane issues it
-      // (the others' edges still count as differing; whatever they would have stored is not below that minimum).
+      // Lanes that lower THEIR SOURCE share the target with their neighbours: their runs are reduced to the smallest label
+      // and one lane issues it (the rule of cp_combine_runs; the others' edges still count as differing, and whatever they
+      // would have stored is not below that minimum).  Lanes that lower their destination issue their own.
       bool issue = diff;
       const bool own = diff && x == src[b];
       const uint64_t pend = wv::ballot(own);

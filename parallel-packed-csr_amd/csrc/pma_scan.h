@@ -280,25 +280,15 @@ PMA_KERNEL void k_bb_edges(View v, const unsigned long long *keys, const uint32_
 PMA_KERNEL void k_bfs_level(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, const uint32_t *front, uint32_t nfront,
                             uint32_t level, uint32_t *levels, uint32_t *next, uint32_t *next_count) {
   const int lane = wv::lane();
-  const uint64_t wstride = cp_waves();
-  const Edge *const items0 = tab[0].items;
-  const Node *const nodes0 = tab[0].nodes;
-  for (uint64_t f = cp_wave(); f < nfront; f += wstride) {
-    const Edge *items;
-    Node nd;
-    if (!cp_frontier_vertex(tab, P, items0, nodes0, wv::uni(front[f]), lane, &next_count[1], items, nd)) continue;  // (k_bfs_edges_bits)
-    for (uint64_t base = (uint64_t)nd.beginning + 1; base < (uint64_t)nd.end; base += 64) {
-      const uint64_t s = base + (uint64_t)lane;
-      uint32_t val = 0, dst = 0;
-      if (s < (uint64_t)nd.end) {
-        val = items[s].value;
-        dst = items[s].dest;
-      }
-      bool won = false;
-      if (val != 0 && dst < n && levels[dst] == kMax) won = wv::atomic_cas_u32(&levels[dst], kMax, level + 1u) == kMax;
-      cp_append(won, dst, next, next_count, lane);
-    }
-  }
+  cp_walk_vertices(
+      tab, P, front, nfront, &next_count[1], lane, [](uint32_t) {},  // (a hub: k_bfs_edges_bits)
+      [&](uint32_t, const Edge *items, const Node &nd) {
+        cp_walk_slots(items, nd, lane, [&](uint32_t val, uint32_t dst) {
+          bool won = false;
+          if (val != 0 && dst < n && levels[dst] == kMax) won = wv::atomic_cas_u32(&levels[dst], kMax, level + 1u) == kMax;
+          cp_append(won, dst, next, next_count, lane);
+        });
+      });
 }
 // The streaming level's two per-edge tests — "is the source on the frontier", "is the destination still unvisited" — as two
 // bitmaps of n/8 bytes (128 KB at n = 1 M: L2-resident on every XCD), built with one coalesced sweep over levels[] per level.
@@ -309,11 +299,8 @@ PMA_KERNEL void k_bfs_bits(const uint32_t *levels, uint32_t n, uint32_t level, u
   for (uint64_t base = (uint64_t)wv::block_idx() * wv::block_dim() + (wv::thread_idx() & ~63u); base < n; base += stride) {
     const uint64_t u = base + (uint64_t)lane;
     const uint32_t lv = u < n ? levels[u] : kMax;
-    const uint64_t mf = wv::ballot(u < n && lv == level), mv = wv::ballot(u < n && lv != kMax);
-    if (lane < 2) {
-      front_bits[(base >> 5) + lane] = (uint32_t)(mf >> (32 * lane));
-      visited_bits[(base >> 5) + lane] = (uint32_t)(mv >> (32 * lane));
-    }
+    cp_store_bits(front_bits, base, wv::ballot(u < n && lv == level), lane);
+    cp_store_bits(visited_bits, base, wv::ballot(u < n && lv != kMax), lane);
   }
 }
 // BFS level for a LARGE frontier: one streaming pass over the gapped arrays instead of one wave per frontier vertex (whose
@@ -328,25 +315,13 @@ PMA_KERNEL void k_bfs_edges_bits(const ConsumerPart *__restrict__ tab, uint32_t 
                                  const uint32_t *__restrict__ front_bits, const uint32_t *__restrict__ visited_bits, uint32_t *levels,
                                  uint32_t *found) {
   PMA_SHARED uint32_t red[4];
-  const int lane = wv::lane();
-  const uint64_t nchunks = tab[P].chunk0;
-  const uint64_t wstride = cp_waves();
-  const Edge *const items0 = tab[0].items;
-  const uint64_t N0 = tab[0].N;
-  const uint32_t n0 = tab[0].n;
   uint32_t mine = 0;
   constexpr int kB = 4;
-  for (uint64_t ch0 = wv::uni(cp_wave() * kB); ch0 < nchunks; ch0 += wstride * kB) {
-    Edge e[kB];
-    uint32_t src[kB];
-    bool hit[kB];
-    cp_load_chunks<kB>(tab, P, n, items0, N0, n0, ch0, nchunks, lane, e, src, hit);
-    // Four phases, each over all kB chunks, so that the kB gathers of a phase are in flight TOGETHER (written one chunk after
-    // the other, the levels[] load of chunk b+1 waits for the store of chunk b: they may alias).
-    uint32_t bit[kB], old[kB];
+  cp_stream<kB>(tab, P, n, [&](Edge(&e)[kB], uint32_t(&src)[kB], bool(&hit)[kB], int) {
+    uint32_t bit[kB], old[kB];  // (four phases: cp_stream)
 #pragma unroll
     for (int b = 0; b < kB; b++) {
-      hit[b] = hit[b] && ((front_bits[src[b] >> 5] >> (src[b] & 31u)) & 1u);
+      hit[b] = hit[b] && cp_bit(front_bits, src[b]);
       bit[b] = 1u << (e[b].dest & 31u);
     }
 #pragma unroll
@@ -365,7 +340,7 @@ PMA_KERNEL void k_bfs_edges_bits(const ConsumerPart *__restrict__ tab, uint32_t 
         mine++;
       }
     }
-  }
+  });
   cp_striped_add<uint32_t, kBfsStripeWords>(found, wv::reduce_add(mine), red);
 }
 // frontier list of one level (used when a small frontier follows an edge-centric level)

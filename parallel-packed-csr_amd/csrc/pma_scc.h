@@ -38,33 +38,16 @@ namespace ppcsr {
 constexpr uint32_t kSccStripeWords = 16;  // 64-bit striped counters, one 128-byte line each
 constexpr uint8_t kSccOpen = 0, kSccMarked = 1, kSccDead = 2;
 
-PMA_DEV bool scc_bit(const uint32_t *__restrict__ bits, uint32_t v) { return (bits[v >> 5] >> (v & 31u)) & 1u; }
-// the 64 vertices from `base` on: lanes 0 and 1 store the two words of their ballot
-PMA_DEV void scc_store_bits(uint32_t *bits, uint64_t base, uint64_t m, int lane) {
-  if (lane < 2) bits[(base >> 5) + lane] = (uint32_t)(m >> (32 * lane));
-}
-
 // ---- 1. trim -------------------------------------------------------------------------------------------------------------------
 // The sweep's streaming pass.  A look at the flag first (possibly stale: then the store is repeated) keeps a hub's run from
 // storing the same byte 64 times per wave.
 PMA_KERNEL void k_scc_trim_edges(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, const uint32_t *__restrict__ live_bits,
                                  uint8_t *has_out, uint8_t *has_in) {
-  const int lane = wv::lane();
-  const uint64_t nchunks = tab[P].chunk0;
-  const uint64_t wstride = cp_waves();
-  const Edge *const items0 = tab[0].items;
-  const uint64_t N0 = tab[0].N;
-  const uint32_t n0 = tab[0].n;
   constexpr int kB = 4;
-  for (uint64_t ch0 = wv::uni(cp_wave() * kB); ch0 < nchunks; ch0 += wstride * kB) {
-    Edge e[kB];
-    uint32_t src[kB];
-    bool live[kB];
-    cp_load_chunks<kB>(tab, P, n, items0, N0, n0, ch0, nchunks, lane, e, src, live);
-    // phases over all kB chunks, so that the kB gathers of a phase are in flight together (k_bfs_edges_bits)
+  cp_stream<kB>(tab, P, n, [&](Edge(&e)[kB], uint32_t(&src)[kB], bool(&live)[kB], int lane) {
     uint8_t fo[kB], fi[kB];
 #pragma unroll
-    for (int b = 0; b < kB; b++) live[b] = live[b] && src[b] != e[b].dest && scc_bit(live_bits, src[b]) && scc_bit(live_bits, e[b].dest);
+    for (int b = 0; b < kB; b++) live[b] = live[b] && src[b] != e[b].dest && cp_bit(live_bits, src[b]) && cp_bit(live_bits, e[b].dest);
 #pragma unroll
     for (int b = 0; b < kB; b++) {
       fo[b] = live[b] ? has_out[src[b]] : (uint8_t)1;
@@ -75,7 +58,7 @@ PMA_KERNEL void k_scc_trim_edges(const ConsumerPart *__restrict__ tab, uint32_t 
       if (!fo[b]) has_out[src[b]] = 1;
       if (!fi[b]) has_in[e[b].dest] = 1;
     }
-  }
+  });
 }
 // The sweep's per-vertex launch, one wave per 64 consecutive vertices: a live vertex that lacks a flag is an SCC of its own;
 // the live bitmap is rebuilt and the flags are cleared for the next sweep.  `found` counts the retired vertices.
@@ -97,7 +80,7 @@ PMA_KERNEL void k_scc_trim_retire(uint32_t *scc, uint32_t n, uint8_t *has_out, u
         mine++;
       }
     }
-    scc_store_bits(live_bits, base, wv::ballot(keep), lane);
+    cp_store_bits(live_bits, base, wv::ballot(keep), lane);
   }
   cp_striped_add<unsigned long long, kSccStripeWords>(found, (unsigned long long)wv::reduce_add(mine), red);
 }
@@ -113,7 +96,7 @@ PMA_KERNEL void k_scc_pivot(const ConsumerPart *__restrict__ tab, uint32_t P, ui
   const uint64_t stride = (uint64_t)wv::grid_dim() * wv::block_dim();
   uint32_t hi = 0, lo = 0;  // the key's two halves
   for (uint64_t v = (uint64_t)wv::block_idx() * wv::block_dim() + wv::thread_idx(); v < n; v += stride) {
-    if (!scc_bit(live_bits, (uint32_t)v)) continue;
+    if (!cp_bit(live_bits, (uint32_t)v)) continue;
     const uint32_t k = P == 1 ? 0u : cp_owner(tab, P, (uint32_t)v);
     const Node nd = tab[k].nodes[(uint32_t)v - tab[k].first];
     const uint32_t range = nd.end - nd.beginning, inv = kMax - (uint32_t)v;
@@ -122,14 +105,9 @@ PMA_KERNEL void k_scc_pivot(const ConsumerPart *__restrict__ tab, uint32_t P, ui
       lo = inv;
     }
   }
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t ohi = wv::shfl(hi, lane ^ d), olo = wv::shfl(lo, lane ^ d);
-    if (ohi > hi || (ohi == hi && olo > lo)) {
-      hi = ohi;
-      lo = olo;
-    }
-  }
-  if (lane == 0) red[wv::wave_in_block()] = ((unsigned long long)hi << 32) | lo;
+  // (the wave's largest key: the minimum of the complements)
+  const unsigned long long wkey = ~cp_wave_min(~(((unsigned long long)hi << 32) | lo), lane);
+  if (lane == 0) red[wv::wave_in_block()] = wkey;
   wv::block_sync();
   if (wv::thread_idx() == 0) {
     unsigned long long key = red[0];
@@ -154,20 +132,9 @@ PMA_KERNEL void k_scc_marks(const uint32_t *scc, uint32_t n, const uint32_t *col
 template <bool kFw, bool kBw, bool kCol>
 PMA_DEV void scc_reach_pass(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, const uint32_t *colour, uint8_t *fw, uint8_t *bw,
                             unsigned long long *found, unsigned long long *red) {
-  const int lane = wv::lane();
-  const uint64_t nchunks = tab[P].chunk0;
-  const uint64_t wstride = cp_waves();
-  const Edge *const items0 = tab[0].items;
-  const uint64_t N0 = tab[0].N;
-  const uint32_t n0 = tab[0].n;
   uint32_t mine_f = 0, mine_b = 0;
   constexpr int kB = 4;
-  for (uint64_t ch0 = wv::uni(cp_wave() * kB); ch0 < nchunks; ch0 += wstride * kB) {
-    Edge e[kB];
-    uint32_t src[kB];
-    bool live[kB];
-    cp_load_chunks<kB>(tab, P, n, items0, N0, n0, ch0, nchunks, lane, e, src, live);
-    // phases over all kB chunks, so that the kB gathers of a phase are in flight together (k_bfs_edges_bits)
+  cp_stream<kB>(tab, P, n, [&](Edge(&e)[kB], uint32_t(&src)[kB], bool(&live)[kB], int lane) {
     uint8_t fu[kB], fd[kB], bu[kB], bd[kB];
     bool wf[kB], wb[kB];
 #pragma unroll
@@ -215,7 +182,7 @@ PMA_DEV void scc_reach_pass(const ConsumerPart *__restrict__ tab, uint32_t P, ui
         }
       }
     }
-  }
+  });
   const unsigned long long mine = (unsigned long long)wv::reduce_add(mine_f) | ((unsigned long long)wv::reduce_add(mine_b) << 32);
   cp_striped_add<unsigned long long, kSccStripeWords>(found, mine, red);
 }
@@ -244,10 +211,7 @@ PMA_KERNEL void k_scc_min(const uint8_t *fw, const uint8_t *bw, uint32_t n, uint
   uint32_t m = kMax;
   for (uint64_t v = (uint64_t)wv::block_idx() * wv::block_dim() + wv::thread_idx(); v < n; v += stride)
     if (fw[v] == kSccMarked && bw[v] == kSccMarked && (uint32_t)v < m) m = (uint32_t)v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = wv::shfl(m, lane ^ d);
-    m = o < m ? o : m;
-  }
+  m = cp_wave_min(m, lane);
   if (lane == 0) red[wv::wave_in_block()] = m;
   wv::block_sync();
   if (wv::thread_idx() == 0) {
@@ -274,7 +238,7 @@ PMA_KERNEL void k_scc_assign(const uint8_t *fw, const uint8_t *bw, uint32_t n, c
         keep = true;
       }
     }
-    scc_store_bits(live_bits, base, wv::ballot(keep), lane);
+    cp_store_bits(live_bits, base, wv::ballot(keep), lane);
   }
   cp_striped_add<unsigned long long, kSccStripeWords>(found, (unsigned long long)wv::reduce_add(mine), red);
 }
@@ -292,22 +256,12 @@ PMA_KERNEL void k_scc_colour_init(const uint32_t *scc, uint32_t n, uint32_t *col
 PMA_KERNEL void k_scc_colour_prop(const ConsumerPart *__restrict__ tab, uint32_t P, uint32_t n, const uint32_t *__restrict__ live_bits,
                                   uint32_t *colour, unsigned long long *found) {
   PMA_SHARED unsigned long long red[4];
-  const int lane = wv::lane();
-  const uint64_t nchunks = tab[P].chunk0;
-  const uint64_t wstride = cp_waves();
-  const Edge *const items0 = tab[0].items;
-  const uint64_t N0 = tab[0].N;
-  const uint32_t n0 = tab[0].n;
   uint32_t mine = 0;
   constexpr int kB = 4;
-  for (uint64_t ch0 = wv::uni(cp_wave() * kB); ch0 < nchunks; ch0 += wstride * kB) {
-    Edge e[kB];
-    uint32_t src[kB];
-    bool live[kB];
-    cp_load_chunks<kB>(tab, P, n, items0, N0, n0, ch0, nchunks, lane, e, src, live);
+  cp_stream<kB>(tab, P, n, [&](Edge(&e)[kB], uint32_t(&src)[kB], bool(&live)[kB], int lane) {
     uint32_t cu[kB], cd[kB];
 #pragma unroll
-    for (int b = 0; b < kB; b++) live[b] = live[b] && src[b] != e[b].dest && scc_bit(live_bits, e[b].dest);
+    for (int b = 0; b < kB; b++) live[b] = live[b] && src[b] != e[b].dest && cp_bit(live_bits, e[b].dest);
 #pragma unroll
     for (int b = 0; b < kB; b++) {
       cu[b] = live[b] ? colour[src[b]] : kMax;
@@ -316,7 +270,7 @@ PMA_KERNEL void k_scc_colour_prop(const ConsumerPart *__restrict__ tab, uint32_t
 #pragma unroll
     for (int b = 0; b < kB; b++)
       if (cu[b] < cd[b] && wv::atomic_min_u32(&colour[e[b].dest], cu[b]) > cu[b]) mine++;
-  }
+  });
   cp_striped_add<unsigned long long, kSccStripeWords>(found, (unsigned long long)wv::reduce_add(mine), red);
 }
 
