@@ -259,6 +259,45 @@ int ppcsr_debug_msf_counters(ppcsr_t h, uint64_t out[8]);
 int ppcsr_triangles(ppcsr_t h, uint64_t *tri, uint64_t *total, double *device_ms);
 int ppcsr_common_neighbours(ppcsr_t h, const uint32_t *a, const uint32_t *b, uint64_t k, uint32_t *counts, double *device_ms);
 int ppcsr_common_neighbours_device(ppcsr_t h, const uint32_t *d_a, const uint32_t *d_b, uint64_t k, uint32_t *d_counts, double *device_ms);
+/* Neighbour sampling, random walks and live degrees, on the graph as it stands (no export).
+ * Neighbour list — L(v) of a vertex v < n: the live slots of v's range (beginning, end) in slot order, with the consumers' edge
+ *   set: the slot is non-null and non-sentinel, it is not slot N - 1, and its destination is < n.  Self-loops count.
+ * Measure — every entry of L(v) has a measure: 1 (uniform), or the edge value when flags bit 0 (PPCSR_SAMPLE_WEIGHTED) is set.
+ *   W(v) is the sum of the measures, in 64 bits.
+ * Draw — a function of (seed, i, j) alone, i the query / walker index, j the draw / step index, all arithmetic mod 2^64:
+ *     sm(z): z += 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *            return z ^ (z >> 31)
+ *     x = sm(sm(sm(seed) + i) + j);   r = (x * W(v)) >> 64  (the high half of the 128-bit product)
+ *     pick = the first entry of L(v) whose inclusive cumulative measure exceeds r
+ *   so the result depends on nothing else: not on the launch geometry, not on where the gaps lie, not on the partitioning (in the
+ *   regular regime a PCSR and a PPPCSR that hold the same edges answer word for word alike).  Draws are with replacement.
+ * PPCSR_NO_VERTEX is returned for a vertex >= n, for an empty L(v), and in a walk for every position after either; the value
+ *   beside it is 0 (never a stored value).
+ * sample_neighbours — dests[i * fanout + j] = the destination picked by draw (seed, i, j) from L(vertices[i]), values[...] that
+ *   edge's value (values may be NULL).  Repeated vertices are separate queries (i differs).
+ * random_walks — out[i * (length + 1)] = starts[i] (PPCSR_NO_VERTEX when >= n), out[i * (length + 1) + t + 1] = the pick of
+ *   draw (seed, i, t) from L(out[i * (length + 1) + t]).
+ * degrees — deg[v] = |L(v)| (uint32) and wsum[v] = the sum of the values of L(v) (uint64), n entries each, either may be NULL:
+ *   one streaming pass that takes every edge's source from the item itself, so it also answers in the sequential regime.
+ * The host forms take host pointers; the _device forms take every array in this GPU's HBM.  Same contract as bfs: synchronous,
+ * nothing of the graph is written (state, stats, snapshot unchanged), device_ms may be NULL.  Every refusal is made before the
+ * first launch.  EINVAL: null handle, vertices / starts or dests / out NULL with k > 0, fanout == 0, length == 0, unknown flags
+ * bits, deg and wsum both NULL; k == 0 succeeds and writes nothing.  EUNSUPPORTED (sample_neighbours, random_walks): the
+ * structure is in the sequential regime (stats.narrow == 0), where vertex ranges cannot be trusted. */
+#define PPCSR_NO_VERTEX 0xFFFFFFFFu
+#define PPCSR_SAMPLE_WEIGHTED 1u
+int ppcsr_sample_neighbours(ppcsr_t h, const uint32_t *vertices, uint64_t k, uint32_t fanout, uint64_t seed, uint32_t flags, uint32_t *dests,
+                            uint32_t *values, double *device_ms);
+int ppcsr_sample_neighbours_device(ppcsr_t h, const uint32_t *d_vertices, uint64_t k, uint32_t fanout, uint64_t seed, uint32_t flags,
+                                   uint32_t *d_dests, uint32_t *d_values, double *device_ms);
+int ppcsr_random_walks(ppcsr_t h, const uint32_t *starts, uint64_t k, uint32_t length, uint64_t seed, uint32_t flags, uint32_t *out,
+                       double *device_ms);
+int ppcsr_random_walks_device(ppcsr_t h, const uint32_t *d_starts, uint64_t k, uint32_t length, uint64_t seed, uint32_t flags, uint32_t *d_out,
+                              double *device_ms);
+int ppcsr_degrees(ppcsr_t h, uint32_t *deg, uint64_t *wsum, double *device_ms);
+/* Debugging: out[i] = the high half of a[i] * b[i], computed on the device by the wave layer's wrapper the draws use (host
+ * pointers, k entries each).  EINVAL: null handle, a null pointer with k > 0. */
+int ppcsr_debug_mulhi(ppcsr_t h, const uint64_t *a, const uint64_t *b, uint64_t k, uint64_t *out);
 /* raw state for parity checks: items[N], nodes[n] exactly as the reference holds them (PCSR.h:67,128) */
 int ppcsr_export_state(ppcsr_t h, ppcsr_edge *items, ppcsr_node *nodes);
 int ppcsr_stats(ppcsr_t h, ppcsr_stats_t *out);
@@ -448,6 +487,16 @@ int pppcsr_betweenness(pppcsr_t h, const uint32_t *sources, uint64_t k, double *
  * EUNSUPPORTED: the partitions sit on more than one device, or any partition is in the sequential regime. */
 int pppcsr_triangles(pppcsr_t h, uint64_t *tri, uint64_t *total, double *device_ms);
 int pppcsr_common_neighbours(pppcsr_t h, const uint32_t *a, const uint32_t *b, uint64_t k, uint32_t *counts, double *device_ms);
+/* ppcsr_sample_neighbours / ppcsr_random_walks / ppcsr_degrees over the GLOBAL vertex ids (host pointers; deg, wsum:
+ * pppcsr_get_n entries), one device call over every partition's array: a walk crosses partitions freely and the results do not
+ * depend on the partitioning.  Same contract as pppcsr_bfs.  EINVAL: as the single calls, or a partition not resident in this
+ * process.  EUNSUPPORTED: the partitions sit on more than one device, or (sample_neighbours, random_walks) any partition is in
+ * the sequential regime. */
+int pppcsr_sample_neighbours(pppcsr_t h, const uint32_t *vertices, uint64_t k, uint32_t fanout, uint64_t seed, uint32_t flags, uint32_t *dests,
+                             uint32_t *values, double *device_ms);
+int pppcsr_random_walks(pppcsr_t h, const uint32_t *starts, uint64_t k, uint32_t length, uint64_t seed, uint32_t flags, uint32_t *out,
+                        double *device_ms);
+int pppcsr_degrees(pppcsr_t h, uint32_t *deg, uint64_t *wsum, double *device_ms);
 /* bucket a host stream by owner (stable: per-partition order == stream order, src made partition-local as in
  * PPPCSR.cpp:46-52) and apply each bucket on its partition's GPU */
 int pppcsr_apply_batch(pppcsr_t h, const ppcsr_op *ops, uint64_t n);

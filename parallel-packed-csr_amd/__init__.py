@@ -77,10 +77,13 @@ EXPORTED = [
     "ppcsr_scc", "pppcsr_scc", "ppcsr_debug_scc_counters",
     "ppcsr_msf", "pppcsr_msf", "ppcsr_debug_msf_counters",
     "ppcsr_triangles", "pppcsr_triangles", "ppcsr_common_neighbours", "ppcsr_common_neighbours_device", "pppcsr_common_neighbours",
+    "ppcsr_sample_neighbours", "ppcsr_sample_neighbours_device", "pppcsr_sample_neighbours",
+    "ppcsr_random_walks", "ppcsr_random_walks_device", "pppcsr_random_walks", "ppcsr_degrees", "pppcsr_degrees", "ppcsr_debug_mulhi",
 ]
 
 NO_PATH = 0xFFFFFFFFFFFFFFFF  # PPCSR_NO_PATH: what sssp reports for a vertex no path reaches
 NO_EDGE = 0xFFFFFFFF  # PPCSR_NO_EDGE: what lookup_edges reports for a pair that is not an edge
+NO_VERTEX = 0xFFFFFFFF  # PPCSR_NO_VERTEX: what sample_neighbours / random_walks report where there is nothing to pick from
 
 _LIBS = {}
 
@@ -161,6 +164,13 @@ def load_library(path=None):
         getattr(L, name).argtypes = [c_vp, c_vp, ctypes.POINTER(c_u64), ctypes.POINTER(ctypes.c_double)]
     for name in ("ppcsr_common_neighbours", "ppcsr_common_neighbours_device", "pppcsr_common_neighbours"):
         getattr(L, name).argtypes = [c_vp, c_vp, c_vp, c_u64, c_vp, ctypes.POINTER(ctypes.c_double)]
+    for name in ("ppcsr_sample_neighbours", "ppcsr_sample_neighbours_device", "pppcsr_sample_neighbours"):
+        getattr(L, name).argtypes = [c_vp, c_vp, c_u64, c_u32, c_u64, c_u32, c_vp, c_vp, ctypes.POINTER(ctypes.c_double)]
+    for name in ("ppcsr_random_walks", "ppcsr_random_walks_device", "pppcsr_random_walks"):
+        getattr(L, name).argtypes = [c_vp, c_vp, c_u64, c_u32, c_u64, c_u32, c_vp, ctypes.POINTER(ctypes.c_double)]
+    for name in ("ppcsr_degrees", "pppcsr_degrees"):
+        getattr(L, name).argtypes = [c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_double)]
+    L.ppcsr_debug_mulhi.argtypes = [c_vp, c_vp, c_vp, c_u64, c_vp]
     L.ppcsr_bulk_build.argtypes = [c_vp, c_vp, c_u64, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_bfs.argtypes = [c_vp, c_u32, c_vp, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_pagerank.argtypes = [c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_double)]
@@ -346,6 +356,36 @@ class _Consumers:
         ms = self._consumer("common_neighbours", a.ctypes.data, b.ctypes.data, a.size, out.ctypes.data)
         return (out, ms) if with_ms else out
 
+    NO_VERTEX = NO_VERTEX
+
+    def sample_neighbours(self, vertices, fanout, seed=0, weighted=False, with_values=False, with_ms=False):
+        """uint32[k, fanout]: `fanout` neighbours of every vertex drawn with replacement, uniformly or in proportion to the edge
+        values (weighted); draw (seed, i, j) is the counter-based pick of include/ppcsr.h, NO_VERTEX where vertices[i] >= n or has
+        no neighbour.  with_values: the picked edges' values beside them (0 beside NO_VERTEX)."""
+        q = _u32(vertices)
+        out = np.empty((q.size, fanout), np.uint32)
+        vals = np.empty((q.size, fanout), np.uint32) if with_values else None
+        ms = self._consumer("sample_neighbours", q.ctypes.data, q.size, fanout, seed, 1 if weighted else 0, out.ctypes.data,
+                            vals.ctypes.data if with_values else None)
+        res = (out, vals) if with_values else (out,)
+        res = res + (ms,) if with_ms else res
+        return res[0] if len(res) == 1 else res
+
+    def random_walks(self, starts, length, seed=0, weighted=False, with_ms=False):
+        """uint32[k, length + 1]: row i starts at starts[i] and takes `length` steps, step t the pick of draw (seed, i, t) among the
+        current vertex's neighbours; NO_VERTEX from a vertex >= n or without neighbours on"""
+        q = _u32(starts)
+        out = np.empty((q.size, length + 1), np.uint32)
+        ms = self._consumer("random_walks", q.ctypes.data, q.size, length, seed, 1 if weighted else 0, out.ctypes.data)
+        return (out, ms) if with_ms else out
+
+    def degrees(self, weighted=False, with_ms=False):
+        """the live out-degree of every vertex (uint32: stored destinations < n), or with weighted the sum of their edge values
+        (uint64)"""
+        out = np.empty(self.get_n(), np.uint64 if weighted else np.uint32)
+        ms = self._consumer("degrees", None if weighted else out.ctypes.data, out.ctypes.data if weighted else None)
+        return (out, ms) if with_ms else out
+
 
 class PCSR(_Consumers):
     """Mirror of the reference class PCSR (PCSR.h:64-124) on one GPU."""
@@ -457,6 +497,27 @@ class PCSR(_Consumers):
         ms = ctypes.c_double(0.0)
         self._chk(self.L.ppcsr_common_neighbours_device(self.h, a_ptr, b_ptr, k, out_ptr, ctypes.byref(ms)))
         return ms.value if with_ms else None
+
+    def sample_neighbours_device(self, vertices_ptr, k, fanout, dests_ptr, values_ptr=None, seed=0, weighted=False, with_ms=False):
+        """sample_neighbours with vertices uint32[k], dests and values uint32[k * fanout] in this GPU's memory (values_ptr may be None)"""
+        ms = ctypes.c_double(0.0)
+        self._chk(self.L.ppcsr_sample_neighbours_device(self.h, vertices_ptr, k, fanout, seed, 1 if weighted else 0, dests_ptr,
+                                                        values_ptr or None, ctypes.byref(ms)))
+        return ms.value if with_ms else None
+
+    def random_walks_device(self, starts_ptr, k, length, out_ptr, seed=0, weighted=False, with_ms=False):
+        """random_walks with starts uint32[k] and out uint32[k * (length + 1)] in this GPU's memory"""
+        ms = ctypes.c_double(0.0)
+        self._chk(self.L.ppcsr_random_walks_device(self.h, starts_ptr, k, length, seed, 1 if weighted else 0, out_ptr, ctypes.byref(ms)))
+        return ms.value if with_ms else None
+
+    def debug_mulhi(self, a, b):
+        """Debugging: the high halves of the 128-bit products a[i] * b[i], computed on the device (ppcsr_debug_mulhi)"""
+        a, b = np.ascontiguousarray(a, np.uint64).reshape(-1), np.ascontiguousarray(b, np.uint64).reshape(-1)
+        assert a.size == b.size
+        out = np.empty(a.size, np.uint64)
+        self._chk(self.L.ppcsr_debug_mulhi(self.h, a.ctypes.data, b.ctypes.data, a.size, out.ctypes.data))
+        return out
 
     def geometry(self):
         N, lg, H = c_u64(), c_int(), c_int()

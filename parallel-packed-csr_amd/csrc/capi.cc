@@ -229,6 +229,52 @@ int ppcsr_common_neighbours_device(ppcsr_t h, const uint32_t *d_a, const uint32_
   const ppcsr::ConsumerRef self{h->e, 0};
   return ret(h->e, h->e->common_neighbours_over(&self, 1, h->e->n(), d_a, d_b, k, d_counts, true, device_ms));
 }
+// what sample_neighbours / random_walks refuse before anything is launched
+static int sample_args(const char *what, const void *in, const void *out, uint64_t k, uint32_t count, uint32_t flags) {
+  if (k && (!in || !out)) return bad((std::string(what) + ": null argument").c_str());
+  if (count == 0) return bad((std::string(what) + ": fanout / length must be at least 1").c_str());
+  if (flags & ~1u) return bad((std::string(what) + ": unknown flags").c_str());
+  return 0;
+}
+int ppcsr_sample_neighbours(ppcsr_t h, const uint32_t *vertices, uint64_t k, uint32_t fanout, uint64_t seed, uint32_t flags, uint32_t *dests,
+                            uint32_t *values, double *device_ms) {
+  H_CHECK();
+  if (sample_args("sample_neighbours", vertices, dests, k, fanout, flags)) return PPCSR_STATUS_EINVAL;
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->sample_over(&self, 1, h->e->n(), vertices, k, fanout, seed, flags, dests, values, false, device_ms));
+}
+int ppcsr_sample_neighbours_device(ppcsr_t h, const uint32_t *d_vertices, uint64_t k, uint32_t fanout, uint64_t seed, uint32_t flags,
+                                   uint32_t *d_dests, uint32_t *d_values, double *device_ms) {
+  H_CHECK();
+  if (sample_args("sample_neighbours", d_vertices, d_dests, k, fanout, flags)) return PPCSR_STATUS_EINVAL;
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->sample_over(&self, 1, h->e->n(), d_vertices, k, fanout, seed, flags, d_dests, d_values, true, device_ms));
+}
+int ppcsr_random_walks(ppcsr_t h, const uint32_t *starts, uint64_t k, uint32_t length, uint64_t seed, uint32_t flags, uint32_t *out,
+                       double *device_ms) {
+  H_CHECK();
+  if (sample_args("random_walks", starts, out, k, length, flags)) return PPCSR_STATUS_EINVAL;
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->walks_over(&self, 1, h->e->n(), starts, k, length, seed, flags, out, false, device_ms));
+}
+int ppcsr_random_walks_device(ppcsr_t h, const uint32_t *d_starts, uint64_t k, uint32_t length, uint64_t seed, uint32_t flags, uint32_t *d_out,
+                              double *device_ms) {
+  H_CHECK();
+  if (sample_args("random_walks", d_starts, d_out, k, length, flags)) return PPCSR_STATUS_EINVAL;
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->walks_over(&self, 1, h->e->n(), d_starts, k, length, seed, flags, d_out, true, device_ms));
+}
+int ppcsr_degrees(ppcsr_t h, uint32_t *deg, uint64_t *wsum, double *device_ms) {
+  H_CHECK();
+  if (!deg && !wsum) return bad("degrees: null outputs");
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->degrees_over(&self, 1, h->e->n(), deg, wsum, device_ms));
+}
+int ppcsr_debug_mulhi(ppcsr_t h, const uint64_t *a, const uint64_t *b, uint64_t k, uint64_t *out) {
+  H_CHECK();
+  if (k && (!a || !b || !out)) return bad("mulhi: null argument");
+  return ret(h->e, h->e->debug_mulhi(a, b, k, out));
+}
 int ppcsr_export_state(ppcsr_t h, ppcsr_edge *items, ppcsr_node *nodes) {
   H_CHECK();
   return ret(h->e, h->e->export_state(reinterpret_cast<ppcsr::Edge *>(items), reinterpret_cast<ppcsr::Node *>(nodes)));
@@ -791,6 +837,28 @@ int pppcsr_common_neighbours(pppcsr_t h, const uint32_t *a, const uint32_t *b, u
   return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) {
     return ret(e, e->common_neighbours_over(r, P, n, a, b, k, counts, false, device_ms));
   });
+}
+
+int pppcsr_sample_neighbours(pppcsr_t h, const uint32_t *vertices, uint64_t k, uint32_t fanout, uint64_t seed, uint32_t flags, uint32_t *dests,
+                             uint32_t *values, double *device_ms) {
+  PP_CHECK();
+  if (sample_args("sample_neighbours", vertices, dests, k, fanout, flags)) return PPCSR_STATUS_EINVAL;
+  return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) {
+    return ret(e, e->sample_over(r, P, n, vertices, k, fanout, seed, flags, dests, values, false, device_ms));
+  });
+}
+int pppcsr_random_walks(pppcsr_t h, const uint32_t *starts, uint64_t k, uint32_t length, uint64_t seed, uint32_t flags, uint32_t *out,
+                        double *device_ms) {
+  PP_CHECK();
+  if (sample_args("random_walks", starts, out, k, length, flags)) return PPCSR_STATUS_EINVAL;
+  return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) {
+    return ret(e, e->walks_over(r, P, n, starts, k, length, seed, flags, out, false, device_ms));
+  });
+}
+int pppcsr_degrees(pppcsr_t h, uint32_t *deg, uint64_t *wsum, double *device_ms) {
+  PP_CHECK();
+  if (!deg && !wsum) return bad("degrees: null outputs");
+  return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) { return ret(e, e->degrees_over(r, P, n, deg, wsum, device_ms)); });
 }
 
 int pppcsr_apply_parts_device(pppcsr_t h, uint64_t first_part, uint64_t n_parts, const ppcsr_op *const *d_ops, const uint64_t *counts) {

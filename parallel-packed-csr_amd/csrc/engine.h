@@ -135,6 +135,17 @@ class Engine {
   int triangles_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint64_t *tri, uint64_t *total, double *device_ms);
   int common_neighbours_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const uint32_t *a, const uint32_t *b, uint64_t k,
                              uint32_t *counts, bool on_device, double *device_ms);
+  // neighbour sampling, random walks and live degrees (pma_sample.h; the definition: include/ppcsr.h).  sample: dests / values
+  // [k * fanout] (values may be null); walks: out [k * (length + 1)]; vertices / starts and the outputs are host memory, or
+  // this GPU's when on_device.  Both fail with PPCSR_EUNSUPPORTED in the sequential regime (vertex ranges cannot be trusted).
+  // degrees: deg[v] = |L(v)|, wsum[v] = the sum of L(v)'s values (total_n entries, either may be null), in either regime.
+  // mulhi: the wave layer's 128-bit product on the device, for the tests (host pointers).
+  int sample_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const uint32_t *vertices, uint64_t k, uint32_t fanout, uint64_t seed,
+                  uint32_t flags, uint32_t *dests, uint32_t *values, bool on_device, double *device_ms);
+  int walks_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const uint32_t *starts, uint64_t k, uint32_t length, uint64_t seed,
+                 uint32_t flags, uint32_t *out, bool on_device, double *device_ms);
+  int degrees_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t *deg, uint64_t *wsum, double *device_ms);
+  int debug_mulhi(const uint64_t *a, const uint64_t *b, uint64_t k, uint64_t *out);
   int export_state(Edge *items, Node *nodes);
   int check_invariants(uint64_t *bad);  // leafcnt == recount(items)
   int stats(EngineStats *out);

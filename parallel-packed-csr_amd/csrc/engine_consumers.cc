@@ -1,5 +1,5 @@
 // Host drivers of the graph-algorithm consumers (kernels: pma_consumer.h, pma_scan.h, pma_paths.h, pma_cores.h, pma_centrality.h,
-// pma_scc.h, pma_msf.h, pma_intersect.h).  Included at the end of engine.cc: part of the engine's single translation unit, in the library
+// pma_scc.h, pma_msf.h, pma_intersect.h, pma_sample.h).  Included at the end of engine.cc: part of the engine's single translation unit, in the library
 // (csrc/ppcsr_hip.hip) and in the emulator (tests/hostsim/ppcsr_sim.cpp) alike.
 namespace ppcsr {
 
@@ -206,6 +206,9 @@ struct Engine::ConsumerScope {
     }
     return PPCSR_OK;
   }
+
+  // sample_over / walks_over: the hubs among d_q[0, k) (d_q == nullptr: among all vertices) and their measure prefix
+  int sample_hubs(uint32_t P, const uint32_t *d_q, uint64_t k, bool weighted, SmHubs *hb);
 };
 
 // bfs.h:15-36: level of every vertex from `start` (UINT32_MAX = unreachable); one launch per level, whatever the number of arrays
@@ -812,6 +815,143 @@ int Engine::common_neighbours_over(const ConsumerRef *parts, uint32_t P, uint32_
     GCHK(gpu::sync(p.stream));
     if (device_ms) *device_ms += p.timer.ms();
   }
+  return cs.done(nullptr);
+}
+
+// Sampling (pma_sample.h).  A vertex whose range is beyond kBfsWaveSlots is never walked by the wave of a draw: such vertices
+// are listed once per call — those among the queried vertices for sample_over, all of the graph for walks_over, whose walkers
+// may reach any of them — and the measure prefix over their 64-slot chunks is built once with the gather's chunk map and
+// scans.  Two host reads (the number of hubs, the number of their chunks); none when the launch meets no hub.
+int Engine::ConsumerScope::sample_hubs(uint32_t P, const uint32_t *d_q, uint64_t k, bool weighted, SmHubs *hb) {
+  const uint64_t cap = slots_ / kBfsWaveSlots + 1;  // (ranges are disjoint in the regular regime)
+  uint32_t *d_hid = alloc<uint32_t>("d_hid", words());
+  uint32_t *d_part = alloc<uint32_t>("d_part", cap), *d_lo = alloc<uint32_t>("d_lo", cap), *d_len = alloc<uint32_t>("d_len", cap);
+  uint32_t *d_nch = alloc<uint32_t>("d_nch", cap), *d_cnt = alloc<uint32_t>("d_cnt", 1);
+  unsigned long long *d_choff = alloc<unsigned long long>("d_choff", cap + 1);
+  if (rc != PPCSR_OK) return rc;
+  GCHK(gpu::dset(d_hid, 0xFF, words() * sizeof(uint32_t), p.stream));
+  GCHK(gpu::dset(d_cnt, 0, sizeof(uint32_t), p.stream));
+  GPU_LAUNCH(p.stream, k_sm_hubs, grid_for(k, 256, 4096), 256, tab_, P, n_, d_q, k, d_hid, d_part, d_lo, d_len, d_nch, (uint32_t)cap, d_cnt);
+  uint32_t nhub = 0;
+  int e = read_back(&nhub, d_cnt, sizeof(uint32_t));
+  if (e != PPCSR_OK) return e;
+  if (nhub > cap) return fail(PPCSR_EHIP, "sampling: more long vertex ranges than the arrays have room for");
+  *hb = SmHubs{d_hid, d_part, d_lo, d_len, d_choff, nullptr};
+  if (nhub == 0) return PPCSR_OK;
+  e = eng.xscan(d_nch, false, nhub, d_choff, true, false, false);
+  if (e != PPCSR_OK) return e;
+  unsigned long long C = 0;
+  e = read_back(&C, d_choff + nhub, sizeof(unsigned long long));
+  if (e != PPCSR_OK) return e;
+  uint32_t *d_crow = alloc<uint32_t>("d_crow", C);
+  unsigned long long *d_cm = alloc<unsigned long long>("d_cm", C), *d_cpre = alloc<unsigned long long>("d_cpre", C + 1);
+  if (rc != PPCSR_OK) return rc;
+  GCHK(gpu::dset(d_crow, 0, C * sizeof(uint32_t), p.stream));
+  GPU_LAUNCH(p.stream, k_gather_mark, grid_for(nhub, 256, 4096), 256, (const uint32_t *)d_nch, (const unsigned long long *)d_choff, (uint64_t)nhub,
+             d_crow);
+  e = eng.xscan(d_crow, false, C, d_crow, false, true, true);
+  if (e != PPCSR_OK) return e;
+  hb->cpre = d_cpre;
+  GPU_LAUNCH(p.stream, k_sm_hub_count, grid_for((C + 63) / 64, 4, 8192), 256, tab_, n_, *hb, (const uint32_t *)d_crow, (uint64_t)C,
+             weighted ? 1u : 0u, d_cm);
+  return eng.xscan(d_cm, true, C, d_cpre, true, false, false);
+}
+
+// dests[i * fanout + j] = draw (seed, i, j) from L(vertices[i]), values beside them
+int Engine::sample_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const uint32_t *vertices, uint64_t k, uint32_t fanout, uint64_t seed,
+                        uint32_t flags, uint32_t *dests, uint32_t *values, bool on_device, double *device_ms) {
+  ConsumerScope cs(this);
+  int rc = cs.open(parts, P, total_n, "sample_neighbours");
+  if (rc != PPCSR_OK) return rc;
+  if (device_ms) *device_ms = 0.0;
+  if (k == 0) return PPCSR_OK;
+  const ConsumerPart *tab = cs.table();
+  const uint64_t cells = k * (uint64_t)fanout;
+  const uint32_t *d_q = vertices;
+  uint32_t *d_d = dests, *d_v = values;
+  if (!on_device) {
+    uint32_t *q = cs.alloc<uint32_t>("d_q", k);
+    d_d = cs.alloc<uint32_t>("d_dests", cells);
+    d_v = values ? cs.alloc<uint32_t>("d_values", cells) : nullptr;
+    if (cs.rc != PPCSR_OK) return cs.rc;
+    GCHK(gpu::h2d(q, vertices, k * sizeof(uint32_t), cs.stream()));
+    d_q = q;
+  }
+  cs.start();
+  SmHubs hb{};
+  rc = cs.sample_hubs(P, d_q, k, (flags & kSmWeighted) != 0, &hb);
+  if (rc != PPCSR_OK) return rc;
+  GPU_LAUNCH(cs.stream(), k_sm_sample, cs.list_grid(k), 256, tab, P, total_n, hb, d_q, k, 0ull, fanout, (unsigned long long)seed, flags, d_d, d_v);
+  cs.stop();
+  if (!on_device) {
+    GCHK(gpu::d2h(dests, d_d, cells * sizeof(uint32_t), cs.stream()));
+    if (values) GCHK(gpu::d2h(values, d_v, cells * sizeof(uint32_t), cs.stream()));
+  }
+  return cs.done(device_ms);
+}
+
+// out[i][0] = starts[i], out[i][t + 1] = draw (seed, i, t) from L(out[i][t]): one launch per step over all walkers.  The hubs'
+// prefix is built ONCE, for every hub of the graph, before the first step: no step recounts a hub, and no step reads back.
+int Engine::walks_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const uint32_t *starts, uint64_t k, uint32_t length, uint64_t seed,
+                       uint32_t flags, uint32_t *out, bool on_device, double *device_ms) {
+  ConsumerScope cs(this);
+  int rc = cs.open(parts, P, total_n, "random_walks");
+  if (rc != PPCSR_OK) return rc;
+  if (device_ms) *device_ms = 0.0;
+  if (k == 0) return PPCSR_OK;
+  const ConsumerPart *tab = cs.table();
+  const uint64_t cells = k * ((uint64_t)length + 1);
+  const uint32_t *d_q = starts;
+  uint32_t *d_out = out;
+  if (!on_device) {
+    uint32_t *q = cs.alloc<uint32_t>("d_q", k);
+    d_out = cs.alloc<uint32_t>("d_out", cells);
+    if (cs.rc != PPCSR_OK) return cs.rc;
+    GCHK(gpu::h2d(q, starts, k * sizeof(uint32_t), cs.stream()));
+    d_q = q;
+  }
+  cs.start();
+  SmHubs hb{};
+  rc = cs.sample_hubs(P, nullptr, total_n, (flags & kSmWeighted) != 0, &hb);
+  if (rc != PPCSR_OK) return rc;
+  GPU_LAUNCH(cs.stream(), k_sm_walk_init, grid_for(k, 256, 4096), 256, d_q, k, total_n, length, d_out);
+  for (uint32_t t = 0; t < length; t++)
+    GPU_LAUNCH(cs.stream(), k_sm_walk, cs.list_grid(k), 256, tab, P, total_n, hb, d_out, k, 0ull, length, t, (unsigned long long)seed, flags);
+  cs.stop();
+  if (!on_device) GCHK(gpu::d2h(out, d_out, cells * sizeof(uint32_t), cs.stream()));
+  return cs.done(device_ms);
+}
+
+// |L(v)| and the weighted W(v) of every vertex: one streaming pass, sources from the items (either regime)
+int Engine::degrees_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t *deg, uint64_t *wsum, double *device_ms) {
+  ConsumerScope cs(this);
+  const int rc = cs.open(parts, P, total_n);
+  if (rc != PPCSR_OK) return rc;
+  const ConsumerPart *tab = cs.table();
+  uint32_t *d_deg = deg ? cs.alloc<uint32_t>("d_deg", cs.words()) : nullptr;
+  unsigned long long *d_ws = wsum ? cs.alloc<unsigned long long>("d_wsum", cs.words()) : nullptr;
+  if (cs.rc != PPCSR_OK) return cs.rc;
+  cs.start();
+  if (deg) GCHK(gpu::dset(d_deg, 0, cs.words() * sizeof(uint32_t), cs.stream()));
+  if (wsum) GCHK(gpu::dset(d_ws, 0, cs.words() * sizeof(unsigned long long), cs.stream()));
+  GPU_LAUNCH(cs.stream(), k_sm_degrees, cs.pass_grid(), 256, tab, P, total_n, d_deg, d_ws);
+  cs.stop();
+  if (deg && total_n) GCHK(gpu::d2h(deg, d_deg, (uint64_t)total_n * sizeof(uint32_t), cs.stream()));
+  if (wsum && total_n) GCHK(gpu::d2h(wsum, d_ws, (uint64_t)total_n * sizeof(uint64_t), cs.stream()));
+  return cs.done(device_ms);
+}
+
+int Engine::debug_mulhi(const uint64_t *a, const uint64_t *b, uint64_t k, uint64_t *out) {
+  if (k == 0) return PPCSR_OK;
+  ConsumerScope cs(this);
+  GCHK(gpu::set_device(device_));
+  unsigned long long *d_a = cs.alloc<unsigned long long>("d_a", k), *d_b = cs.alloc<unsigned long long>("d_b", k);
+  unsigned long long *d_o = cs.alloc<unsigned long long>("d_o", k);
+  if (cs.rc != PPCSR_OK) return cs.rc;
+  GCHK(gpu::h2d(d_a, a, k * sizeof(uint64_t), cs.stream()));
+  GCHK(gpu::h2d(d_b, b, k * sizeof(uint64_t), cs.stream()));
+  GPU_LAUNCH(cs.stream(), k_sm_mulhi, grid_for(k, 256, 4096), 256, (const unsigned long long *)d_a, (const unsigned long long *)d_b, k, d_o);
+  GCHK(gpu::d2h(out, d_o, k * sizeof(uint64_t), cs.stream()));
   return cs.done(nullptr);
 }
 

@@ -13,6 +13,7 @@
 //   pma_intersect.h    triangle counts and common-neighbour counts: sorted intersection of two gapped vertex ranges
 //   pma_isect_probe.h  debugging probe of the intersection routines (ppcsr_debug_isect_probe)
 //   pma_query.h        batched reads: edge lookups with values, neighbourhood gathers
+//   pma_sample.h       neighbour sampling, random walks, live degrees: rank / weight select over gapped ranges, hub prefix per call
 //   pma_exchange.h     owner bucketing for the multi-GPU exchange
 #pragma once
 #include "pma_rounds.h"
@@ -29,4 +30,5 @@
 #include "pma_intersect.h"
 #include "pma_isect_probe.h"
 #include "pma_query.h"
+#include "pma_sample.h"
 #include "pma_exchange.h"

@@ -111,3 +111,14 @@ PMA_DEV uint32_t grid_dim() { return gridDim.x; }
 }  // namespace wv
 }  // namespace ppcsr
 #endif
+
+namespace ppcsr {
+namespace wv {
+// high half of the 128-bit product of two 64-bit words (the draws of pma_sample.h)
+#if defined(PPCSR_SIM)
+inline unsigned long long mulhi64(unsigned long long a, unsigned long long b) { return (unsigned long long)(((unsigned __int128)a * b) >> 64); }
+#else
+PMA_DEV unsigned long long mulhi64(unsigned long long a, unsigned long long b) { return __umul64hi(a, b); }
+#endif
+}  // namespace wv
+}  // namespace ppcsr
