@@ -298,6 +298,31 @@ int ppcsr_degrees(ppcsr_t h, uint32_t *deg, uint64_t *wsum, double *device_ms);
 /* Debugging: out[i] = the high half of a[i] * b[i], computed on the device by the wave layer's wrapper the draws use (host
  * pointers, k entries each).  EINVAL: null handle, a null pointer with k > 0. */
 int ppcsr_debug_mulhi(ppcsr_t h, const uint64_t *a, const uint64_t *b, uint64_t k, uint64_t *out);
+/* ---- multi-source BFS: the levels from k sources in one call, with the sums closeness and eccentricity are made of ----
+ * The edge set is ppcsr_bfs's (live, non-sentinel slots other than slot N-1, src < n, dest < n; directed, values unused), and
+ * the distances are OUT-distances: from the source along stored edges.  For closeness over incoming paths store the transpose.
+ * With c_i(L) = the number of vertices at level L >= 1 from sources[i]:
+ *   levels (k * n words, row-major) — row i is what ppcsr_bfs(h, sources[i], ...) returns, word for word (UINT32_MAX: unreachable)
+ *   reached[i]  = vertices with a finite level, the source included
+ *   far[i]      = sum over L of L * c_i(L)  (64-bit: n (n - 1) < 2^64, nothing saturates)
+ *   ecc[i]      = the largest finite level (0 when nothing but the source is reached)
+ *   harmonic[i] = sum over L = 1 .. ecc[i] of (double)c_i(L) / (double)L, added in ascending L, left to right, in fp64 on the
+ *                 host from the integer counts: one division per level, nothing fused — a bit-reproducible number
+ * Each of the five outputs may be NULL, not all five when k > 0.  Repeated sources are separate rows.  Sources are handled 64 at
+ * a time, one bit each in a 64-bit word per vertex; a group of 64 costs about the streaming passes of one ppcsr_bfs.
+ * Same contract as bfs: synchronous on the engine's stream, sees every batch applied before it, nothing of the graph is
+ * written (state, stats, dirty tags, snapshot unchanged), device_ms may be NULL (it covers the level loops, not the copy of
+ * levels to the host).  Every refusal is made before the first launch.  EINVAL: null handle, sources NULL with k > 0, all five
+ * outputs NULL with k > 0, any sources[i] >= n; k == 0 succeeds and writes nothing.
+ * Sequential regime (stats.narrow == 0): the call still answers; every level is then a streaming pass that takes each edge's
+ * source from the item itself, as ppcsr_degrees / ppcsr_scc do — node ranges are never walked there. */
+int ppcsr_multi_bfs(ppcsr_t h, const uint32_t *sources, uint64_t k, uint32_t *levels, uint64_t *reached, uint64_t *far, uint32_t *ecc,
+                    double *harmonic, double *device_ms);
+/* Debugging: what the last ppcsr_multi_bfs / pppcsr_multi_bfs run by this engine did, kept on the host from the reads the call
+ * makes anyway: [0] groups of 64 sources, [1] level steps (all groups), [2] streaming edge passes, [3] per-vertex edge launches,
+ * [4] passes that finished the hubs of a per-vertex launch, [5] largest union frontier of any step, [6] vertex-step launches,
+ * [7] host reads inside the timed region.  EINVAL: null handle, out NULL. */
+int ppcsr_debug_multi_bfs_counters(ppcsr_t h, uint64_t out[8]);
 /* raw state for parity checks: items[N], nodes[n] exactly as the reference holds them (PCSR.h:67,128) */
 int ppcsr_export_state(ppcsr_t h, ppcsr_edge *items, ppcsr_node *nodes);
 int ppcsr_stats(ppcsr_t h, ppcsr_stats_t *out);
@@ -312,6 +337,7 @@ int ppcsr_stats(ppcsr_t h, ppcsr_stats_t *out);
  *              "rb_tile", "rb_min_tiles", "rb_prefetch", "rb_inplace_min" (partial windows of at least this many slots are
  *              rebalanced in place; 0 = always through the scratch array), "rb_inplace_cpw", "rb_inplace_lists"
  *   search     "search_narrow" (0: literal binary walk only)
+ *   consumers  "msbfs_look" (0: the streaming pass of ppcsr_multi_bfs issues its ORs without first looking at next[w]; default 1)
  *   measuring  "profile" (1: HIP events around every round kernel, reported through ppcsr_stats), "diag" (1: why updates
  *              did not commit, per epoch, on stderr; 2: also a per-update dependency trace, PPCSR_DIAG_DUMP = file), "marker" (marker kernels for profile cuts), "test_block_rebalance"
  *   reads      test hooks that move the seams of the batched reads (defaults = the shipped sizes; values in [1, 2^32]):
@@ -497,6 +523,12 @@ int pppcsr_sample_neighbours(pppcsr_t h, const uint32_t *vertices, uint64_t k, u
 int pppcsr_random_walks(pppcsr_t h, const uint32_t *starts, uint64_t k, uint32_t length, uint64_t seed, uint32_t flags, uint32_t *out,
                         double *device_ms);
 int pppcsr_degrees(pppcsr_t h, uint32_t *deg, uint64_t *wsum, double *device_ms);
+/* ppcsr_multi_bfs over the GLOBAL vertex ids (sources global; levels: k * pppcsr_get_n words), one device call over every
+ * partition's array; the results do not depend on the partitioning.  Same contract as pppcsr_bfs; the sequential regime of any
+ * partition makes every level a streaming pass.  EINVAL: as the single call, or a partition not resident in this process.
+ * EUNSUPPORTED: the partitions sit on more than one device.  The counters are kept by the first partition's engine. */
+int pppcsr_multi_bfs(pppcsr_t h, const uint32_t *sources, uint64_t k, uint32_t *levels, uint64_t *reached, uint64_t *far, uint32_t *ecc,
+                     double *harmonic, double *device_ms);
 /* bucket a host stream by owner (stable: per-partition order == stream order, src made partition-local as in
  * PPPCSR.cpp:46-52) and apply each bucket on its partition's GPU */
 int pppcsr_apply_batch(pppcsr_t h, const ppcsr_op *ops, uint64_t n);

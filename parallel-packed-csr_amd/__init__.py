@@ -79,6 +79,7 @@ EXPORTED = [
     "ppcsr_triangles", "pppcsr_triangles", "ppcsr_common_neighbours", "ppcsr_common_neighbours_device", "pppcsr_common_neighbours",
     "ppcsr_sample_neighbours", "ppcsr_sample_neighbours_device", "pppcsr_sample_neighbours",
     "ppcsr_random_walks", "ppcsr_random_walks_device", "pppcsr_random_walks", "ppcsr_degrees", "pppcsr_degrees", "ppcsr_debug_mulhi",
+    "ppcsr_multi_bfs", "pppcsr_multi_bfs", "ppcsr_debug_multi_bfs_counters",
 ]
 
 NO_PATH = 0xFFFFFFFFFFFFFFFF  # PPCSR_NO_PATH: what sssp reports for a vertex no path reaches
@@ -171,6 +172,9 @@ def load_library(path=None):
     for name in ("ppcsr_degrees", "pppcsr_degrees"):
         getattr(L, name).argtypes = [c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_debug_mulhi.argtypes = [c_vp, c_vp, c_vp, c_u64, c_vp]
+    for name in ("ppcsr_multi_bfs", "pppcsr_multi_bfs"):
+        getattr(L, name).argtypes = [c_vp, c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_double)]
+    L.ppcsr_debug_multi_bfs_counters.argtypes = [c_vp, c_vp]
     L.ppcsr_bulk_build.argtypes = [c_vp, c_vp, c_u64, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_bfs.argtypes = [c_vp, c_u32, c_vp, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_pagerank.argtypes = [c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_double)]
@@ -386,6 +390,30 @@ class _Consumers:
         ms = self._consumer("degrees", None if weighted else out.ctypes.data, out.ctypes.data if weighted else None)
         return (out, ms) if with_ms else out
 
+    def multi_bfs(self, sources, levels=False, with_ms=False):
+        """(reached, far, ecc, harmonic[, levels][, ms]) from every source at once, 64 sources to a 64-bit word per vertex:
+        reached[i] = vertices with a finite level from sources[i], itself included (uint64); far[i] = the sum of their levels
+        (uint64); ecc[i] = the largest of them (uint32); harmonic[i] = the sum of 1 / level over the others (float64, added level
+        by level: include/ppcsr.h).  levels: row i is bfs(sources[i]) (uint32[k, n]).  The distances are OUT-distances, along
+        stored edges away from the source; repeated sources are separate rows."""
+        q = _u32(sources)
+        k, n = q.size, self.get_n()
+        reached, far = np.empty(k, np.uint64), np.empty(k, np.uint64)
+        ecc, harm = np.empty(k, np.uint32), np.empty(k, np.float64)
+        lv = np.empty((k, n), np.uint32) if levels else None
+        ms = self._consumer("multi_bfs", q.ctypes.data if k else None, k, lv.ctypes.data if levels else None, reached.ctypes.data,
+                            far.ctypes.data, ecc.ctypes.data, harm.ctypes.data)
+        res = (reached, far, ecc, harm) + ((lv,) if levels else ()) + ((ms,) if with_ms else ())
+        return res
+
+    def closeness(self, sources):
+        """(reached - 1) / far per source (float64), 0 where far == 0: the reciprocal of the mean OUT-distance to the vertices
+        the source reaches (for closeness over incoming paths store the transpose)"""
+        reached, far, _, _ = self.multi_bfs(sources)
+        out = np.zeros(reached.size, np.float64)
+        np.divide((reached - np.uint64(1)).astype(np.float64), far.astype(np.float64), out=out, where=far != 0)
+        return out
+
 
 class PCSR(_Consumers):
     """Mirror of the reference class PCSR (PCSR.h:64-124) on one GPU."""
@@ -559,6 +587,14 @@ class PCSR(_Consumers):
         out = np.zeros(6, np.uint64)
         self._chk(self.L.ppcsr_debug_snap_counters(self.h, out.ctypes.data))
         return dict(zip(("full_saves", "full_loads", "inc_commits", "inc_rollbacks", "leaves_copied", "nodes_copied"), (int(x) for x in out)))
+
+    def debug_multi_bfs_counters(self):
+        """Debugging (ppcsr_debug_multi_bfs_counters): uint64[8] of the last multi_bfs call on this engine — groups, level steps,
+        streaming edge passes, per-vertex edge launches, passes that finished hubs, largest union frontier, vertex-step launches,
+        host reads"""
+        out = np.zeros(8, np.uint64)
+        self._chk(self.L.ppcsr_debug_multi_bfs_counters(self.h, out.ctypes.data))
+        return out
 
     def debug_scc_counters(self):
         """Debugging (ppcsr_debug_scc_counters): uint64[8] of the last scc call on this engine — vertices trimmed, trim sweeps,
@@ -747,6 +783,10 @@ class PPPCSR(_Consumers):
         out = c_vp()
         self._chk(self.L.pppcsr_partition(self.h, k, ctypes.byref(out)))
         return PCSR(0, lib=self.L, _handle=out.value)
+
+    def debug_multi_bfs_counters(self):
+        """the counters of the last multi_bfs call: kept by the engine that ran it, the first partition's"""
+        return self.partition(0).debug_multi_bfs_counters()
 
     def debug_scc_counters(self):
         """the counters of the last scc call: kept by the engine that ran it, the first partition's"""

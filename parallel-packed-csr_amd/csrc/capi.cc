@@ -204,6 +204,21 @@ int ppcsr_scc(ppcsr_t h, uint32_t *labels, uint64_t *count, double *device_ms) {
   return ret(h->e, h->e->scc_over(&self, 1, h->e->n(), labels, count, device_ms));
 }
 int ppcsr_debug_scc_counters(ppcsr_t h, uint64_t out[8]) { H_CHECK(); return ret(h->e, h->e->scc_counters(out)); }
+// the argument checks ppcsr_multi_bfs and pppcsr_multi_bfs share (true: refused)
+static bool multi_bfs_args(const uint32_t *sources, uint64_t k, const void *levels, const void *reached, const void *far, const void *ecc,
+                           const void *harmonic) {
+  if (!sources && k > 0) return bad("multi_bfs: null sources") != 0;
+  if (k > 0 && !levels && !reached && !far && !ecc && !harmonic) return bad("multi_bfs: null outputs") != 0;
+  return false;
+}
+int ppcsr_multi_bfs(ppcsr_t h, const uint32_t *sources, uint64_t k, uint32_t *levels, uint64_t *reached, uint64_t *far, uint32_t *ecc,
+                    double *harmonic, double *device_ms) {
+  H_CHECK();
+  if (multi_bfs_args(sources, k, levels, reached, far, ecc, harmonic)) return PPCSR_STATUS_EINVAL;
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->multi_bfs_over(&self, 1, h->e->n(), sources, k, levels, reached, far, ecc, harmonic, device_ms));
+}
+int ppcsr_debug_multi_bfs_counters(ppcsr_t h, uint64_t out[8]) { H_CHECK(); return ret(h->e, h->e->multi_bfs_counters(out)); }
 int ppcsr_msf(ppcsr_t h, ppcsr_edge *edges, uint64_t cap, uint64_t *count, uint64_t *weight, uint32_t *labels, double *device_ms) {
   H_CHECK();
   if (!edges && !count && !weight && !labels) return bad("msf: null outputs");
@@ -818,6 +833,16 @@ int pppcsr_scc(pppcsr_t h, uint32_t *labels, uint64_t *count, double *device_ms)
   PP_CHECK();
   if (!labels && !count) return bad("scc: null outputs");
   return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) { return ret(e, e->scc_over(r, P, n, labels, count, device_ms)); });
+}
+int pppcsr_multi_bfs(pppcsr_t h, const uint32_t *sources, uint64_t k, uint32_t *levels, uint64_t *reached, uint64_t *far, uint32_t *ecc,
+                     double *harmonic, double *device_ms) {
+  PP_CHECK();
+  if (multi_bfs_args(sources, k, levels, reached, far, ecc, harmonic)) return PPCSR_STATUS_EINVAL;
+  return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) {
+    for (uint64_t i = 0; i < k; i++)
+      if (sources[i] >= n) return bad("multi_bfs: source vertex out of range");
+    return ret(e, e->multi_bfs_over(r, P, n, sources, k, levels, reached, far, ecc, harmonic, device_ms));
+  });
 }
 int pppcsr_msf(pppcsr_t h, ppcsr_edge *edges, uint64_t cap, uint64_t *count, uint64_t *weight, uint32_t *labels, double *device_ms) {
   PP_CHECK();

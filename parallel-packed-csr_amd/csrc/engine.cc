@@ -98,6 +98,8 @@ struct Engine::Impl {
   // what the last scc_over on this engine did (ppcsr_debug_scc_counters): kept on the host from the reads the call makes anyway
   uint64_t scc_ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t msf_ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the same for msf_over (ppcsr_debug_msf_counters)
+  uint64_t msbfs_ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the same for multi_bfs_over (ppcsr_debug_multi_bfs_counters)
+  uint32_t msbfs_look = 1;  // multi_bfs_over's pass looks at next[w] before it issues an OR (0: the variant tools/multibfs_bench.py measures)
   // dirty tags: writers stamp View::ldirty / vdirty with `serial`; every snapshot synchronisation advances it
   uint32_t serial = 1;
   uint64_t array_gen = 1;
@@ -682,6 +684,10 @@ int Engine::set_option(const char *key, int64_t value) {
   }
   if (k == "rb_prefetch") {
     p.rb_prefetch = value ? 1u : 0u;
+    return PPCSR_OK;
+  }
+  if (k == "msbfs_look") {
+    p.msbfs_look = value ? 1u : 0u;
     return PPCSR_OK;
   }
   if (k == "scatter_variant") {

@@ -146,6 +146,13 @@ class Engine {
                  uint32_t flags, uint32_t *out, bool on_device, double *device_ms);
   int degrees_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t *deg, uint64_t *wsum, double *device_ms);
   int debug_mulhi(const uint64_t *a, const uint64_t *b, uint64_t k, uint64_t *out);
+  // multi-source BFS (pma_msbfs.h; the definition: include/ppcsr.h), in either regime: row i of levels (k * total_n words) as
+  // bfs_over gives it from sources[i]; reached / far / ecc / harmonic: k entries each; every output may be null.  A source
+  // >= total_n is refused before the first launch; k == 0 writes nothing.  multi_bfs_counters: what the last multi_bfs_over
+  // on this engine did (ppcsr_debug_multi_bfs_counters)
+  int multi_bfs_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const uint32_t *sources, uint64_t k, uint32_t *levels,
+                     uint64_t *reached, uint64_t *far, uint32_t *ecc, double *harmonic, double *device_ms);
+  int multi_bfs_counters(uint64_t out[8]);
   int export_state(Edge *items, Node *nodes);
   int check_invariants(uint64_t *bad);  // leafcnt == recount(items)
   int stats(EngineStats *out);

@@ -1,5 +1,5 @@
 // Host drivers of the graph-algorithm consumers (kernels: pma_consumer.h, pma_scan.h, pma_paths.h, pma_cores.h, pma_centrality.h,
-// pma_scc.h, pma_msf.h, pma_intersect.h, pma_sample.h).  Included at the end of engine.cc: part of the engine's single translation unit, in the library
+// pma_scc.h, pma_msf.h, pma_intersect.h, pma_sample.h, pma_msbfs.h).  Included at the end of engine.cc: part of the engine's single translation unit, in the library
 // (csrc/ppcsr_hip.hip) and in the emulator (tests/hostsim/ppcsr_sim.cpp) alike.
 namespace ppcsr {
 
@@ -939,6 +939,152 @@ int Engine::degrees_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n,
   if (deg && total_n) GCHK(gpu::d2h(deg, d_deg, (uint64_t)total_n * sizeof(uint32_t), cs.stream()));
   if (wsum && total_n) GCHK(gpu::d2h(wsum, d_ws, (uint64_t)total_n * sizeof(uint64_t), cs.stream()));
   return cs.done(device_ms);
+}
+
+// Multi-source BFS (pma_msbfs.h): the sources in groups of 64, a group's levels until one finds nothing.  The loop is the
+// hybrid loop's — a union frontier of at least hybrid_big vertices takes one streaming pass, a smaller one is listed (from
+// stamp[] by k_bfs_collect when the level before was a pass) and expanded one wave per vertex, and hubs that launch leaves
+// behind are finished by one pass — with a vertex step behind every edge step.  One host read per level: the 64 counts, the
+// length of the next list and the hub flag (a level whose per-vertex launch met a hub is read twice: the listed vertex step
+// declines to run, and the pass and the step over all n follow).  In the sequential regime every level is a pass: node
+// ranges are never walked.  device_ms adds the groups' loops up; the copy of a group's rows to the caller lies between them.
+int Engine::multi_bfs_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const uint32_t *sources, uint64_t k, uint32_t *levels,
+                           uint64_t *reached, uint64_t *far, uint32_t *ecc, double *harmonic, double *device_ms) {
+  const uint32_t nn = total_n;
+  for (uint64_t i = 0; i < k; i++)
+    if (sources[i] >= nn) return fail(PPCSR_EINVAL, "multi_bfs: source vertex out of range");
+  if (k == 0) return PPCSR_OK;
+  bool ranges = true;  // node ranges may be walked: no partition is in the sequential regime
+  for (uint32_t q = 0; q < P; q++) ranges = ranges && parts[q].e->p_->v.g.narrow != 0u;
+  ConsumerScope cs(this);
+  const int rc = cs.open(parts, P, nn);
+  if (rc != PPCSR_OK) return rc;
+  const ConsumerPart *tab = cs.table();
+  const uint64_t bit_words = ((uint64_t)nn + 63) / 64 * 2;  // union-frontier bitmap of the passes (d_vb: k_bfs_bits' second output, unused)
+  uint32_t *d_fb = cs.alloc<uint32_t>("d_fb", bit_words), *d_vb = cs.alloc<uint32_t>("d_vb", bit_words);
+  unsigned long long *d_seen = cs.alloc<unsigned long long>("d_seen", nn), *d_front = cs.alloc<unsigned long long>("d_front", nn);
+  unsigned long long *d_next = cs.alloc<unsigned long long>("d_next", nn), *d_sw = cs.alloc<unsigned long long>("d_sw", 64);
+  uint32_t *d_st = cs.alloc<uint32_t>("d_st", nn), *d_f0 = cs.alloc<uint32_t>("d_f0", nn), *d_f1 = cs.alloc<uint32_t>("d_f1", nn);
+  uint32_t *d_lvg = levels ? cs.alloc<uint32_t>("d_levels", std::min<uint64_t>(k, 64) * nn) : nullptr;
+  ConsumerScope::Striped<uint32_t, kMsStripeWords, kMsLead> cnt(cs, "d_cnt");
+  uint32_t *const d_cnt = cnt.dev, *const d_stripes = cnt.stripes();  // (a launch's arguments are plain pointers)
+  if (cs.rc != PPCSR_OK) return cs.rc;
+  const uint32_t big = ConsumerScope::hybrid_big(nn);
+  const bool look = p_->msbfs_look != 0u;
+  uint64_t ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double ms = 0;
+  for (uint64_t g0 = 0; g0 < k; g0 += 64) {
+    const uint32_t nbits = (uint32_t)std::min<uint64_t>(64, k - g0);
+    uint32_t verts[64], nv = 0;
+    unsigned long long words[64];
+    for (uint32_t b = 0; b < nbits; b++) {  // repeated sources share a vertex's word
+      uint32_t at = 0;
+      while (at < nv && verts[at] != sources[g0 + b]) at++;
+      if (at == nv) {
+        verts[nv] = sources[g0 + b];
+        words[nv++] = 0;
+      }
+      words[at] |= 1ull << b;
+    }
+    uint64_t g_reached[64], g_far[64];
+    uint32_t g_ecc[64];
+    double g_harm[64];
+    for (uint32_t b = 0; b < 64; b++) g_reached[b] = 1, g_far[b] = 0, g_ecc[b] = 0, g_harm[b] = 0.0;
+    ctr[0]++;
+    cs.start();
+    GCHK(gpu::dset(d_seen, 0, (uint64_t)nn * sizeof(unsigned long long), cs.stream()));
+    GCHK(gpu::dset(d_front, 0, (uint64_t)nn * sizeof(unsigned long long), cs.stream()));
+    GCHK(gpu::dset(d_next, 0, (uint64_t)nn * sizeof(unsigned long long), cs.stream()));
+    GCHK(gpu::dset(d_st, 0xFF, (uint64_t)nn * sizeof(uint32_t), cs.stream()));
+    if (d_lvg) GCHK(gpu::dset(d_lvg, 0xFF, (uint64_t)nbits * nn * sizeof(uint32_t), cs.stream()));
+    GCHK(gpu::h2d(d_f0, verts, nv * sizeof(uint32_t), cs.stream()));
+    GCHK(gpu::h2d(d_sw, words, nv * sizeof(unsigned long long), cs.stream()));
+    GPU_LAUNCH(cs.stream(), k_ms_init, 1, 64, (const uint32_t *)d_f0, (const unsigned long long *)d_sw, nv, nn, d_seen, d_front, d_st, d_lvg);
+    const auto full = [&](uint32_t level) {  // the edge step as a pass, the vertex step over all n
+      GPU_LAUNCH(cs.stream(), k_bfs_bits, cs.vert_grid(), 256, (const uint32_t *)d_st, nn, level, d_fb, d_vb);
+      if (look)
+        GPU_LAUNCH(cs.stream(), k_ms_edges<true>, cs.pass_grid(), 256, tab, P, nn, (const uint32_t *)d_fb, (const unsigned long long *)d_front,
+                   (const unsigned long long *)d_seen, d_next);
+      else
+        GPU_LAUNCH(cs.stream(), k_ms_edges<false>, cs.pass_grid(), 256, tab, P, nn, (const uint32_t *)d_fb, (const unsigned long long *)d_front,
+                   (const unsigned long long *)d_seen, d_next);
+      GPU_LAUNCH(cs.stream(), k_ms_vertices, cs.vert_grid(), 256, nn, (const uint32_t *)nullptr, (const uint32_t *)d_cnt, level, nbits, d_seen,
+                 d_front, d_next, d_st, d_lvg, d_stripes);
+      ctr[2]++;
+      ctr[6]++;
+    };
+    uint32_t nfront = nv;
+    uint32_t *cur = d_f0, *nxt = d_f1;
+    bool have_list = true;
+    for (uint32_t level = 0; nfront > 0; level++) {
+      ctr[1]++;
+      ctr[5] = std::max<uint64_t>(ctr[5], nfront);
+      GCHK(cnt.zero());
+      bool listed = ranges && nfront < big;
+      if (!listed) {
+        full(level);
+        have_list = false;
+      } else {
+        if (!have_list) {  // (the union count of the vertex step is exact: the list's length is not read back)
+          GPU_LAUNCH(cs.stream(), k_bfs_collect, grid_for(nn, 256), 256, (const uint32_t *)d_st, nn, level, cur, d_cnt);
+          GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), cs.stream()));
+        }
+        GPU_LAUNCH(cs.stream(), k_ms_level, cs.list_grid(nfront), 256, tab, P, nn, (const uint32_t *)cur, nfront, d_front,
+                   (const unsigned long long *)d_seen, d_next, nxt, d_cnt);
+        GPU_LAUNCH(cs.stream(), k_ms_vertices, grid_for(nn, 256, 512), 256, nn, (const uint32_t *)nxt, (const uint32_t *)d_cnt, level, nbits, d_seen,
+                   d_front, d_next, d_st, d_lvg, d_stripes);
+        ctr[3]++;
+        ctr[6]++;
+      }
+      int e = cnt.read();
+      if (e != PPCSR_OK) return e;
+      ctr[7]++;
+      if (listed && cnt.lead(1)) {  // hubs were skipped, and with them the vertex step: one pass finishes the level
+        GCHK(cnt.zero());
+        full(level);
+        ctr[4]++;
+        e = cnt.read();
+        if (e != PPCSR_OK) return e;
+        ctr[7]++;
+        listed = false;
+        have_list = false;
+      }
+      if (listed) {
+        nfront = cnt.lead(0);
+        std::swap(cur, nxt);
+        have_list = true;
+      } else {
+        nfront = (uint32_t)cnt.sum(kMsUnion);
+      }
+      for (uint32_t b = 0; b < nbits; b++) {
+        const uint64_t c = cnt.sum(b);
+        if (c == 0) continue;
+        g_reached[b] += c;
+        g_far[b] += (uint64_t)(level + 1u) * c;
+        g_ecc[b] = level + 1u;
+        g_harm[b] += (double)c / (double)(level + 1u);
+      }
+    }
+    cs.stop();
+    if (d_lvg) GCHK(gpu::d2h(levels + g0 * nn, d_lvg, (uint64_t)nbits * nn * sizeof(uint32_t), cs.stream()));
+    const int done = cs.done(nullptr);
+    if (done != PPCSR_OK) return done;
+    ms += p_->timer.ms();
+    for (uint32_t b = 0; b < nbits; b++) {
+      if (reached) reached[g0 + b] = g_reached[b];
+      if (far) far[g0 + b] = g_far[b];
+      if (ecc) ecc[g0 + b] = g_ecc[b];
+      if (harmonic) harmonic[g0 + b] = g_harm[b];
+    }
+  }
+  if (device_ms) *device_ms = ms;
+  for (int i = 0; i < 8; i++) p_->msbfs_ctr[i] = ctr[i];
+  return PPCSR_OK;
+}
+int Engine::multi_bfs_counters(uint64_t out[8]) {
+  if (!out) return fail(PPCSR_EINVAL, "multi_bfs counters: no output");
+  for (int i = 0; i < 8; i++) out[i] = p_->msbfs_ctr[i];
+  return PPCSR_OK;
 }
 
 int Engine::debug_mulhi(const uint64_t *a, const uint64_t *b, uint64_t k, uint64_t *out) {

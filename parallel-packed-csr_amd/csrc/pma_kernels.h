@@ -14,6 +14,7 @@
 //   pma_isect_probe.h  debugging probe of the intersection routines (ppcsr_debug_isect_probe)
 //   pma_query.h        batched reads: edge lookups with values, neighbourhood gathers
 //   pma_sample.h       neighbour sampling, random walks, live degrees: rank / weight select over gapped ranges, hub prefix per call
+//   pma_msbfs.h        multi-source BFS: 64 sources per 64-bit word and vertex, edge step as a pass or per listed vertex, vertex step
 //   pma_exchange.h     owner bucketing for the multi-GPU exchange
 #pragma once
 #include "pma_rounds.h"
@@ -31,4 +32,5 @@
 #include "pma_isect_probe.h"
 #include "pma_query.h"
 #include "pma_sample.h"
+#include "pma_msbfs.h"
 #include "pma_exchange.h"

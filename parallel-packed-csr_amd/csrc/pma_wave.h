@@ -120,5 +120,11 @@ inline unsigned long long mulhi64(unsigned long long a, unsigned long long b) { 
 #else
 PMA_DEV unsigned long long mulhi64(unsigned long long a, unsigned long long b) { return __umul64hi(a, b); }
 #endif
+// device-wide OR into a 64-bit word, the old value back (the source bit sets of pma_msbfs.h)
+#if defined(PPCSR_SIM)
+inline unsigned long long atomic_or_u64(unsigned long long *p, unsigned long long v) { unsigned long long o = *p; *p = o | v; return o; }
+#else
+PMA_DEV unsigned long long atomic_or_u64(unsigned long long *p, unsigned long long v) { return atomicOr(p, v); }
+#endif
 }  // namespace wv
 }  // namespace ppcsr
