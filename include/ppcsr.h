@@ -239,6 +239,42 @@ int ppcsr_msf(ppcsr_t h, ppcsr_edge *edges, uint64_t cap, uint64_t *count, uint6
  *   out[7] host reads (stream synchronisations inside the timed region)
  * EINVAL: null handle or out. */
 int ppcsr_debug_msf_counters(ppcsr_t h, uint64_t out[8]);
+/* Edge support and truss numbers (the k-truss decomposition), in the undirected graph G that ppcsr_triangles counts in and
+ * ppcsr_kcore peels: live non-sentinel slots only, slot N - 1 excluded, local src < n, dest < n; {a, b}, a < b < n, is an edge
+ * exactly when the pair (a, b) is stored; self-loops and stored pairs with src > dst play no part.  A pair is stored at most
+ * once, so G is simple.
+ *   support(e), e = {a, b}: the number of vertices c with {a, c} and {b, c} in G.  The supports sum to 3 x the total of
+ *     ppcsr_triangles, and those of the edges at v to 2 x tri[v].
+ *   truss(e): the largest k such that e lies in a subgraph of G whose every edge is in at least k - 2 triangles inside that
+ *     subgraph (the convention of networkx k_truss and of cuGraph): an edge in no triangle has truss 2, every edge of a clique
+ *     on m vertices has truss m.
+ * edges — every edge of G as (src = a, dest = b, value = support or truss number), ascending by (a, b); at most cap are written
+ *   and ERANGE is returned when edges != NULL and cap < *count (as ppcsr_msf), the other outputs still delivered (may be NULL).
+ * *count = |E(G)| (may be NULL; a call that asks for nothing else is a cheap size query).  *total = the number of triangles (may
+ * be NULL).  *tmax = the largest truss number, 0 when G has no edge (may be NULL).  vtruss[v], n entries: the largest truss number
+ * of an edge at v, 0 for a vertex without an edge in G (may be NULL); vtruss[v] <= core[v] + 1 and tmax <= kmax + 1 against
+ * ppcsr_kcore.  Not all outputs may be NULL.  Everything returned is unique.
+ * Same contract as every consumer: synchronous on the engine's stream, sees every batch applied before it, writes nothing to
+ * the graph (state, stats, dirty tags and snapshot unchanged), device_ms may be NULL, every refusal is made before the first
+ * launch.  EINVAL: null handle, all outputs NULL.  ENOMEM: a device allocation of the call failed (nothing written).
+ * EUNSUPPORTED, with the reason in ppcsr_last_error: the sequential regime (stats.narrow == 0) — sorted ranges are searched, as
+ * ppcsr_triangles refuses it; a table of 2^32 slots or more (slots rounded up to 64 per array) — an edge is named by a 32-bit
+ * slot id.  Extra device memory: three words per slot, five per vertex, five per edge of G. */
+int ppcsr_edge_support(ppcsr_t h, ppcsr_edge *edges, uint64_t cap, uint64_t *count, uint64_t *total, double *device_ms);
+int ppcsr_ktruss(ppcsr_t h, ppcsr_edge *edges, uint64_t cap, uint64_t *count, uint32_t *tmax, uint32_t *vtruss, double *device_ms);
+/* Debugging: what the last edge_support / ktruss call on this engine did — for a pppcsr_* call the engine that ran it, the first
+ * partition's (pppcsr_partition).  Kept on the host from the reads the loop makes anyway and always on; all zeros before the
+ * first call.  The peel is synchronous in sub-rounds, so out[2] .. out[5] are functions of the graph (0 after edge_support).
+ *   out[0] |E(G)|
+ *   out[1] triangles (0 after a size query)
+ *   out[2] levels run: distinct truss numbers
+ *   out[3] sub-rounds, all levels together
+ *   out[4] most sub-rounds in one level
+ *   out[5] widest frontier (edges)
+ *   out[6] frontier edges handed to the long-range kernel (a walked side beyond 1024 positions)
+ *   out[7] host reads (stream synchronisations inside the timed region)
+ * EINVAL: null handle or out. */
+int ppcsr_debug_ktruss_counters(ppcsr_t h, uint64_t out[8]);
 /* Two consumers that intersect two neighbourhoods, over the same edge set (live slots of every vertex's (beginning, end), slot
  * N - 1 excluded, destinations >= n skipped; a (src, dst) pair is stored at most once).  A vertex's live slots lie in
  * ascending destination order, so the neighbourhoods are intersected in place: no export, no sort.
@@ -409,6 +445,7 @@ int ppcsr_debug_chain_probe(ppcsr_t h, const ppcsr_chain_probe_io *io);
  *   3 lower_bound  the 64-sample search of [blo, bhi) for key, one wave per case                       first slot of [blo, bhi] behind which no
  *                                                                                                      live slot holds a dest < key
  *   4 probe        one lane's gap-aware binary search of [blo, bhi) for key, one case per lane         1: a live slot holds key, else 0
+ *                  (reserved == 1: the slot is handed back, as edge_support / ktruss use the search)   reserved == 1: that slot, 0xFFFFFFFF: none
  * A slot is live when its value is not 0; the live dests of every range must ascend (the caller's duty: nothing checks it here).
  * tri: optional, modes 0-2: tri_n 64-bit words, zeroed by the call, tri[c] += 1 for every c counted by any case.
  * EINVAL: a range that leaves its buffer, lo > hi, a case with n > tri_n while tri is asked for, tri with tri_n == 0, more than
@@ -500,6 +537,12 @@ int pppcsr_scc(pppcsr_t h, uint32_t *labels, uint64_t *count, double *device_ms)
  * pppcsr_components; a partition in the sequential regime is answered.  EINVAL: null handle, all four outputs NULL, or a
  * partition not resident in this process.  EUNSUPPORTED: the partitions sit on more than one device. */
 int pppcsr_msf(pppcsr_t h, ppcsr_edge *edges, uint64_t cap, uint64_t *count, uint64_t *weight, uint32_t *labels, double *device_ms);
+/* ppcsr_edge_support / ppcsr_ktruss over the GLOBAL vertex ids (edges' src / dest; vtruss: pppcsr_get_n entries), one device call
+ * over every partition's array: a triangle may span partitions, and NO output depends on the partitioning.  Same contract as
+ * pppcsr_triangles.  EINVAL: null handle, all outputs NULL, or a partition not resident in this process.  EUNSUPPORTED: a
+ * partition in the sequential regime, 2^32 slots or more in all, or partitions on more than one device. */
+int pppcsr_edge_support(pppcsr_t h, ppcsr_edge *edges, uint64_t cap, uint64_t *count, uint64_t *total, double *device_ms);
+int pppcsr_ktruss(pppcsr_t h, ppcsr_edge *edges, uint64_t cap, uint64_t *count, uint32_t *tmax, uint32_t *vtruss, double *device_ms);
 /* ppcsr_path_counts / ppcsr_betweenness over the GLOBAL vertex ids (start, sources; levels, sigma, bc: pppcsr_get_n entries),
  * one device call over every partition's array: path_counts does not depend on the partitioning, betweenness only within its
  * error bound (the order of the sums differs).  Same contract as pppcsr_sssp; a partition in the sequential regime is

@@ -76,6 +76,7 @@ EXPORTED = [
     "ppcsr_path_counts", "ppcsr_betweenness", "pppcsr_path_counts", "pppcsr_betweenness",
     "ppcsr_scc", "pppcsr_scc", "ppcsr_debug_scc_counters",
     "ppcsr_msf", "pppcsr_msf", "ppcsr_debug_msf_counters",
+    "ppcsr_edge_support", "pppcsr_edge_support", "ppcsr_ktruss", "pppcsr_ktruss", "ppcsr_debug_ktruss_counters",
     "ppcsr_triangles", "pppcsr_triangles", "ppcsr_common_neighbours", "ppcsr_common_neighbours_device", "pppcsr_common_neighbours",
     "ppcsr_sample_neighbours", "ppcsr_sample_neighbours_device", "pppcsr_sample_neighbours",
     "ppcsr_random_walks", "ppcsr_random_walks_device", "pppcsr_random_walks", "ppcsr_degrees", "pppcsr_degrees", "ppcsr_debug_mulhi",
@@ -161,6 +162,11 @@ def load_library(path=None):
     for name in ("ppcsr_msf", "pppcsr_msf"):
         getattr(L, name).argtypes = [c_vp, c_vp, c_u64, ctypes.POINTER(c_u64), ctypes.POINTER(c_u64), c_vp, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_debug_msf_counters.argtypes = [c_vp, c_vp]
+    for name in ("ppcsr_edge_support", "pppcsr_edge_support"):
+        getattr(L, name).argtypes = [c_vp, c_vp, c_u64, ctypes.POINTER(c_u64), ctypes.POINTER(c_u64), ctypes.POINTER(ctypes.c_double)]
+    for name in ("ppcsr_ktruss", "pppcsr_ktruss"):
+        getattr(L, name).argtypes = [c_vp, c_vp, c_u64, ctypes.POINTER(c_u64), ctypes.POINTER(c_u32), c_vp, ctypes.POINTER(ctypes.c_double)]
+    L.ppcsr_debug_ktruss_counters.argtypes = [c_vp, c_vp]
     for name in ("ppcsr_triangles", "pppcsr_triangles"):
         getattr(L, name).argtypes = [c_vp, c_vp, ctypes.POINTER(c_u64), ctypes.POINTER(ctypes.c_double)]
     for name in ("ppcsr_common_neighbours", "ppcsr_common_neighbours_device", "pppcsr_common_neighbours"):
@@ -351,6 +357,29 @@ class _Consumers:
         ms = self._consumer("msf", edges.ctypes.data, len(edges), ctypes.byref(count), ctypes.byref(weight), labels.ctypes.data)
         edges = edges[: count.value]
         return (edges, weight.value, labels, ms) if with_ms else (edges, weight.value, labels)
+
+    def _edge_list(self, name, *outputs):
+        """the size query (edges = NULL), then the call into an array of that size: (edges[count, 3], ms)"""
+        count = c_u64()
+        self._consumer(name, None, 0, ctypes.byref(count), *[None] * len(outputs))
+        edges = np.empty((count.value, 3), np.uint32)
+        ms = self._consumer(name, edges.ctypes.data if count.value else None, count.value, ctypes.byref(count), *outputs)
+        return edges[: count.value], ms
+
+    def edge_support(self, with_ms=False):
+        """(edges, total[, ms]): edges[count, 3] uint32 rows (a, b, support) of every edge {a, b}, a < b, of the upper-orientation
+        graph triangles() counts in, ascending by (a, b) — support = the triangles through the edge — and the number of triangles"""
+        total = c_u64()
+        edges, ms = self._edge_list("edge_support", ctypes.byref(total))
+        return (edges, total.value, ms) if with_ms else (edges, total.value)
+
+    def ktruss(self, with_ms=False):
+        """(edges, tmax, vtruss[, ms]): edges[count, 3] uint32 rows (a, b, truss number) in the order of edge_support(), the largest
+        truss number (0 without an edge) and, per vertex, the largest truss number of an edge at it (uint32, 0 without one)"""
+        vtruss = np.empty(self.get_n(), np.uint32)
+        tmax = c_u32()
+        edges, ms = self._edge_list("ktruss", ctypes.byref(tmax), vtruss.ctypes.data)
+        return (edges, tmax.value, vtruss, ms) if with_ms else (edges, tmax.value, vtruss)
 
     def common_neighbours(self, a, b, with_ms=False):
         """counts[i] = stored destinations < n that a[i] and b[i] share (uint32; vertices >= n give 0)"""
@@ -610,6 +639,14 @@ class PCSR(_Consumers):
         self._chk(self.L.ppcsr_debug_msf_counters(self.h, out.ctypes.data))
         return out
 
+    def debug_ktruss_counters(self):
+        """Debugging (ppcsr_debug_ktruss_counters): uint64[8] of the last edge_support / ktruss call on this engine — edges,
+        triangles, levels run, sub-rounds, the most of them in one level, the widest frontier, frontier edges handed to the
+        long-range kernel, host reads"""
+        out = np.zeros(8, np.uint64)
+        self._chk(self.L.ppcsr_debug_ktruss_counters(self.h, out.ctypes.data))
+        return out
+
     def check_invariants(self):
         bad = c_u64()
         self._chk(self.L.ppcsr_check_invariants(self.h, ctypes.byref(bad)))
@@ -696,12 +733,13 @@ class PCSR(_Consumers):
             res["samples"] = [spos[int(soff[c]):int(soff[c + 1])] for c in range(n)]
         return res
 
-    def debug_isect_probe(self, mode, cases, items_a, items_b=None, tri_n=None):
+    def debug_isect_probe(self, mode, cases, items_a, items_b=None, tri_n=None, slot=False):
         """Debugging: the intersection routines of triangles / common_neighbours run alone on the device (ppcsr_debug_isect_probe);
         engine state untouched.  mode "lane" / "wave" / "block": count of {from <= c < n} in both ranges; "lower_bound": the slot;
         "probe": 0 or 1.  cases = (alo, ahi, blo, bhi, from_or_key, n) rows over items_a / items_b ((slots, 3) uint32 arrays of
         (src, dest, value), value 0 = a null; items_b None: both ranges in items_a).  The live dests of every range must ascend:
-        asserted here.  tri_n: also return the uint64[tri_n] credits of all cases (intersecting modes) -> (out, tri)."""
+        asserted here.  tri_n: also return the uint64[tri_n] credits of all cases (intersecting modes) -> (out, tri).  slot
+        ("probe" only): the slot that holds the key comes back, 0xFFFFFFFF where none does — the form edge_support / ktruss use."""
         m = ISECT_PROBE_MODES[mode]
         cs = np.ascontiguousarray(np.asarray(cases, np.uint32).reshape(-1, 6))
         ia = np.ascontiguousarray(items_a, np.uint32).reshape(-1, 3)
@@ -716,7 +754,7 @@ class PCSR(_Consumers):
                     assert not np.any((lo <= pq) & (q < hi)), f"live dests of a range descend at slot {q}"
         out = np.zeros(len(cs), np.uint32)
         tri = np.zeros(max(tri_n, 1), np.uint64) if tri_n is not None else None  # (tri_n == 0: the library refuses it)
-        io = IsectProbeIO(mode=m, ncases=len(cs), cases=cs.ctypes.data, items_a=ia.ctypes.data, len_a=len(ia),
+        io = IsectProbeIO(mode=m, reserved=1 if slot and mode == "probe" else 0, ncases=len(cs), cases=cs.ctypes.data, items_a=ia.ctypes.data, len_a=len(ia),
                           items_b=None if items_b is None else ib.ctypes.data, len_b=0 if items_b is None else len(ib),
                           out=out.ctypes.data, tri=None if tri is None else tri.ctypes.data, tri_n=tri_n or 0)
         self._chk(self.L.ppcsr_debug_isect_probe(self.h, ctypes.byref(io)))
@@ -795,6 +833,10 @@ class PPPCSR(_Consumers):
     def debug_msf_counters(self):
         """the counters of the last msf call: kept by the engine that ran it, the first partition's"""
         return self.partition(0).debug_msf_counters()
+
+    def debug_ktruss_counters(self):
+        """the counters of the last edge_support / ktruss call: kept by the engine that ran it, the first partition's"""
+        return self.partition(0).debug_ktruss_counters()
 
     def add_edge(self, s, d, v=1): self._chk(self.L.pppcsr_add_edge(self.h, s, d, v))
     def remove_edge(self, s, d): self._chk(self.L.pppcsr_remove_edge(self.h, s, d))

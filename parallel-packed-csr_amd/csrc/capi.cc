@@ -226,6 +226,19 @@ int ppcsr_msf(ppcsr_t h, ppcsr_edge *edges, uint64_t cap, uint64_t *count, uint6
   return ret(h->e, h->e->msf_over(&self, 1, h->e->n(), reinterpret_cast<ppcsr::Edge *>(edges), cap, count, weight, labels, device_ms));
 }
 int ppcsr_debug_msf_counters(ppcsr_t h, uint64_t out[8]) { H_CHECK(); return ret(h->e, h->e->msf_counters(out)); }
+int ppcsr_edge_support(ppcsr_t h, ppcsr_edge *edges, uint64_t cap, uint64_t *count, uint64_t *total, double *device_ms) {
+  H_CHECK();
+  if (!edges && !count && !total) return bad("edge_support: null outputs");
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->edge_support_over(&self, 1, h->e->n(), reinterpret_cast<ppcsr::Edge *>(edges), cap, count, total, device_ms));
+}
+int ppcsr_ktruss(ppcsr_t h, ppcsr_edge *edges, uint64_t cap, uint64_t *count, uint32_t *tmax, uint32_t *vtruss, double *device_ms) {
+  H_CHECK();
+  if (!edges && !count && !tmax && !vtruss) return bad("ktruss: null outputs");
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->ktruss_over(&self, 1, h->e->n(), reinterpret_cast<ppcsr::Edge *>(edges), cap, count, tmax, vtruss, device_ms));
+}
+int ppcsr_debug_ktruss_counters(ppcsr_t h, uint64_t out[8]) { H_CHECK(); return ret(h->e, h->e->ktruss_counters(out)); }
 int ppcsr_triangles(ppcsr_t h, uint64_t *tri, uint64_t *total, double *device_ms) {
   H_CHECK();
   if (!tri && !total) return bad("triangles: null outputs");
@@ -849,6 +862,20 @@ int pppcsr_msf(pppcsr_t h, ppcsr_edge *edges, uint64_t cap, uint64_t *count, uin
   if (!edges && !count && !weight && !labels) return bad("msf: null outputs");
   return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) {
     return ret(e, e->msf_over(r, P, n, reinterpret_cast<ppcsr::Edge *>(edges), cap, count, weight, labels, device_ms));
+  });
+}
+int pppcsr_edge_support(pppcsr_t h, ppcsr_edge *edges, uint64_t cap, uint64_t *count, uint64_t *total, double *device_ms) {
+  PP_CHECK();
+  if (!edges && !count && !total) return bad("edge_support: null outputs");
+  return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) {
+    return ret(e, e->edge_support_over(r, P, n, reinterpret_cast<ppcsr::Edge *>(edges), cap, count, total, device_ms));
+  });
+}
+int pppcsr_ktruss(pppcsr_t h, ppcsr_edge *edges, uint64_t cap, uint64_t *count, uint32_t *tmax, uint32_t *vtruss, double *device_ms) {
+  PP_CHECK();
+  if (!edges && !count && !tmax && !vtruss) return bad("ktruss: null outputs");
+  return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) {
+    return ret(e, e->ktruss_over(r, P, n, reinterpret_cast<ppcsr::Edge *>(edges), cap, count, tmax, vtruss, device_ms));
   });
 }
 int pppcsr_triangles(pppcsr_t h, uint64_t *tri, uint64_t *total, double *device_ms) {

@@ -98,6 +98,7 @@ struct Engine::Impl {
   // what the last scc_over on this engine did (ppcsr_debug_scc_counters): kept on the host from the reads the call makes anyway
   uint64_t scc_ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t msf_ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the same for msf_over (ppcsr_debug_msf_counters)
+  uint64_t ktruss_ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the same for edge_support_over / ktruss_over (ppcsr_debug_ktruss_counters)
   uint64_t msbfs_ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the same for multi_bfs_over (ppcsr_debug_multi_bfs_counters)
   uint32_t msbfs_look = 1;  // multi_bfs_over's pass looks at next[w] before it issues an OR (0: the variant tools/multibfs_bench.py measures)
   // dirty tags: writers stamp View::ldirty / vdirty with `serial`; every snapshot synchronisation advances it
@@ -2757,7 +2758,7 @@ int Engine::isect_probe(const IsectProbeIO *io) {
   else if (io->mode == 1) GPU_LAUNCH(p.stream, k_probe_isect_wave, per_wave, kIsectProbeThreads, ia, ib, dcs, nc, d_out, d_tri);
   else if (io->mode == 2) GPU_LAUNCH(p.stream, k_probe_isect_block, (uint32_t)nc, kIsectProbeThreads, ia, ib, dcs, d_out, d_tri);
   else if (io->mode == 3) GPU_LAUNCH(p.stream, k_probe_isect_lower_bound, per_wave, kIsectProbeThreads, ib, dcs, nc, d_out);
-  else GPU_LAUNCH(p.stream, k_probe_isect_probe, per_lane, kIsectProbeThreads, ib, dcs, nc, d_out);
+  else GPU_LAUNCH(p.stream, k_probe_isect_probe, per_lane, kIsectProbeThreads, ib, dcs, nc, d_out, io->reserved == 1u ? 1u : 0u);
   GCHK(gpu::d2h(io->out, d_out, nc * sizeof(uint32_t), p.stream));
   if (want_tri) GCHK(gpu::d2h(io->tri, d_tri, io->tri_n * sizeof(unsigned long long), p.stream));
   GCHK(gpu::sync(p.stream));

@@ -119,6 +119,16 @@ class Engine {
   int msf_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, Edge *edges, uint64_t cap, uint64_t *count, uint64_t *weight,
                uint32_t *labels, double *device_ms);
   int msf_counters(uint64_t out[8]);
+  // edge support and truss numbers of the upper-orientation graph triangles counts in (pma_truss.h; the definitions:
+  // include/ppcsr.h), regular regime only.  edges (at most cap, ascending (src, dest) = slot order, value = support / truss
+  // number), *count = |E(G)|, *total = triangles, *tmax = the largest truss number, vtruss (total_n entries): the largest at every
+  // vertex; each may be null.  PPCSR_ERANGE when edges != null and cap < *count, everything else delivered.  ktruss_counters:
+  // what the last of the two calls on this engine did (ppcsr_debug_ktruss_counters)
+  int edge_support_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, Edge *edges, uint64_t cap, uint64_t *count, uint64_t *total,
+                        double *device_ms);
+  int ktruss_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, Edge *edges, uint64_t cap, uint64_t *count, uint32_t *tmax,
+                  uint32_t *vtruss, double *device_ms);
+  int ktruss_counters(uint64_t out[8]);
   // shortest-path counts and betweenness centrality (pma_centrality.h), in either regime.  path_counts: levels as bfs_over
   // gives them and sigma[v] = number of fewest-edge paths from `start` to v, in fp64 (total_n entries each; either may be
   // null, not both).  betweenness: bc[v] (total_n entries) = Brandes' dependency of the k sources on v, endpoints
@@ -203,7 +213,10 @@ class Engine {
   // tile sums (edge total in part's d_total), then the writing pass
   int scan_count(Engine *part, uint32_t *tile, uint64_t *ntiles);
   int intersect_regime(const ConsumerRef *parts, uint32_t P, const char *what, std::string *msg);
-  int consumer_table(const ConsumerRef *parts, uint32_t P, uint32_t total_n, void **d_tab, uint64_t *slots);
+  int consumer_table(const ConsumerRef *parts, uint32_t P, uint32_t total_n, void **d_tab, uint64_t *slots, int alloc_code);
+  // what edge_support_over and ktruss_over share: stage 1, the support phase and, for ktruss, the peel
+  int truss_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, bool peel, Edge *edges, uint64_t cap, uint64_t *count, uint64_t *total,
+                 uint32_t *tmax, uint32_t *vtruss, double *device_ms);
   // what path_counts_over and betweenness_over share: the forward phase from every source and, when bc is wanted, the backward sweep
   int centrality_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const uint32_t *sources, uint64_t k, uint32_t *levels,
                       double *sigma, double *bc, double *device_ms);

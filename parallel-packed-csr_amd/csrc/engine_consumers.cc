@@ -1,12 +1,13 @@
 // Host drivers of the graph-algorithm consumers (kernels: pma_consumer.h, pma_scan.h, pma_paths.h, pma_cores.h, pma_centrality.h,
-// pma_scc.h, pma_msf.h, pma_intersect.h, pma_sample.h, pma_msbfs.h).  Included at the end of engine.cc: part of the engine's single translation unit, in the library
+// pma_scc.h, pma_msf.h, pma_intersect.h, pma_truss.h, pma_sample.h, pma_msbfs.h).  Included at the end of engine.cc: part of the engine's single translation unit, in the library
 // (csrc/ppcsr_hip.hip) and in the emulator (tests/hostsim/ppcsr_sim.cpp) alike.
 namespace ppcsr {
 
 // The consumers run over a table of gapped arrays (pma_consumer.h: ConsumerPart) — a PPPCSR's partitions, or one engine alone —
 // on this engine's stream.  The partitions' own streams must be idle first: their last batch may still be in flight.
-// *slots = slots of all arrays; the table goes to the device (one copy, into *d_tab) unless d_tab is null.
-int Engine::consumer_table(const ConsumerRef *parts, uint32_t P, uint32_t total_n, void **d_tab, uint64_t *slots) {
+// *slots = slots of all arrays; the table goes to the device (one copy, into *d_tab) unless d_tab is null.  alloc_code: the status
+// of a table that cannot be allocated (ConsumerScope::alloc_code).
+int Engine::consumer_table(const ConsumerRef *parts, uint32_t P, uint32_t total_n, void **d_tab, uint64_t *slots, int alloc_code) {
   Impl &p = *p_;
   std::vector<ConsumerPart> tab(P + 1);
   uint64_t chunks = 0, tot = 0;
@@ -20,7 +21,8 @@ int Engine::consumer_table(const ConsumerRef *parts, uint32_t P, uint32_t total_
   tab[P] = ConsumerPart{nullptr, nullptr, 0, chunks, 0, total_n, {0, 0}};
   *slots = tot;
   if (!d_tab) return PPCSR_OK;
-  GCHK(gpu::dmalloc(d_tab, (P + 1) * sizeof(ConsumerPart)));
+  const int oom = gpu::dmalloc(d_tab, (P + 1) * sizeof(ConsumerPart));
+  if (oom != 0) return fail(alloc_code, std::string("device allocation of the consumer table: ") + gpu::err_str(oom));
   GCHK(gpu::h2d(*d_tab, tab.data(), (P + 1) * sizeof(ConsumerPart), p.stream));
   GCHK(gpu::sync(p.stream));
   return PPCSR_OK;
@@ -51,8 +53,9 @@ struct Engine::ConsumerScope {
   uint64_t slots_ = 0;
   uint32_t n_ = 0;
   int rc = PPCSR_OK;  // the first allocation that failed (later ones are not tried)
+  const int alloc_code;  // its status: PPCSR_EHIP from the earlier consumers, PPCSR_ENOMEM from edge_support / ktruss
 
-  explicit ConsumerScope(Engine *e) : eng(*e), p(*e->p_) {}
+  explicit ConsumerScope(Engine *e, int alloc_status = PPCSR_EHIP) : eng(*e), p(*e->p_), alloc_code(alloc_status) {}
   ConsumerScope(const ConsumerScope &) = delete;  // (it owns the buffers; a launch's arguments are copies of plain pointers)
   ~ConsumerScope() {
     for (void *b : bufs) gpu::dfree(b);
@@ -65,7 +68,7 @@ struct Engine::ConsumerScope {
     if (intersects && eng.intersect_regime(parts, P, intersects, &msg) != PPCSR_OK) return fail(PPCSR_EUNSUPPORTED, msg);
     n_ = total_n;
     void *d_tab = nullptr;
-    const int e = eng.consumer_table(parts, P, total_n, device_table ? &d_tab : nullptr, &slots_);
+    const int e = eng.consumer_table(parts, P, total_n, device_table ? &d_tab : nullptr, &slots_, alloc_code);
     if (d_tab) bufs.push_back(d_tab);
     tab_ = static_cast<const ConsumerPart *>(d_tab);
     return e;
@@ -85,7 +88,7 @@ struct Engine::ConsumerScope {
     if (rc != PPCSR_OK) return nullptr;
     const int e = gpu::dmalloc(&b, count * sizeof(T));
     if (e != 0) {
-      rc = fail(PPCSR_EHIP, std::string("device allocation of ") + what + ": " + gpu::err_str(e));
+      rc = fail(alloc_code, std::string("device allocation of ") + what + ": " + gpu::err_str(e));
       return nullptr;
     }
     bufs.push_back(b);
@@ -741,6 +744,163 @@ int Engine::msf_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, Edg
 int Engine::msf_counters(uint64_t out[8]) {
   if (!out) return fail(PPCSR_EINVAL, "msf counters: no output");
   for (int i = 0; i < 8; i++) out[i] = p_->msf_ctr[i];
+  return PPCSR_OK;
+}
+
+// Edge support and truss numbers (pma_truss.h).  Stage 1: one streaming pass marks the edges of G by slot and counts
+// in-degrees and edges per chunk, two scans give the offsets of the in-lists and of the output, one host read the number of
+// edges (the lists are allocated then), a second pass fills the in-lists.  The support phase is one launch and, if it deferred
+// edges, a second one finds them.  The peel (ktruss only) costs one host read of the small counter block per level (the threshold
+// and the first frontier) and per sub-round (the next frontier, the deferred edges), as kcore_over.  device_ms covers the whole call,
+// allocations and round trips included.  A failed allocation is PPCSR_ENOMEM here.
+int Engine::truss_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, bool peel, Edge *edges, uint64_t cap, uint64_t *count, uint64_t *total,
+                       uint32_t *tmax, uint32_t *vtruss, double *device_ms) {
+  const uint32_t nn = total_n;
+  const char *const what = peel ? "ktruss" : "edge_support";
+  ConsumerScope cs(this, PPCSR_ENOMEM);
+  uint64_t slots = 0;
+  for (uint32_t k = 0; k < P; k++) slots += (parts[k].e->N() + 63) / 64 * 64;
+  if (slots >= (1ull << 32)) return fail(PPCSR_EUNSUPPORTED, std::string(what) + ": 2^32 slots or more (an edge is named by a 32-bit slot id)");
+  int rc = cs.open(parts, P, nn, what);
+  if (rc != PPCSR_OK) return rc;
+  const ConsumerPart *tab = cs.table();
+  const uint64_t words = cs.words(), swords = std::max<uint64_t>(slots, 1);
+  const uint32_t chunks = (uint32_t)(slots / 64);
+  const uint32_t vtiles = (uint32_t)(((uint64_t)nn + kKcTile - 1) / kKcTile), ctiles = (chunks + kKcTile - 1) / kKcTile;
+  uint32_t *d_stamp = cs.alloc<uint32_t>("d_stamp", swords), *d_sup = cs.alloc<uint32_t>("d_sup", swords);
+  uint32_t *d_tr = peel ? cs.alloc<uint32_t>("d_tr", swords) : nullptr;
+  uint32_t *d_indeg = cs.alloc<uint32_t>("d_indeg", words), *d_fill = cs.alloc<uint32_t>("d_fill", words);
+  uint32_t *d_ccnt = cs.alloc<uint32_t>("d_ccnt", std::max<uint32_t>(chunks, 1));
+  unsigned long long *d_inoff = cs.alloc<unsigned long long>("d_inoff", words + 1), *d_choff = cs.alloc<unsigned long long>("d_choff", (uint64_t)chunks + 1);
+  unsigned long long *d_tiles = cs.alloc<unsigned long long>("d_tiles", std::max<uint32_t>(std::max(vtiles, ctiles), 1));
+  uint32_t *d_vt = vtruss ? cs.alloc<uint32_t>("d_vt", words) : nullptr;
+  ConsumerScope::Striped<unsigned long long, kTrStripeWords> tot(cs, "d_tot");
+  uint32_t *d_cnt = cs.alloc<uint32_t>("d_cnt", kTrCntWords);
+  if (cs.rc != PPCSR_OK) return cs.rc;
+  uint64_t ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t &reads = ctr[7];
+  uint64_t m = 0;
+  uint32_t top = 0;
+  Edge *d_out = nullptr;
+  uint32_t h_cnt[4] = {0, 0, 0, 0};
+  const auto read_cnt = [&](uint32_t nwords) {
+    reads++;
+    return cs.read_back(h_cnt, d_cnt, nwords * sizeof(uint32_t));
+  };
+  cs.start();
+  if (nn && chunks) {
+    const uint32_t chunk_grid = grid_for(chunks, 4, 8192), slot_grid = grid_for(slots, 256, 4096);
+    const uint32_t long_grid = 2048;  // the long-range kernels: at most the 8192 waves the chip holds at once
+    // stage 1
+    GCHK(gpu::dset(d_indeg, 0, words * sizeof(uint32_t), cs.stream()));
+    GCHK(gpu::dset(d_fill, 0, words * sizeof(uint32_t), cs.stream()));
+    GCHK(gpu::dset(d_sup, 0, swords * sizeof(uint32_t), cs.stream()));
+    GCHK(gpu::dset(d_cnt, 0, kTrCntWords * sizeof(uint32_t), cs.stream()));
+    GCHK(tot.zero());
+    GPU_LAUNCH(cs.stream(), k_tr_init, cs.pass_grid(), 256, tab, P, nn, d_stamp, d_indeg, d_ccnt);
+    GPU_LAUNCH(cs.stream(), k_kc_tile_sums, grid_for(vtiles, 1, 65536), 256, (const uint32_t *)d_indeg, nn, vtiles, d_tiles);
+    GPU_LAUNCH(cs.stream(), k_kc_scan_tiles, 1, 64, d_tiles, vtiles, d_inoff + nn);
+    GPU_LAUNCH(cs.stream(), k_kc_scan_write, grid_for(vtiles, 1, 65536), 256, (const uint32_t *)d_indeg, nn, vtiles, (const unsigned long long *)d_tiles, d_inoff);
+    GPU_LAUNCH(cs.stream(), k_kc_tile_sums, grid_for(ctiles, 1, 65536), 256, (const uint32_t *)d_ccnt, chunks, ctiles, d_tiles);
+    GPU_LAUNCH(cs.stream(), k_kc_scan_tiles, 1, 64, d_tiles, ctiles, d_choff + chunks);
+    GPU_LAUNCH(cs.stream(), k_kc_scan_write, grid_for(ctiles, 1, 65536), 256, (const uint32_t *)d_ccnt, chunks, ctiles, (const unsigned long long *)d_tiles, d_choff);
+    unsigned long long entries = 0;
+    rc = cs.read_back(&entries, d_inoff + nn, sizeof(entries));
+    if (rc != PPCSR_OK) return rc;
+    reads++;
+    m = entries;
+    const uint64_t ewords = std::max<uint64_t>(m, 1);
+    uint32_t *d_inw = cs.alloc<uint32_t>("d_inw", ewords), *d_ins = cs.alloc<uint32_t>("d_ins", ewords);
+    uint32_t *d_long = cs.alloc<uint32_t>("d_long", ewords);
+    // (an edge enters one frontier once: no list exceeds |E|)
+    uint32_t *d_f0 = peel ? cs.alloc<uint32_t>("d_f0", ewords) : nullptr, *d_f1 = peel ? cs.alloc<uint32_t>("d_f1", ewords) : nullptr;
+    if (edges && cap && m) d_out = cs.alloc<Edge>("d_out", std::min<uint64_t>(cap, m));
+    if (cs.rc != PPCSR_OK) return cs.rc;
+    if (m && (edges || total || tmax || vtruss)) {  // (a call that only asks for *count ends here: the size query)
+      const unsigned long long *inoff = d_inoff;
+      const uint32_t *inw = d_inw, *ins = d_ins;
+      GPU_LAUNCH(cs.stream(), k_tr_fill, cs.pass_grid(), 256, tab, P, nn, inoff, d_fill, d_inw, d_ins);
+      // support
+      GPU_LAUNCH(cs.stream(), k_tr_support, chunk_grid, 256, tab, P, nn, inoff, inw, ins, (const uint32_t *)d_stamp, d_sup, d_long, d_cnt, tot.stripes());
+      // (the deferred edges, their number read on the device: no round trip, and a launch that finds none ends at once)
+      GPU_LAUNCH(cs.stream(), k_tr_support_long, long_grid, 256, tab, P, nn, inoff, inw, ins, (const uint32_t *)d_long, (const uint32_t *)d_cnt, d_sup,
+                 tot.stripes());
+      // peel
+      uint32_t *cur = d_f0, *nxt = d_f1;
+      uint32_t r = 1;  // the sub-round about to run
+      while (peel) {
+        GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), cs.stream()));
+        GCHK(gpu::dset(d_cnt + 2, 0xFF, sizeof(uint32_t), cs.stream()));
+        GPU_LAUNCH(cs.stream(), k_tr_min, grid_for(slots, 256, 1024), 256, (const uint32_t *)d_sup, (const uint32_t *)d_stamp, slots, d_cnt);
+        GPU_LAUNCH(cs.stream(), k_tr_collect, slot_grid, 256, (const uint32_t *)d_sup, d_stamp, d_tr, slots, r, cur, d_cnt);
+        rc = read_cnt(3);
+        if (rc != PPCSR_OK) return rc;
+        uint32_t nfront = h_cnt[0];
+        if (nfront == 0) break;  // (the threshold is kMax: every edge has its truss number)
+        const TrPeel level{h_cnt[2], 0, d_sup, d_stamp, d_tr, nullptr, d_cnt};
+        top = level.s + 2;
+        ctr[2]++;
+        uint64_t here = 0;
+        while (nfront > 0) {
+          TrPeel pl = level;
+          pl.r = r;
+          pl.next = nxt;
+          here++;
+          ctr[5] = std::max<uint64_t>(ctr[5], nfront);
+          GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), cs.stream()));
+          // (8192 waves are what the chip holds at once: a frontier below that gets teams of waves per edge, a wider one goes round)
+          const uint32_t team = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(8192 / nfront, 1), kTrTeamMax);
+          GPU_LAUNCH(cs.stream(), k_tr_peel, grid_for((uint64_t)nfront * team, 4, 2048), 256, tab, P, nn, inoff, inw, ins, (const uint32_t *)cur, nfront, team,
+                     pl, d_long);
+          // walks beyond kTrWaveSlots: a second launch splits them over waves and appends to the same frontier
+          // (at most nfront edges are deferred: 64 waves for each, up to the chip's)
+          GPU_LAUNCH(cs.stream(), k_tr_peel_long, grid_for((uint64_t)nfront * 64, 4, long_grid), 256, tab, P, nn, inoff, inw, ins, (const uint32_t *)d_long, pl);
+          rc = read_cnt(2);
+          if (rc != PPCSR_OK) return rc;
+          ctr[6] += h_cnt[1];
+          nfront = h_cnt[0];
+          std::swap(cur, nxt);
+          r++;
+        }
+        ctr[3] += here;
+        ctr[4] = std::max(ctr[4], here);
+      }
+      // output
+      if (d_vt) GCHK(gpu::dset(d_vt, 0, words * sizeof(uint32_t), cs.stream()));
+      if (d_out || d_vt)
+        GPU_LAUNCH(cs.stream(), k_tr_emit, chunk_grid, 256, tab, P, (const uint32_t *)d_stamp, (const uint32_t *)(peel ? d_tr : d_sup),
+                   (const unsigned long long *)d_choff, d_out, cap, d_vt);
+    }
+  }
+  cs.stop();
+  GCHK(gpu::d2h(tot.host.data(), tot.dev, sizeof(unsigned long long) * tot.kCount, cs.stream()));  // (waited for by done(), with the rest)
+  if (d_out) GCHK(gpu::d2h(edges, d_out, std::min<uint64_t>(cap, m) * sizeof(Edge), cs.stream()));
+  if (vtruss && nn) {
+    if (m) GCHK(gpu::d2h(vtruss, d_vt, (uint64_t)nn * sizeof(uint32_t), cs.stream()));  // (vtruss != null: the block above ran)
+    else memset(vtruss, 0, (uint64_t)nn * sizeof(uint32_t));
+  }
+  rc = cs.done(device_ms);
+  if (rc != PPCSR_OK) return rc;
+  const uint64_t triangles = (nn && chunks && m) ? tot.sum() / 3 : 0;
+  if (count) *count = m;
+  if (total) *total = triangles;
+  if (tmax) *tmax = top;
+  ctr[0] = m;
+  ctr[1] = triangles;
+  for (int i = 0; i < 8; i++) p_->ktruss_ctr[i] = ctr[i];
+  return (edges && cap < m) ? PPCSR_ERANGE : PPCSR_OK;
+}
+int Engine::edge_support_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, Edge *edges, uint64_t cap, uint64_t *count, uint64_t *total,
+                              double *device_ms) {
+  return truss_over(parts, P, total_n, false, edges, cap, count, total, nullptr, nullptr, device_ms);
+}
+int Engine::ktruss_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, Edge *edges, uint64_t cap, uint64_t *count, uint32_t *tmax,
+                        uint32_t *vtruss, double *device_ms) {
+  return truss_over(parts, P, total_n, true, edges, cap, count, nullptr, tmax, vtruss, device_ms);
+}
+int Engine::ktruss_counters(uint64_t out[8]) {
+  if (!out) return fail(PPCSR_EINVAL, "ktruss counters: no output");
+  for (int i = 0; i < 8; i++) out[i] = p_->ktruss_ctr[i];
   return PPCSR_OK;
 }
 

@@ -61,9 +61,9 @@ PMA_DEV uint32_t isect_lower_bound(const Edge *__restrict__ items, uint32_t lo, 
   return hi;
 }
 
-// does a live slot of [lo, hi) hold dest == key?  One lane's own search (every lane of a wave runs one, each for its key):
-// a binary search whose probe, landing on a null, walks right to the next live slot.
-PMA_DEV bool isect_probe(const Edge *__restrict__ items, uint32_t lo, uint32_t hi, uint32_t key) {
+// the live slot of [lo, hi) that holds dest == key, kMax when there is none.  One lane's own search (every lane of a wave runs
+// one, each for its key): a binary search whose probe, landing on a null, walks right to the next live slot.
+PMA_DEV uint32_t isect_probe_slot(const Edge *__restrict__ items, uint32_t lo, uint32_t hi, uint32_t key) {
   while (lo < hi) {
     const uint32_t mid = lo + ((hi - lo) >> 1);
     uint32_t p = mid, d = 0;
@@ -75,10 +75,14 @@ PMA_DEV bool isect_probe(const Edge *__restrict__ items, uint32_t lo, uint32_t h
         break;
       }
     if (!live || d > key) hi = mid;
-    else if (d == key) return true;
+    else if (d == key) return p;
     else lo = p + 1u;
   }
-  return false;
+  return kMax;
+}
+// does a live slot of [lo, hi) hold dest == key?
+PMA_DEV bool isect_probe(const Edge *__restrict__ items, uint32_t lo, uint32_t hi, uint32_t key) {
+  return isect_probe_slot(items, lo, hi, key) != kMax;
 }
 // the same over a staged tile: tile[i] = dest, or kIsectNone where the slot held nothing that counts
 PMA_DEV bool isect_probe_tile(const uint32_t *tile, uint32_t cnt, uint32_t key) {

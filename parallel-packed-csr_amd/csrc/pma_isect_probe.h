@@ -52,12 +52,14 @@ PMA_KERNEL void k_probe_isect_lower_bound(const Edge *__restrict__ ib, const Ise
   const uint32_t r = isect_lower_bound(ib, k.blo, k.bhi, k.fk);
   if (wv::lane() == 0) out[c] = r;
 }
-// one case per lane: every lane its own search, as in the lopsided form of isect_wave
-PMA_KERNEL void k_probe_isect_probe(const Edge *__restrict__ ib, const IsectCase *__restrict__ cs, uint64_t nc, uint32_t *out) {
+// one case per lane: every lane its own search, as in the lopsided form of isect_wave; slot: the slot itself is handed back
+// (kMax: none), as tr_find of pma_truss.h takes it
+PMA_KERNEL void k_probe_isect_probe(const Edge *__restrict__ ib, const IsectCase *__restrict__ cs, uint64_t nc, uint32_t *out, uint32_t slot) {
   const uint64_t c = (uint64_t)wv::block_idx() * wv::block_dim() + wv::thread_idx();
   if (c >= nc) return;
   const IsectCase k = cs[c];
-  out[c] = isect_probe(ib, k.blo, k.bhi, k.fk) ? 1u : 0u;
+  if (slot) out[c] = isect_probe_slot(ib, k.blo, k.bhi, k.fk);
+  else out[c] = isect_probe(ib, k.blo, k.bhi, k.fk) ? 1u : 0u;
 }
 
 }  // namespace ppcsr

@@ -11,6 +11,7 @@
 //   pma_scc.h          strongly connected components: trimming, forward-backward reach from a pivot, colouring
 //   pma_msf.h          minimum spanning forest over the edge values: Boruvka rounds of two streaming passes, hook, pointer doubling
 //   pma_intersect.h    triangle counts and common-neighbour counts: sorted intersection of two gapped vertex ranges
+//   pma_truss.h        edge support and truss numbers: per-edge state by slot, in-lists, slot-returning searches, peeling in sub-rounds
 //   pma_isect_probe.h  debugging probe of the intersection routines (ppcsr_debug_isect_probe)
 //   pma_query.h        batched reads: edge lookups with values, neighbourhood gathers
 //   pma_sample.h       neighbour sampling, random walks, live degrees: rank / weight select over gapped ranges, hub prefix per call
@@ -29,6 +30,7 @@
 #include "pma_scc.h"
 #include "pma_msf.h"
 #include "pma_intersect.h"
+#include "pma_truss.h"
 #include "pma_isect_probe.h"
 #include "pma_query.h"
 #include "pma_sample.h"
