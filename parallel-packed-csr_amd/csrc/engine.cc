@@ -105,6 +105,10 @@ struct Engine::Impl {
   uint32_t serial = 1;
   uint64_t array_gen = 1;
   bool stamps_clean = false;  // the validation stamps hold nothing from an earlier batch or a rolled-back epoch
+  // the live state equals `snap` and nothing has written since: set by snapshot() and restore(), cleared by every writer of the
+  // live arrays or their geometry (the writers of the dirty-tag convention).  While it holds, a speculative epoch
+  // takes `snap` for its rollback point and copies nothing (run_speculative)
+  bool live_is_snap = false;
   // speculative scheduler state
   OptCtl *d_octl = nullptr, *h_octl = nullptr;
   uint32_t *d_vdbg = nullptr;
@@ -715,6 +719,7 @@ int Engine::set_option(const char *key, int64_t value) {
     gpu::set_device(device_);
     Edge *sc = nullptr;
     GCHK(gpu::dmalloc((void **)&sc, wl * sizeof(Edge)));
+    p.live_is_snap = false;
     GPU_LAUNCH(p.stream, k_block_rebalance, 1, dev::kBigThreads, p.v, ws, wl, sc);
     GCHK(gpu::sync(p.stream));
     GCHK(gpu::last_error());
@@ -848,6 +853,7 @@ int Engine::apply_batch_device(const Op *d_ops, uint64_t n) {
 
 int Engine::run_rounds(const Op *d_ops, uint64_t n) {
   Impl &p = *p_;
+  p.live_is_snap = false;
   if (p.round > 0xFFFF0000u) GCHK(reset_tags(p));  // reservation tags would wrap
   GCHK(ensure_plans(p));
   uint64_t cur = 0;
@@ -939,6 +945,7 @@ int Engine::run_rounds(const Op *d_ops, uint64_t n) {
 
 static int snap_commit(Engine::Impl &p, Engine::Impl::Snap &sn);
 static int snap_rollback(Engine::Impl &p, Engine::Impl::Snap &sn, Engine::Impl::Snap &other);
+static bool snap_in_step(const Engine::Impl &p, const Engine::Impl::Snap &sn);
 
 // Speculative rounds (pma_kernels.h, second half): epochs of at most `epoch_ops` updates, each with a rollback
 // snapshot; a validation failure replays the epoch with the strict prefix rounds, an exclusive update ends the epoch.
@@ -1003,19 +1010,11 @@ int Engine::run_speculative(const Op *d_ops, uint64_t n) {
     if (p.round > 0xFFFF0000u) GCHK(reset_tags(p));
     // rollback point of the epoch: the epoch snapshot catches up with what the previous epoch wrote (dirty tags) — a full
     // copy only the first time and after the array was replaced
-    GCHK(snap_commit(p, p.esnap));
-    GCHK(gpu::d2d(p.d_stats_snap, p.d_stats, kStatShards * sizeof(StatShard), p.stream));
-    if (!p.stamps_clean) {
-      // validation stamps hold 1 + the stream index of the latest committed toucher: what earlier epochs of this batch left
-      // is smaller than anything this epoch compares with, so they are cleared at the start of a batch and after a
-      // rollback only (the rolled-back commits must not look like later updates to the retried ones)
-      const uint64_t leaves = p.v.g.N >> p.v.g.sh;
-      GCHK(gpu::dset(p.d_wstamp, 0, leaves * sizeof(uint32_t), p.stream));
-      GCHK(gpu::dset(p.d_rstamp, 0, leaves * sizeof(uint32_t), p.stream));
-      GCHK(gpu::dset(p.d_vws, 0, (p.n_cap + 1) * sizeof(uint32_t), p.stream));
-      GCHK(gpu::dset(p.d_vrs, 0, (p.n_cap + 1) * sizeof(uint32_t), p.stream));
-      p.stamps_clean = true;
-    }
+    // ... and none at all while the live state still equals the user's snapshot (restore() or snapshot() came last and nothing
+    // has written since): that snapshot IS the rollback point.  The epoch snapshot stays where it was; the next epoch that
+    // needs it catches up by the tags, with what the restore re-stamped among them
+    const bool from_snap = p.live_is_snap && snap_in_step(p, p.snap);
+    if (!from_snap) GCHK(snap_commit(p, p.esnap));
     OptCtl &c = *p.h_octl;
     memset(&c, 0, sizeof(c));
     // the epoch's first round is p.round + 1: the words it reads as "the previous round" describe an empty round that ended at e0
@@ -1031,13 +1030,37 @@ int Engine::run_speculative(const Op *d_ops, uint64_t n) {
       c.gbar[t] = c.sbar[t] = ~0ull;
     }
     c.e1 = (uint32_t)e1;
-    c.max_horizon = p.opt_horizon;
     c.width_cap = p.opt_horizon;
     c.resident = p.resident_waves;
     c.viol_idx = kMax;
     c.skip_idx = kMax;
     c.skip_round = 0;
-    GCHK(gpu::h2d(p.d_octl, p.h_octl, sizeof(OptCtl), p.stream));
+    // grid of a chunk: wide enough for the adapted width to grow during the chunk (x1.25 per full-width round), narrow at the
+    // tail, never narrower than the carry list (a round plans the whole of it) and never wider than opt_horizon
+    auto chunk_grid = [&p](uint32_t width, uint64_t pending, uint64_t carry) {
+      uint32_t gh = p.opt_horizon;
+      const uint64_t want = std::max<uint64_t>(1024, 4ull * (width ? width : p.opt_horizon));
+      if (want < gh) gh = (uint32_t)want;
+      const uint64_t pend = (pending + 255) & ~255ull;
+      if (pend < gh) gh = (uint32_t)std::max<uint64_t>(pend, 256);
+      const uint64_t need = (carry + 255) & ~255ull;
+      if (gh < need) gh = (uint32_t)std::min<uint64_t>(need, p.opt_horizon);
+      return gh;
+    };
+    c.max_horizon = chunk_grid(c.cur_h[pp0], e1 - e0, 0);  // (the first chunk's: the device never chooses a horizon wider than the launched grid)
+    {
+      // one launch opens the epoch (k_epoch_begin).  Validation stamps hold 1 + the stream index of the latest committed
+      // toucher: what earlier epochs of this batch left is smaller than anything this epoch compares with, so they are
+      // cleared at the start of a batch and after a rollback only (the rolled-back commits must not look like later updates
+      // to the retried ones)
+      const uint64_t leaves = p.v.g.N >> p.v.g.sh, nv = (uint64_t)p.n_cap + 1;
+      const uint32_t clear = p.stamps_clean ? 0u : 1u;
+      // (the loops are grid-stride: the grid only bounds the stride — one 16-byte store per thread and array up to 2048 workgroups)
+      const uint64_t quads = clear ? std::max(leaves, nv) / 4 + 1 : kStatShards * sizeof(StatShard) / 16;
+      GPU_LAUNCH(p.stream, k_epoch_begin, (uint32_t)std::min<uint64_t>((quads + 255) / 256, 2048), 256, p.d_wstamp, p.d_rstamp, leaves, p.d_vws, p.d_vrs, nv,
+                 clear, (const StatShard *)p.d_stats, p.d_stats_snap, p.d_octl, c);
+      p.stamps_clean = true;
+    }
     int rs = 0;
     if (p.region_eff < p.region_slots) p.region_eff = p.region_slots;
     while ((p.region_eff >> rs) > (uint32_t)p.v.g.logN) rs++;
@@ -1086,17 +1109,7 @@ int Engine::run_speculative(const Op *d_ops, uint64_t n) {
       if (!p.soft_barrier && p.region_rare_span && p.region_eff >= p.region_rare) a.soft_barrier = 0x40000000u;
       // grid sized for the horizon the device last reported (it can only shrink within a chunk when fresh
       // updates run out; it never exceeds opt_horizon)
-      // grid: wide enough for the adapted width to grow during the chunk (x1.25 per full-width round), narrow at the tail
-      uint32_t gh = p.opt_horizon;
-      {
-        const uint64_t want = std::max<uint64_t>(1024, 4ull * (cur_width ? cur_width : p.opt_horizon));
-        if (want < gh) gh = (uint32_t)want;
-        const uint64_t pend = (chunk_pending + 255) & ~255ull;
-        if (pend < gh) gh = (uint32_t)std::max<uint64_t>(pend, 256);
-        // (a round plans the whole carry list: the grid is never narrower than it)
-        const uint64_t need = (carry_now + 255) & ~255ull;
-        if (gh < need) gh = (uint32_t)std::min<uint64_t>(need, p.opt_horizon);
-      }
+      const uint32_t gh = chunk_grid(cur_width, chunk_pending, carry_now);
       const uint32_t blocks = (gh + 3) / 4;
       if (gh != c.max_horizon) {  // the device must never choose a horizon larger than the launched grid
         GCHK(gpu::h2d(&p.d_octl->max_horizon, &gh, sizeof(uint32_t), p.stream));
@@ -1119,6 +1132,7 @@ int Engine::run_speculative(const Op *d_ops, uint64_t n) {
         p.events.resize(5ull * rounds);
         for (size_t i = oldn; i < p.events.size(); i++) GCHK(p.events[i].init());
       }
+      p.live_is_snap = false;
       for (uint32_t r = 0; r < rounds; r++) {
         a.round = ++p.round;
         if (p.profile) p.events[5 * r + 0].record(p.stream);
@@ -1240,7 +1254,13 @@ int Engine::run_speculative(const Op *d_ops, uint64_t n) {
           fprintf(stderr, "[ppcsr] rollback: epoch [%llu,%llu) viol_idx=%u excl=%u later=%u after %llu rounds; kind=%u leaf=%u stamp=%u what=%u wleaf=[%u,%u] index=%u nr=%u\n",
                   (unsigned long long)e0, (unsigned long long)e1, c.viol_idx, c.excl, c.excl_later, c.rounds, c.viol_info[0],
                   c.viol_info[1], c.viol_info[2], c.viol_info[3], c.viol_info[4], c.viol_info[5], c.viol_info[6], c.viol_info[7]);
-        GCHK(snap_rollback(p, p.esnap, p.snap));
+        if (from_snap) {
+          // the epoch started from the user's snapshot: back to it, and the retried epoch starts from it again
+          GCHK(snap_rollback(p, p.snap, p.esnap));
+          p.live_is_snap = true;
+        } else {
+          GCHK(snap_rollback(p, p.esnap, p.snap));
+        }
         p.stamps_clean = false;
         GCHK(gpu::d2d(p.d_stats, p.d_stats_snap, kStatShards * sizeof(StatShard), p.stream));
         p.st.wasted_rounds += c.rounds;  // (kept apart: `rounds` / `committed` / `planned` describe committed work only)
@@ -1343,6 +1363,7 @@ int Engine::run_speculative(const Op *d_ops, uint64_t n) {
 
 int Engine::run_exclusive(Op op, uint32_t flags, const Op *d_ops, uint32_t spec_index, bool *violation, bool *resized, bool later_committed) {
   Impl &p = *p_;
+  p.live_is_snap = false;
   if (violation) *violation = false;
   if (resized) *resized = false;
   const bool spec = spec_index != kMax;
@@ -1479,6 +1500,7 @@ int Engine::rebalance_fused(const View &nv, const Edge *src_items, uint64_t src_
                             uint32_t *src_cnt, bool inplace, uint64_t tb_index, uint64_t tb_len, Edge *dst, uint64_t dst_bias,
                             uint32_t *dst_cnt, uint64_t dst_nleaves) {
   Impl &p = *p_;
+  p.live_is_snap = false;
   const uint64_t nleaves = src_len >> src_sh;
   // tile size: as large as the workgroup when that still gives every CU several tiles, smaller for smaller windows
   uint32_t tile = p.rb_tile;
@@ -1513,6 +1535,7 @@ int Engine::resize(uint64_t newN) {
   Impl &p = *p_;
   if (newN < 2) return fail(PPCSR_EUNSUPPORTED, "array cannot shrink further");
   if (newN > (1ull << 31)) return fail(PPCSR_EUNSUPPORTED, "edge array would exceed 2^31 slots (reference indexes with int)");
+  p.live_is_snap = false;
   const View old = p.v;
   const uint64_t oldN = old.g.N;
   const uint64_t old_leaves = oldN >> old.g.sh;
@@ -1586,6 +1609,7 @@ int Engine::inplace_fault_check() {
 // persistent scratch array; a whole-array window then just swaps the buffers, a partial window is copied back
 int Engine::big_redistribute(uint64_t wstart, uint64_t wlen, bool sync) {
   Impl &p = *p_;
+  p.live_is_snap = false;
   const View v = p.v;
   const uint64_t leaf_lo = wstart >> v.g.sh, nleaves = wlen >> v.g.sh;
   const bool fused = p.scatter_variant == 2 && v.g.logN <= 32;
@@ -1676,6 +1700,7 @@ int Engine::remove_edge(uint32_t s, uint32_t d) {
 int Engine::add_node() {  // PCSR.cpp:681-703
   Impl &p = *p_;
   GCHK(gpu::set_device(device_));
+  p.live_is_snap = false;
   const uint32_t len = p.v.g.n;
   if ((uint64_t)len + 1 > p.n_cap) {
     const uint64_t ncap = p.n_cap * 2;
@@ -2042,6 +2067,7 @@ int Engine::set_num_neighbors_device(const Op *d_recs, uint64_t cnt) {
   Impl &p = *p_;
   GCHK(gpu::set_device(device_));
   if (cnt == 0) return PPCSR_OK;
+  p.live_is_snap = false;
   GPU_LAUNCH(p.stream, k_nn_set, grid_for(cnt, 256), 256, p.v, d_recs, cnt);
   GCHK(gpu::sync(p.stream));
   GCHK(gpu::last_error());
@@ -2116,6 +2142,7 @@ int Engine::bulk_build_device(const Op *d_adds, uint64_t m, double *device_ms) {
 int Engine::bulk_build_from(const Op *in_ops, bool on_device, uint64_t m, double *device_ms) {
   Impl &p = *p_;
   GCHK(gpu::set_device(device_));
+  p.live_is_snap = false;
   const uint32_t nn = n();
   if (nn == 0) return fail(PPCSR_EINVAL, "bulk_build: the graph has no vertices");
   if (m >= (1ull << 31)) return fail(PPCSR_EUNSUPPORTED, "bulk_build: too many edges for one call");
@@ -2447,6 +2474,7 @@ int Engine::snapshot() {
   Impl &p = *p_;
   GCHK(gpu::set_device(device_));
   GCHK(snap_commit(p, p.snap));
+  p.live_is_snap = true;
   GCHK(gpu::sync(p.stream));
   return PPCSR_OK;
 }
@@ -2461,7 +2489,8 @@ int Engine::restore() {
   Impl &p = *p_;
   if (!p.snap.valid) return fail(PPCSR_EINVAL, "restore without snapshot");
   GCHK(gpu::set_device(device_));
-  GCHK(snap_rollback(p, p.snap, p.esnap));
+  GCHK(snap_rollback(p, p.snap, p.esnap));  // (either path: the incremental one or the full load)
+  p.live_is_snap = true;
   p.stamps_clean = false;
   return PPCSR_OK;
 }

@@ -235,6 +235,35 @@ PMA_KERNEL void o_settle(OptArgs a) {
   if (wv::thread_idx() == 0) round_record(a, c, s);
 }
 
+// Start of an epoch, one launch in front of its first round: the validation stamps cleared (clear != 0: first epoch of a batch
+// and after a rollback; wstamp / rstamp: `leaves` words, vws / vrs: `nv` words), the stat shards saved for a rollback, and the
+// control block as the host composed it — max_horizon, the first chunk's grid, included.  Grid-stride, 16 bytes per store where
+// four words are left, word stores for the up to three behind them.
+PMA_DEV void epoch_zero_words(uint32_t *p, uint64_t n, uint64_t tid, uint64_t stride) {
+  uint4 *p4 = reinterpret_cast<uint4 *>(p);
+  const uint64_t n4 = n >> 2;
+  uint4 z;
+  z.x = z.y = z.z = z.w = 0u;
+  for (uint64_t i = tid; i < n4; i += stride) p4[i] = z;
+  if (tid < (n & 3ull)) p[(n4 << 2) + tid] = 0u;
+}
+PMA_KERNEL void k_epoch_begin(uint32_t *wstamp, uint32_t *rstamp, uint64_t leaves, uint32_t *vws, uint32_t *vrs, uint64_t nv, uint32_t clear,
+                              const StatShard *stats, StatShard *stats_snap, OptCtl *ctl, OptCtl init) {
+  const uint64_t stride = (uint64_t)wv::grid_dim() * wv::block_dim();
+  const uint64_t tid = (uint64_t)wv::block_idx() * wv::block_dim() + wv::thread_idx();
+  if (clear) {
+    epoch_zero_words(wstamp, leaves, tid, stride);
+    epoch_zero_words(rstamp, leaves, tid, stride);
+    epoch_zero_words(vws, nv, tid, stride);
+    epoch_zero_words(vrs, nv, tid, stride);
+  }
+  static_assert((kStatShards * sizeof(StatShard)) % sizeof(uint4) == 0, "stat shards: whole 16-byte words");
+  const uint4 *s4 = reinterpret_cast<const uint4 *>(stats);
+  uint4 *d4 = reinterpret_cast<uint4 *>(stats_snap);
+  for (uint64_t i = tid; i < kStatShards * sizeof(StatShard) / sizeof(uint4); i += stride) d4[i] = s4[i];
+  if (tid == 0) *ctl = init;
+}
+
 // words of the round's state that wave 0 of a workgroup hands to the others (LDS, lane i <-> word i)
 enum RoundWord : int { RW_STOP = 0, RW_HOR, RW_USED, RW_NF, RW_PRE0, RW_SKIP_IDX = RW_PRE0 + (int)kStripes + 1, RW_SKIP_ROUND, RW_WORDS };
 static_assert(RW_WORDS <= 16, "round words");
