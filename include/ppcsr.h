@@ -395,6 +395,9 @@ int ppcsr_restore(ppcsr_t h);
  * only while option "snap_count" is 1 (0 until then; the option adds a stream synchronisation to every incremental
  * synchronisation, so it is for tests).  EINVAL: null handle or out. */
 int ppcsr_debug_snap_counters(ppcsr_t h, uint64_t out[6]);
+/* Debugging: entries of the speculative rounds' per-slot reservation table for duplicate overwrites (a power of two; slots that
+ * many apart share an entry, which defers the later of two overwrites planned together by a round).  For tests that place edges. */
+uint64_t ppcsr_debug_dup_slot_entries(void);
 /* debugging / measurement helpers */
 int ppcsr_check_invariants(ppcsr_t h, uint64_t *bad_leaves);
 int ppcsr_bench_scan_all(ppcsr_t h, double *ms, uint64_t *total);

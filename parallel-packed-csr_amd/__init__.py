@@ -80,7 +80,7 @@ EXPORTED = [
     "ppcsr_triangles", "pppcsr_triangles", "ppcsr_common_neighbours", "ppcsr_common_neighbours_device", "pppcsr_common_neighbours",
     "ppcsr_sample_neighbours", "ppcsr_sample_neighbours_device", "pppcsr_sample_neighbours",
     "ppcsr_random_walks", "ppcsr_random_walks_device", "pppcsr_random_walks", "ppcsr_degrees", "pppcsr_degrees", "ppcsr_debug_mulhi",
-    "ppcsr_multi_bfs", "pppcsr_multi_bfs", "ppcsr_debug_multi_bfs_counters",
+    "ppcsr_multi_bfs", "pppcsr_multi_bfs", "ppcsr_debug_multi_bfs_counters", "ppcsr_debug_dup_slot_entries",
 ]
 
 NO_PATH = 0xFFFFFFFFFFFFFFFF  # PPCSR_NO_PATH: what sssp reports for a vertex no path reaches
@@ -88,6 +88,14 @@ NO_EDGE = 0xFFFFFFFF  # PPCSR_NO_EDGE: what lookup_edges reports for a pair that
 NO_VERTEX = 0xFFFFFFFF  # PPCSR_NO_VERTEX: what sample_neighbours / random_walks report where there is nothing to pick from
 
 _LIBS = {}
+
+
+def dup_slot_entries(lib=None):
+    """Debugging (ppcsr_debug_dup_slot_entries): entries of the speculative rounds' per-slot table for duplicate overwrites — two
+    slots that many apart share an entry.  (Resolved on use: a library older than the table still loads.)"""
+    f = (lib or load_library()).ppcsr_debug_dup_slot_entries
+    f.restype, f.argtypes = c_u64, []
+    return int(f())
 
 
 def _share_hip_runtime():

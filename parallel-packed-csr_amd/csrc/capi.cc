@@ -348,6 +348,7 @@ int ppcsr_bench_resize(ppcsr_t h, int iters, double *double_ms, double *half_ms)
 int ppcsr_snapshot(ppcsr_t h) { H_CHECK(); return ret(h->e, h->e->snapshot()); }
 int ppcsr_restore(ppcsr_t h) { H_CHECK(); return ret(h->e, h->e->restore()); }
 int ppcsr_debug_snap_counters(ppcsr_t h, uint64_t out[6]) { H_CHECK(); return ret(h->e, h->e->snap_counters(out)); }
+uint64_t ppcsr_debug_dup_slot_entries(void) { return ppcsr::Engine::dup_slot_entries(); }
 const char *ppcsr_strerror(int status) { return ppcsr::error_string(status); }
 const char *ppcsr_last_error(void) { return g_last_error.c_str(); }
 

@@ -115,6 +115,7 @@ struct Engine::Impl {
   uint32_t *d_status = nullptr, *d_carry0 = nullptr, *d_carry1 = nullptr;
   uint64_t carry_cap = 0, hslot_cap = 0;
   unsigned long long *d_regfail = nullptr, *d_pfail = nullptr;
+  unsigned long long *d_dslot = nullptr;  // kDupSlots entries whatever the array's size: allocated once, restarted with the other tag arrays
   uint32_t *d_vws = nullptr, *d_vrs = nullptr;  // per-vertex sentinel stamps (capacity n_cap + 1)
   uint32_t *d_wstamp = nullptr, *d_rstamp = nullptr;
   uint32_t mode = 1;             // 0 = strict prefix rounds, 1 = speculative rounds with validated rollback
@@ -165,8 +166,14 @@ struct Engine::Impl {
   // config #2 258 / 263 / 261 M/s).  A round's kernels are bound by latency, so a round
   // of 2 x resident takes ~1.4x the time of one of 1 x resident; widths in between leave the second pass partly empty
   // (config #2, updates/s: 6144 -> 139 M, 8192 -> 130 M, 12288 -> 162 M, 18432 -> 169 M, 24576 -> 153 M: the re-planned
-  // share grows with the width — 3 %, 7 %, 12 %).  init() sets opt_horizon = 3 x resident, start_horizon = resident; the
-  // adaptive width only climbs above 1 x while more than 85 % of a round commits.
+  // share grows with the width — 3 %, 7 %, 12 %).  Those figures are from rounds whose count a chain of duplicate overwrites in
+  // one leaf bounded whatever the width; with duplicates ordered per slot (kDupSlots) the commits follow the width and config #2
+  // takes 51 / 40 / 34 / 30 rounds per step at 3 / 4 / 5 / 6 x resident, 3.37 / 3.28 / 3.37 / 3.51 ms: the re-planned share
+  // (4 / 7 / 9 / 13 %) and the cost per planned update past three passes eat the rounds saved above 4 x.  4 x was not made the
+  // default: in the same call it cost config #3 1.5 % (12 instead of 7 synchronisations in 3 steps) and the hot-vertex stream
+  // 4 % at equal round counts, both outside the parent's range (profiles/dup_slot_rounds.json).  init() sets
+  // opt_horizon = 3 x resident, start_horizon = resident; the adaptive width only climbs above 1 x while more than 85 % of a
+  // round commits.
   uint32_t resident_waves = 0;  // 0: unknown (emulator) — no quantisation of the adapted width
   uint32_t opt_horizon = 6144;    // (the CPU emulator, which reports no CUs, keeps these)
   uint32_t start_horizon = 6144;
@@ -272,6 +279,7 @@ static int reset_tags(Engine::Impl &p) {
   if (p.v.dres && (e = gpu::dset(p.v.dres, 0xFF, leaves * sizeof(unsigned long long), p.stream))) return e;
   if (p.d_regfail && (e = gpu::dset(p.d_regfail, 0xFF, (leaves + 1) * sizeof(unsigned long long), p.stream))) return e;
   if (p.d_pfail && (e = gpu::dset(p.d_pfail, 0xFF, (leaves + 1) * sizeof(unsigned long long), p.stream))) return e;
+  if (p.d_dslot && (e = gpu::dset(p.d_dslot, 0xFF, (uint64_t)kDupSlots * sizeof(unsigned long long), p.stream))) return e;
   if (p.v.vw && (e = gpu::dset(p.v.vw, 0xFF, (p.n_cap + 1) * sizeof(unsigned long long), p.stream))) return e;
   if (p.v.vr && (e = gpu::dset(p.v.vr, 0xFF, (p.n_cap + 1) * sizeof(unsigned long long), p.stream))) return e;
   p.round = 0;
@@ -294,6 +302,9 @@ static int alloc_aux(Engine::Impl &p, View &v) {
   if ((e = gpu::dset(v.wres, 0xFF, leaves * sizeof(unsigned long long), p.stream))) return e;
   if ((e = gpu::dset(v.rres, 0xFF, leaves * sizeof(unsigned long long), p.stream))) return e;
   if ((e = gpu::dset(p.d_regfail, 0xFF, (leaves + 1) * sizeof(unsigned long long), p.stream))) return e;
+  // (not per leaf: it outlives the array, but the round counter restarts below and its keys with it)
+  if (!p.d_dslot && (e = gpu::dmalloc((void **)&p.d_dslot, (uint64_t)kDupSlots * sizeof(unsigned long long)))) return e;
+  if ((e = gpu::dset(p.d_dslot, 0xFF, (uint64_t)kDupSlots * sizeof(unsigned long long), p.stream))) return e;
   if ((e = gpu::dset(p.d_wstamp, 0, leaves * sizeof(uint32_t), p.stream))) return e;
   if ((e = gpu::dset(p.d_rstamp, 0, leaves * sizeof(uint32_t), p.stream))) return e;
   if ((e = gpu::dmalloc((void **)&v.ldirty, leaves * sizeof(uint32_t)))) return e;
@@ -345,6 +356,8 @@ static void free_aux(Engine::Impl &p, View &v) {
   p.d_regfail = nullptr;
 }
 
+uint64_t Engine::dup_slot_entries() { return kDupSlots; }
+
 int Engine::fail(int code, const std::string &msg) {
   err_ = msg;
   return code;
@@ -393,7 +406,7 @@ int Engine::init(uint32_t init_n, uint32_t src_n, int lock_search, int device) {
     if (cus > 0) {
       p.resident_waves = (uint32_t)cus * 28u;
       p.start_horizon = p.resident_waves;
-      p.opt_horizon = 3u * p.resident_waves;
+      p.opt_horizon = 3u * p.resident_waves;  // (4 x is faster on config #2 and slower on configs #3 and #5: profiles/dup_slot_rounds.json)
     }
   }
   const uint64_t N = initial_N(init_n, src_n);
@@ -491,6 +504,7 @@ Engine::~Engine() {
   if (p.d_vdbg) GPU_DFREE(p.d_vdbg);
   if (p.d_carry0) GPU_DFREE(p.d_carry0);
   if (p.d_carry1) GPU_DFREE(p.d_carry1);
+  if (p.d_dslot) GPU_DFREE(p.d_dslot);
   GPU_DFREE(p.d_ctl);
   gpu::hfree(p.h_ctl);
   GPU_DFREE(p.d_stats);
@@ -1096,6 +1110,7 @@ int Engine::run_speculative(const Op *d_ops, uint64_t n) {
       a.rstamp = p.d_rstamp;
       a.vws = p.d_vws;
       a.vrs = p.d_vrs;
+      a.dslot = p.d_dslot;
       a.regshift = rs;
       a.diag = p.diag;
       a.defer_barrier = p.defer_barrier;

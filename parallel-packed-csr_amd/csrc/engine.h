@@ -175,6 +175,7 @@ class Engine {
   int restore();   // back to the last snapshot (device-to-device)  // whole-window rebalance kernel timing
 
   int snap_counters(uint64_t out[6]);  // ppcsr_debug_snap_counters (include/ppcsr.h)
+  static uint64_t dup_slot_entries();  // ppcsr_debug_dup_slot_entries (include/ppcsr.h)
 
   uint64_t N() const;
   uint32_t n() const;

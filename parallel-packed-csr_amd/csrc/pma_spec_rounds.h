@@ -13,7 +13,9 @@ namespace ppcsr {
 // writes.  Passing updates commit unless an earlier update of the same REGION (aligned block of 2^regshift leaves)
 // failed this round — a per-region strict prefix, which keeps later updates from overtaking a deferred update inside
 // the block where its footprint can still move (rebalance windows are aligned power-of-two blocks no larger than a
-// region, so a deferred update's window cannot leave its region).
+// region, so a deferred update's window cannot leave its region).  Duplicate overwrites (K_DUP) write one slot's value and move
+// nothing: they reserve their leaf in dres, which only strong writers of the leaf test, and their SLOT in dslot, which orders two
+// overwrites of one slot — duplicates of different slots of a leaf commit in the same round.
 //
 // Soundness does not rest on that heuristic: every committed update stamps the leaves it read (rstamp) and wrote
 // (wstamp) with its stream index, and an update may only commit if no LATER update has already written a leaf it
@@ -83,6 +85,7 @@ struct OptArgs {
   unsigned long long *pfail;  // per-leaf: smallest deferred update whose footprint may still grow over this leaf
   uint32_t *wstamp, *rstamp;
   uint32_t *vws, *vrs;  // per vertex: 1 + latest committed update that moved / read the position of its sentinel
+  unsigned long long *dslot;  // kDupSlots entries, entry (slot & (kDupSlots - 1)): earliest pending DUPLICATE update of that slot
   uint32_t round;
   int regshift;
   uint32_t diag;
@@ -100,6 +103,12 @@ struct OptArgs {
   uint32_t *dg;
 };
 constexpr uint32_t kBigJobs = 256;  // capacity of the round's job queue
+// Duplicates are ordered among themselves per SLOT, not per leaf (a hot vertex' first leaves take dozens of overwrites of different
+// edges per batch, which commute).  The table has a fixed size and is indexed by the slot modulo that size — no scrambling: the slots
+// of a leaf, of a region, of any array of at most kDupSlots slots never share an entry; two slots a multiple of kDupSlots apart do,
+// which only defers the later update by a round.
+constexpr uint32_t kDupSlots = 1u << 16;
+static_assert((kDupSlots & (kDupSlots - 1u)) == 0u, "dslot is indexed by slot & (kDupSlots - 1)");
 constexpr uint32_t kRegionPadLeaves = 2u;
 constexpr uint32_t kGrowLeaves = 8u;
 constexpr uint32_t OS_PASS = 1u, OS_STAMP_BAD = 2u;
@@ -353,7 +362,9 @@ PMA_DEV void o_plan_t(const OptArgs &a) {
     return;
   }
   if (kind == K_DUP) {
-    if (lane == 0) wv::atomic_min_u64(&a.v.dres[pr.wleaf_lo], key);
+    // lane 0: the leaf's entry (what strong writers of the leaf test), lane 1: the slot's (what later duplicates of the slot test) — one instruction
+    unsigned long long *const e = lane == 0 ? &a.v.dres[pr.wleaf_lo] : &a.dslot[pr.index & (kDupSlots - 1u)];
+    if (lane < 2) wv::atomic_min_u64(e, key);
   } else if (kind_strong(kind)) {
     const uint32_t wl = pr.wleaf_lo, wh = pr.wleaf_hi;
     for (uint32_t base = wl; base <= wh; base += 64) {  // (scalar trip count)
@@ -431,7 +442,7 @@ PMA_DEV void o_check_one(const OptArgs &a, OptCtl *c, uint32_t par, uint32_t wid
   if (kind == K_DUP) {
     const uint32_t leaf = h.wleaf_lo;
     if (key_earlier(a.v.wres[leaf], tag, idx)) { fail = true; PMA_WHY(2u); }  // an earlier pending update moves slots of this leaf
-    if (a.v.dres[leaf] != key) { fail = true; PMA_WHY(2u); }                   // an earlier pending duplicate on this leaf
+    if (a.dslot[h.index & (kDupSlots - 1u)] != key) { fail = true; PMA_WHY(2u); }  // an earlier pending duplicate of this slot (or of one kDupSlots apart)
   }
   if (strong) {
     const uint32_t wl = h.wleaf_lo, wh = h.wleaf_hi;
@@ -643,6 +654,7 @@ PMA_KERNEL void o_check(OptArgs a) {
     const uint32_t w0 = wany ? wl : 0u, w1 = (wany && wh > wl) ? wh : w0;
     const unsigned long long kw0 = a.v.wres[w0], kd0 = a.v.dres[w0], kr0 = a.v.rres[w0], kw1 = a.v.wres[w1], kd1 = a.v.dres[w1], kr1 = a.v.rres[w1];
     const uint32_t sw0 = a.wstamp[w0], sr0 = a.rstamp[w0], sw1 = a.wstamp[w1], sr1 = a.rstamp[w1];
+    const unsigned long long ks0 = a.dslot[(mine && kind == K_DUP) ? (index & (kDupSlots - 1u)) : 0u];
     unsigned long long rk[kCkRanges][2];
     uint32_t rs[kCkRanges][2], rl[kCkRanges][2];
 #pragma unroll
@@ -673,7 +685,7 @@ PMA_KERNEL void o_check(OptArgs a) {
     // ---- every compare ------------------------------------------------------------------------------------------------
     if (mine && kind == K_DUP) {
       if (key_earlier(kw0, tag, idx)) fail = true;  // an earlier pending update moves slots of this leaf
-      if (kd0 != key) fail = true;                   // an earlier pending duplicate on this leaf
+      if (ks0 != key) fail = true;                   // an earlier pending duplicate of this slot (or of one kDupSlots apart)
     }
     if (mine && strong) {
       if (kw0 != key || kw1 != key) fail = true;                                  // an earlier pending update writes it
