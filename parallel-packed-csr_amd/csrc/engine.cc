@@ -11,16 +11,43 @@
 #include <chrono>
 
 #include "gpu_rt.h"
+#include "pma_epoch_policy.h"
 #define GPU_DFREE(x) gpu::dfree_named((x), #x, __LINE__)
 #include "pma_kernels.h"
 
 namespace ppcsr {
 
-#define GCHK(expr)                                                                       \
-  do {                                                                                   \
-    int _e = (expr);                                                                     \
-    if (_e != 0) return fail(PPCSR_EHIP, std::string(#expr) + ": " + gpu::err_str(_e)); \
+// GCHK_AS: the message names `text`, not the expression: a runtime call made inside a helper (grow_buf) fails under its own name
+#define GCHK_AS(expr, text)                                                             \
+  do {                                                                                  \
+    int _e = (expr);                                                                    \
+    if (_e != 0) return fail(PPCSR_EHIP, std::string(text) + ": " + gpu::err_str(_e)); \
   } while (0)
+#define GCHK(expr) GCHK_AS(expr, #expr)
+
+// (re)allocate a device buffer to hold `need` elements; the old contents are not kept.  The one way a scratch buffer grows:
+// a failed allocation leaves *b null and *cap 0, so the next call tries again
+template <class T>
+static int grow_buf(T **b, uint64_t *cap, uint64_t need) {
+  if (need <= *cap) return 0;
+  if (*b) gpu::dfree(*b);
+  *b = nullptr;
+  *cap = 0;
+  const int e = gpu::dmalloc((void **)b, need * sizeof(T));
+  if (e == 0) *cap = need;
+  return e;
+}
+// ... and several buffers of `need` elements each that share one capacity field
+template <class... T>
+static int grow_bufs(uint64_t *cap, uint64_t need, T **...b) {
+  if (need <= *cap) return 0;
+  *cap = 0;
+  int e = 0;
+  uint64_t c = 0;
+  (void)(((c = 0, e = grow_buf(b, &c, need)) != 0) || ...);
+  if (e == 0) *cap = need;
+  return e;
+}
 
 // frees the device buffers registered with it on every exit path (error returns included) unless dismissed
 struct DevGuard {
@@ -113,53 +140,13 @@ struct Engine::Impl {
   OptCtl *d_octl = nullptr, *h_octl = nullptr;
   uint32_t *d_vdbg = nullptr;
   uint32_t *d_status = nullptr, *d_carry0 = nullptr, *d_carry1 = nullptr;
-  uint64_t carry_cap = 0, hslot_cap = 0;
+  uint64_t carry_cap = 0, status_cap = 0, vdbg_cap = 0;  // (carry_cap: entries per sub-list, OptArgs::carry_cap; the others: words)
   unsigned long long *d_regfail = nullptr, *d_pfail = nullptr;
   unsigned long long *d_dslot = nullptr;  // kDupSlots entries whatever the array's size: allocated once, restarted with the other tag arrays
   uint32_t *d_vws = nullptr, *d_vrs = nullptr;  // per-vertex sentinel stamps (capacity n_cap + 1)
   uint32_t *d_wstamp = nullptr, *d_rstamp = nullptr;
   uint32_t mode = 1;             // 0 = strict prefix rounds, 1 = speculative rounds with validated rollback
-  uint32_t epoch_ops = 1u << 20;  // rollback granularity (upper bound)
-  // adaptive epoch length: a rollback throws away everything since the epoch's snapshot, so a stream that provokes
-  // rollbacks (hot vertices whose windows balloon while they wait) is cut into short epochs — kEpochShort updates after a
-  // rollback, doubling again with every epoch that ends cleanly — while a stream that never rolls back keeps one
-  // snapshot per epoch_ops updates
-  uint32_t cur_epoch = 0;
-  // (a snapshot costs about one round; a rollback re-does half an epoch on average.  On a config #4 partition — 3 rollbacks
-  // per 1.25 M inserts — 8192 / 8 spent 16 % of the batch copying snapshots: 16384 / 2 took 30.4 ms instead of 38.4; the
-  // Zipf stream on the same partition, 50 rollbacks per 1.5 M updates, was indifferent: 208 ms either way)
-  uint32_t epoch_short = 16384;  // epoch length after a rollback
-  uint32_t epoch_clean = 0, epoch_grow_after = 2;  // clean epochs in a row / how many of them double the length again
-  // Round 3: with incremental snapshots an epoch boundary costs ~30 us, so a stream that rolls back often is better off with
-  // epochs a good deal shorter than the distance between its rollbacks (hot-vertex stream: one rollback per 28 K updates;
-  // 2048-update epochs that double after 4 clean ones: 121 -> 105 ms per 1 M), while a stream that rolls back three times
-  // per million (a config #4 partition) needs the long ones (4096-update epochs: 24 -> 35 ms).  epoch_adapt = 1: the epoch
-  // after a rollback is 1/epoch_adapt (default 8) of the running mean distance between rollbacks, within [2048, epoch_short].
-  uint32_t epoch_adapt = 8, grow_eff = 2;  // (epoch_adapt: 0 off, else the divisor)
-  uint64_t since_rollback = 0;
-  double rb_dist = -1.0;
-  // per-region prefix rule: nothing later may commit in a region where an earlier update was deferred.  4096 slots blocked
-  // 43 K of the 69 K non-commits per 1 M updates of config #2 for nothing (179 M/s; 2048: 184, 1024: 187, 512: 188, 256: 189);
-  // the hot-vertex stream needs the rule (1024: 142 ms as with 4096, 83 rollbacks instead of 36; 256: 191 ms, 199 rollbacks)
-  uint32_t region_slots = 1024;
-  // ... so the rule is tightened where rollbacks happen: after one, regions are region_wide slots until region_calm epochs in
-  // a row have ended cleanly (a config #4 partition at critical density: 31.1 ms / 9 rollbacks with 1024 throughout, 26.7 ms
-  // / 3 rollbacks with 4096; its calm second half is config-#2-like again)
-  uint32_t region_wide = 4096, region_calm = 8, region_eff = 0, region_clean = 0;
-  // Round 3: a stream whose rollbacks are RARE (running mean distance >= region_rare_dist updates: a config #4 partition at
-  // critical density, one per ~150 K updates while its levels sit at their bounds) is better off paying for none at all:
-  // region_rare slots after a rollback, for region_rare_calm (8) x that distance of committed updates (24.9 -> 19.3 ms per batch of
-  // the partition: 193 -> 157 rounds, 0 rollbacks; the wide rule ends about where the array doubles and the stream turns calm).
-  // A stream that rolls back all the time (hot vertices, one per 28 K updates) keeps region_wide / region_calm: with 16 K-slot
-  // regions it loses more commits per round than the rollbacks cost (105 -> 131 ms); a stream that never rolls back never
-  // sees either rule.
-  uint32_t region_rare = 16384, region_rare_calm = 8, region_rare_dist = 65536;
-  uint64_t region_rare_span = 0;  // > 0: the rare rule is on until this many updates have committed since the rollback
-  // ... and only for streams that commit a good share of a chip-full per round (running mean >= region_rare_cpr): wide regions
-  // make rollbacks rarer for ANY stream, so the distance alone would also switch the rule on for the hot-vertex stream once it
-  // has been on for a while (600-750 commits per round there, 6-8 K on the critical-density partition)
-  uint32_t region_rare_cpr = 1536;
-  double cpr_mean = -1.0;
+  EpochPolicy pol;  // epoch length and region width (pma_epoch_policy.h, with the measurements behind its constants)
   // Round width (upper bound when `adaptive` is on).  One update = one wave; `resident_waves` of them fit the chip at once
   // (rounds 1-3: o_plan at 78 VGPRs = 6 waves per SIMD, 24 per CU, 6144 on 256 CUs; since round 4 o_plan runs 8 per SIMD and
   // o_apply — one 6 KB LDS tile per wave — 6: the unit is 7 per SIMD, 7168 on 256 CUs, measured best of 6144 / 7168 / 8192:
@@ -193,16 +180,8 @@ struct Engine::Impl {
   uint64_t bigscratch_cap = 0;
   uint32_t rb_tile = 0;          // leaves per rebalance tile (power of two <= 256); 0 = pick per window
   uint32_t rb_min_tiles = 4096;  // auto tile: shrink the tile until the window has at least this many
-  // o_big (the launch that rebalances the windows a round queues for workgroups) is left out of the rounds while a stream queues
-  // none: a round that does queue one then stops the chunk (OptCtl::need_big), the host runs the launch and keeps it in for a while
-  bool big_on = false;
-  double big_rate = 0;
-  // o_check: a lane per update while updates have short footprints (one leaf, two or three read ranges); a wave per update for
-  // streams where more than ~1 in 64 has a long one (hot ranges, critical density: big windows, many-level climbs, runs of moved
-  // sentinels), which the lane kernel leaves to its wave one by one
-  bool check_lanes = true;
-  uint32_t check_wave_chunks = 0;
-  int check_force = -1;  // option "check_lanes": -1 by the share of long footprints (default), 0 always a wave per update, 1 always a lane
+  BigChoice big;      // whether o_big stays in the rounds, and
+  CheckChoice check;  // which o_check runs (pma_epoch_policy.h)
   uint32_t rb_prefetch = 1;  // 1: four chunks in flight per wave, 0: one
   bool time_resize = false;  // resize_bench: time the passes of resize() with events
   double last_resize_ms = 0;
@@ -262,12 +241,7 @@ static int ensure_plans(Engine::Impl &p) {
   if (p.plans_cap >= need) return 0;
   int e = gpu::sync(p.stream);
   if (e) return e;
-  Plan *np = nullptr;
-  if ((e = gpu::dmalloc((void **)&np, need * sizeof(Plan)))) return e;
-  if (p.d_plans) GPU_DFREE(p.d_plans);
-  p.d_plans = np;
-  p.plans_cap = need;
-  return 0;
+  return grow_buf(&p.d_plans, &p.plans_cap, need);
 }
 
 // every round-tagged reservation array restarts together with the round counter (stale keys must never meet a reused tag)
@@ -500,10 +474,6 @@ Engine::~Engine() {
   if (p.v.vdirty) GPU_DFREE(p.v.vdirty);
   GPU_DFREE(p.d_octl);
   gpu::hfree(p.h_octl);
-  if (p.d_status) GPU_DFREE(p.d_status);
-  if (p.d_vdbg) GPU_DFREE(p.d_vdbg);
-  if (p.d_carry0) GPU_DFREE(p.d_carry0);
-  if (p.d_carry1) GPU_DFREE(p.d_carry1);
   if (p.d_dslot) GPU_DFREE(p.d_dslot);
   GPU_DFREE(p.d_ctl);
   gpu::hfree(p.h_ctl);
@@ -518,18 +488,12 @@ Engine::~Engine() {
   GPU_DFREE(p.d_table);
   if (p.d_ip) GPU_DFREE(p.d_ip);
   if (p.d_snapcnt) GPU_DFREE(p.d_snapcnt);
-  GPU_DFREE(p.d_plans);
-  if (p.d_ops) GPU_DFREE(p.d_ops);
-  if (p.d_rank) GPU_DFREE(p.d_rank);
-  if (p.d_tiles) GPU_DFREE(p.d_tiles);
-  if (p.d_nbr) GPU_DFREE(p.d_nbr);
-  if (p.d_scratch) GPU_DFREE(p.d_scratch);
-  if (p.d_scan_state) GPU_DFREE(p.d_scan_state);
   if (p.d_jobs) GPU_DFREE(p.d_jobs);
-  if (p.d_bigscratch) GPU_DFREE(p.d_bigscratch);
-  if (p.d_dg) GPU_DFREE(p.d_dg);
-  for (void *b : {(void *)p.q.src, (void *)p.q.dst, (void *)p.q.val, (void *)p.q.q, (void *)p.q.lo, (void *)p.q.len, (void *)p.q.nch,
-                  (void *)p.q.choff, (void *)p.q.rows, (void *)p.q.crow, (void *)p.q.ccnt, (void *)p.q.ooff, (void *)p.q.sdst,
+  // (what grow_buf allocates)
+  for (void *b : {(void *)p.d_plans, (void *)p.d_ops, (void *)p.d_status, (void *)p.d_vdbg, (void *)p.d_carry0, (void *)p.d_carry1,
+                  (void *)p.d_bigscratch, (void *)p.d_dg, (void *)p.d_rank, (void *)p.d_tiles, (void *)p.d_scratch, (void *)p.d_nbr,
+                  (void *)p.d_scan_state, (void *)p.q.src, (void *)p.q.dst, (void *)p.q.val, (void *)p.q.q, (void *)p.q.lo, (void *)p.q.len,
+                  (void *)p.q.nch, (void *)p.q.choff, (void *)p.q.rows, (void *)p.q.crow, (void *)p.q.ccnt, (void *)p.q.ooff, (void *)p.q.sdst,
                   (void *)p.q.sval, (void *)p.q.xs})
     if (b) gpu::dfree(b);
   for (Impl::Snap *sp : {&p.snap, &p.esnap}) {
@@ -543,9 +507,94 @@ Engine::~Engine() {
   delete p_;
 }
 
+// The options that check or clamp a value and store one scalar.  What a row's rule does with `value`:
+//   kReject: EINVAL outside [lo, hi]                        kClamp: stores max(lo, min(value, hi))
+//   kPow2:   EINVAL unless a power of two >= lo (kPow2Or0: or 0); stores min(value, hi)
+//   kBool:   stores value != 0                              kOneOf: EINVAL unless bit `value` of the mask lo is set
+// The stored value is cast to the field's type as it is (a clamp open at the top keeps the low 32 bits of a huge value).
+enum OptRule { kReject, kClamp, kPow2, kPow2Or0, kBool, kOneOf };
+struct OptRow {
+  const char *key;
+  void *(*field)(Engine::Impl &);
+  bool wide;  // the field is a uint64_t, else a uint32_t
+  OptRule rule;
+  int64_t lo, hi;
+  const char *msg;  // of a rejected value
+};
+#define OPT_U32(key, field) key, [](Engine::Impl &p) -> void * { return &p.field; }, false
+#define OPT_U64(key, field) key, [](Engine::Impl &p) -> void * { return &p.field; }, true
+static const int64_t kOptMin = INT64_MIN, kOptMax = INT64_MAX;
+static const OptRow kOptRows[] = {
+    {OPT_U32("mode", mode), kOneOf, 0x3, 0, "mode must be 0 (strict) or 1 (speculative)"},
+    {OPT_U32("epoch_ops", pol.epoch_ops), kReject, 1, 1 << 24, "epoch_ops out of range"},
+    {OPT_U32("epoch_short", pol.epoch_short), kClamp, 64, kOptMax, nullptr},
+    {OPT_U32("epoch_adapt", pol.epoch_adapt), kClamp, 0, 1024, nullptr},
+    {OPT_U32("epoch_grow_after", pol.epoch_grow_after), kClamp, 1, kOptMax, nullptr},
+    {OPT_U32("region_wide", pol.region_wide), kPow2, 1, kOptMax, "region_wide must be a power of two"},
+    {OPT_U32("region_rare", pol.region_rare), kPow2Or0, 1, kOptMax, "region_rare must be 0 or a power of two"},  // 0: off
+    {OPT_U32("region_rare_calm", pol.region_rare_calm), kClamp, 1, kOptMax, nullptr},
+    {OPT_U32("region_rare_cpr", pol.region_rare_cpr), kClamp, 0, kOptMax, nullptr},
+    {OPT_U32("region_rare_dist", pol.region_rare_dist), kClamp, 1, kOptMax, nullptr},
+    {OPT_U32("region_calm", pol.region_calm), kClamp, 1, kOptMax, nullptr},
+    {OPT_U32("scatter_blocks", scatter_blocks), kClamp, 64, kOptMax, nullptr},
+    {OPT_U32("search_narrow", v.g.narrow), kBool, 0, 0, nullptr},  // 0: the literal binary walk only (what a structure add_node has corrupted falls back to)
+    {OPT_U32("small_batch", small_batch), kClamp, 0, kOptMax, nullptr},
+    {OPT_U32("excl_in_wave", excl_in_wave), kClamp, 64, kOptMax, nullptr},
+    // (big_window <= kBigWindow: o_big is not launched at all — every window of a round is rebalanced by its own wave)
+    {OPT_U32("big_window", big_window), kPow2, 64, 1 << 20, "big_window must be a power of two >= 64"},
+    {OPT_U32("big_min", big_min), kClamp, 64, kBigWindow, nullptr},
+    {OPT_U32("big_grid", big_grid), kClamp, 1, 256, nullptr},
+    {OPT_U32("rb_min_tiles", rb_min_tiles), kClamp, 1, kOptMax, nullptr},
+    // (test hook: 1, 2, 4 or 8 ticket lists whatever the probe saw)
+    {OPT_U32("rb_inplace_lists", ip_lists), kOneOf, 0x116, 0, "rb_inplace_lists must be 1, 2, 4 or 8"},
+    // batched-read sizes (test hooks, as rb_inplace_lists: they move the seams of the staging and of the gather blocks; the
+    // scratch they size is regrown by the next call that needs more)
+    {OPT_U64("query_lookup_stage", q.lookup_stage), kReject, 1, 1ll << 32, "query sizes must be in [1, 2^32]"},
+    {OPT_U64("query_gather_rows", q.gather_rows), kReject, 1, 1ll << 32, "query sizes must be in [1, 2^32]"},
+    {OPT_U64("query_gather_chunks", q.gather_chunks), kReject, 1, 1ll << 32, "query sizes must be in [1, 2^32]"},
+    {OPT_U64("query_gather_stage", q.gather_stage), kReject, 1, 1ll << 32, "query sizes must be in [1, 2^32]"},
+    // snapshot hook (a test hook as well): the workgroup cap of k_snap_sync_leaves / k_snap_sync_nodes, which moves their
+    // grid-stride seam down to small arrays
+    {OPT_U32("snap_grid", snap_grid), kReject, 1, 4096, "snap_grid must be in [1, 4096]"},
+    {OPT_U64("rb_inplace_min", rb_inplace_min), kClamp, 0, kOptMax, nullptr},
+    {OPT_U32("rb_bench_upper", rb_bench_upper), kBool, 0, 0, nullptr},
+    {OPT_U32("rb_prefetch", rb_prefetch), kBool, 0, 0, nullptr},
+    {OPT_U32("msbfs_look", msbfs_look), kBool, 0, 0, nullptr},
+    {OPT_U32("scatter_variant", scatter_variant), kClamp, kOptMin, 2, nullptr},
+    {OPT_U32("adaptive", adaptive), kBool, 0, 0, nullptr},
+    {OPT_U32("resident_waves", resident_waves), kReject, 0, 1 << 20, "resident_waves out of range"},
+    {OPT_U32("start_horizon", start_horizon), kReject, 1, 1 << 20, "start_horizon out of range"},
+    {OPT_U32("soft_barrier", soft_barrier), kClamp, 0, kOptMax, nullptr},
+    {OPT_U32("defer_barrier", defer_barrier), kClamp, 0, kOptMax, nullptr},
+    {OPT_U32("rb_defer_table", rb_defer_table), kClamp, 0, 1ll << 31, nullptr},
+    {OPT_U32("dbg_repeat", dbg_repeat), kClamp, kOptMin, kOptMax, nullptr},
+    // 1: per-epoch counts of why updates did not commit; 2: + a per-update trace, dumped per epoch to $PPCSR_DIAG_DUMP
+    {OPT_U32("diag", diag), kClamp, 0, 2, nullptr},
+    {OPT_U32("rounds_per_sync", rounds_per_sync), kReject, 1, 4096, "rounds_per_sync out of range"},
+};
+#undef OPT_U32
+#undef OPT_U64
+
 int Engine::set_option(const char *key, int64_t value) {
   Impl &p = *p_;
   std::string k(key ? key : "");
+  for (const OptRow &r : kOptRows) {
+    if (k != r.key) continue;
+    const bool pow2 = value >= r.lo && !(value & (value - 1));
+    const bool ok = r.rule == kReject  ? value >= r.lo && value <= r.hi
+                  : r.rule == kPow2    ? pow2
+                  : r.rule == kPow2Or0 ? pow2 || value == 0
+                  : r.rule == kOneOf   ? value >= 0 && value < 63 && ((r.lo >> value) & 1)
+                                       : true;
+    if (!ok) return fail(PPCSR_EINVAL, r.msg);
+    int64_t s = value;
+    if (r.rule == kClamp) s = std::max(r.lo, std::min(value, r.hi));
+    if (r.rule == kPow2 || r.rule == kPow2Or0) s = std::min(value, r.hi);
+    if (r.rule == kBool) s = value != 0;
+    if (r.wide) *(uint64_t *)r.field(p) = (uint64_t)s;
+    else *(uint32_t *)r.field(p) = (uint32_t)s;
+    return PPCSR_OK;
+  }
   if (k == "max_horizon") {
     if (value < 1 || value > (1 << 20)) return fail(PPCSR_EINVAL, "max_horizon out of range");
     gpu::set_device(device_);
@@ -565,46 +614,10 @@ int Engine::set_option(const char *key, int64_t value) {
     p.init_horizon = (uint32_t)std::min<int64_t>(value, p.max_horizon);
     return PPCSR_OK;
   }
-  if (k == "mode") {
-    if (value != 0 && value != 1) return fail(PPCSR_EINVAL, "mode must be 0 (strict) or 1 (speculative)");
-    p.mode = (uint32_t)value;
-    return PPCSR_OK;
-  }
-  if (k == "epoch_ops") {
-    if (value < 1 || value > (1 << 24)) return fail(PPCSR_EINVAL, "epoch_ops out of range");
-    p.epoch_ops = (uint32_t)value;
-    return PPCSR_OK;
-  }
   if (k == "region_slots") {
     if (value < 1 || (value & (value - 1))) return fail(PPCSR_EINVAL, "region_slots must be a power of two");
-    p.region_slots = (uint32_t)value;
-    p.region_eff = 0;
-    return PPCSR_OK;
-  }
-  if (k == "region_wide") {
-    if (value < 1 || (value & (value - 1))) return fail(PPCSR_EINVAL, "region_wide must be a power of two");
-    p.region_wide = (uint32_t)value;
-    return PPCSR_OK;
-  }
-  if (k == "region_rare") {  // 0: off
-    if (value < 0 || (value & (value - 1))) return fail(PPCSR_EINVAL, "region_rare must be 0 or a power of two");
-    p.region_rare = (uint32_t)value;
-    return PPCSR_OK;
-  }
-  if (k == "region_rare_calm") {
-    p.region_rare_calm = (uint32_t)std::max<int64_t>(1, value);
-    return PPCSR_OK;
-  }
-  if (k == "region_rare_cpr") {
-    p.region_rare_cpr = (uint32_t)std::max<int64_t>(0, value);
-    return PPCSR_OK;
-  }
-  if (k == "region_rare_dist") {
-    p.region_rare_dist = (uint32_t)std::max<int64_t>(1, value);
-    return PPCSR_OK;
-  }
-  if (k == "region_calm") {
-    p.region_calm = (uint32_t)std::max<int64_t>(1, value);
+    p.pol.region_slots = (uint32_t)value;
+    p.pol.region_eff = 0;
     return PPCSR_OK;
   }
   if (k == "opt_horizon") {
@@ -616,68 +629,13 @@ int Engine::set_option(const char *key, int64_t value) {
     if (!p.adaptive) p.start_horizon = p.opt_horizon;
     return PPCSR_OK;
   }
-  if (k == "scatter_blocks") {
-    p.scatter_blocks = (uint32_t)std::max<int64_t>(64, value);
-    return PPCSR_OK;
-  }
-  if (k == "search_narrow") {  // 0: the literal binary walk only (what a structure add_node has corrupted falls back to)
-    p.v.g.narrow = value ? 1u : 0u;
-    return PPCSR_OK;
-  }
-  if (k == "small_batch") {
-    p.small_batch = value < 0 ? 0u : (uint32_t)value;
-    return PPCSR_OK;
-  }
-  if (k == "excl_in_wave") {
-    p.excl_in_wave = (uint32_t)std::max<int64_t>(64, value);
-    return PPCSR_OK;
-  }
-  if (k == "big_window") {  // <= kBigWindow: o_big is not launched at all (every window of a round is rebalanced by its own wave)
-    if (value < 64 || (value & (value - 1))) return fail(PPCSR_EINVAL, "big_window must be a power of two >= 64");
-    p.big_window = (uint32_t)std::min<int64_t>(value, 1 << 20);
-    return PPCSR_OK;
-  }
-  if (k == "big_min") {
-    p.big_min = (uint32_t)std::max<int64_t>(64, std::min<int64_t>(value, kBigWindow));
-    return PPCSR_OK;
-  }
-  if (k == "big_grid") {
-    p.big_grid = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(value, 256));
-    return PPCSR_OK;
-  }
   if (k == "rb_tile") {
     uint32_t t = 0;
     if (value > 0) for (t = 8; t < (uint32_t)value && t < kRbTile; t <<= 1) {}
     p.rb_tile = t;
     return PPCSR_OK;
   }
-  if (k == "rb_min_tiles") {
-    p.rb_min_tiles = value < 1 ? 1u : (uint32_t)value;
-    return PPCSR_OK;
-  }
-  if (k == "rb_inplace_lists") {  // (test hook: 1, 2, 4 or 8 ticket lists whatever the probe saw)
-    if (value != 1 && value != 2 && value != 4 && value != 8) return fail(PPCSR_EINVAL, "rb_inplace_lists must be 1, 2, 4 or 8");
-    p.ip_lists = (uint32_t)value;
-    return PPCSR_OK;
-  }
-  // batched-read sizes (test hooks, as rb_inplace_lists: they move the seams of the staging and of the gather blocks; the
-  // scratch they size is regrown by the next call that needs more)
-  if (k == "query_lookup_stage" || k == "query_gather_rows" || k == "query_gather_chunks" || k == "query_gather_stage") {
-    if (value < 1 || value > (1ll << 32)) return fail(PPCSR_EINVAL, "query sizes must be in [1, 2^32]");
-    uint64_t &f = k == "query_lookup_stage" ? p.q.lookup_stage
-                : k == "query_gather_rows" ? p.q.gather_rows
-                : k == "query_gather_chunks" ? p.q.gather_chunks : p.q.gather_stage;
-    f = (uint64_t)value;
-    return PPCSR_OK;
-  }
-  // snapshot hooks (test hooks as well): the workgroup cap of k_snap_sync_leaves / k_snap_sync_nodes, which moves their
-  // grid-stride seam down to small arrays, and the counting of what an incremental synchronisation copies
-  if (k == "snap_grid") {
-    if (value < 1 || value > 4096) return fail(PPCSR_EINVAL, "snap_grid must be in [1, 4096]");
-    p.snap_grid = (uint32_t)value;
-    return PPCSR_OK;
-  }
-  if (k == "snap_count") {
+  if (k == "snap_count") {  // snapshot hook (a test hook, like snap_grid): count what an incremental synchronisation copies
     if (value && !p.d_snapcnt) {
       gpu::set_device(device_);
       GCHK(gpu::dmalloc((void **)&p.d_snapcnt, 2 * sizeof(unsigned long long)));
@@ -689,42 +647,8 @@ int Engine::set_option(const char *key, int64_t value) {
     p.rb_inplace_cpw = value >= 16 ? 16u : (value >= 8 ? 8u : 0u);
     return PPCSR_OK;
   }
-  if (k == "rb_inplace_min") {
-    p.rb_inplace_min = value < 0 ? 0ull : (uint64_t)value;
-    return PPCSR_OK;
-  }
   if (k == "check_lanes") {
-    p.check_force = value < 0 ? -1 : (value ? 1 : 0);
-    return PPCSR_OK;
-  }
-  if (k == "rb_bench_upper") {
-    p.rb_bench_upper = value ? 1u : 0u;
-    return PPCSR_OK;
-  }
-  if (k == "rb_prefetch") {
-    p.rb_prefetch = value ? 1u : 0u;
-    return PPCSR_OK;
-  }
-  if (k == "msbfs_look") {
-    p.msbfs_look = value ? 1u : 0u;
-    return PPCSR_OK;
-  }
-  if (k == "scatter_variant") {
-    p.scatter_variant = value > 2 ? 2u : (uint32_t)value;
-    return PPCSR_OK;
-  }
-  if (k == "adaptive") {
-    p.adaptive = value != 0;
-    return PPCSR_OK;
-  }
-  if (k == "resident_waves") {
-    if (value < 0 || value > (1 << 20)) return fail(PPCSR_EINVAL, "resident_waves out of range");
-    p.resident_waves = (uint32_t)value;
-    return PPCSR_OK;
-  }
-  if (k == "start_horizon") {
-    if (value < 1 || value > (1 << 20)) return fail(PPCSR_EINVAL, "start_horizon out of range");
-    p.start_horizon = (uint32_t)value;
+    p.check.force = value < 0 ? -1 : (value ? 1 : 0);
     return PPCSR_OK;
   }
   if (k == "test_block_rebalance") {  // test hook: value = wstart << 32 | wlen; rebalances that window with the workgroup routine
@@ -756,47 +680,10 @@ int Engine::set_option(const char *key, int64_t value) {
     }
     return PPCSR_OK;
   }
-  if (k == "epoch_short") {
-    p.epoch_short = (uint32_t)std::max<int64_t>(64, value);
-    return PPCSR_OK;
-  }
-  if (k == "epoch_adapt") {
-    p.epoch_adapt = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 1024));
-    return PPCSR_OK;
-  }
-  if (k == "epoch_grow_after") {
-    p.epoch_grow_after = (uint32_t)std::max<int64_t>(1, value);
-    return PPCSR_OK;
-  }
-  if (k == "soft_barrier") {
-    p.soft_barrier = (uint32_t)std::max<int64_t>(0, value);
-    return PPCSR_OK;
-  }
-  if (k == "defer_barrier") {
-    p.defer_barrier = (uint32_t)std::max<int64_t>(0, value);
-    return PPCSR_OK;
-  }
-  if (k == "rb_defer_table") {
-    p.rb_defer_table = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 1ll << 31));
-    return PPCSR_OK;
-  }
-  if (k == "dbg_repeat") {
-    p.dbg_repeat = (uint32_t)value;
-    return PPCSR_OK;
-  }
-  if (k == "diag") {  // 1: per-epoch counts of why updates did not commit; 2: + a per-update trace, dumped per epoch to $PPCSR_DIAG_DUMP
-    p.diag = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 2));
-    return PPCSR_OK;
-  }
   if (k == "profile") {
     p.profile = value != 0;
     p.st.prof_plan_ms = p.st.prof_check_ms = p.st.prof_apply_ms = p.st.prof_compact_ms = 0;
     p.st.prof_launches = 0;
-    return PPCSR_OK;
-  }
-  if (k == "rounds_per_sync") {
-    if (value < 1 || value > 4096) return fail(PPCSR_EINVAL, "rounds_per_sync out of range");
-    p.rounds_per_sync = (uint32_t)value;
     return PPCSR_OK;
   }
   return fail(PPCSR_EINVAL, "unknown option " + k);
@@ -808,13 +695,7 @@ int Engine::apply_batch_host(const Op *ops, uint64_t n) {
   if (n == 0) return PPCSR_OK;
   if (!ops) return fail(PPCSR_EINVAL, "null ops");
   GCHK(gpu::set_device(device_));
-  if (n > p.ops_cap) {
-    if (p.d_ops) GPU_DFREE(p.d_ops);
-    p.d_ops = nullptr;
-    p.ops_cap = 0;
-    GCHK(gpu::dmalloc((void **)&p.d_ops, n * sizeof(Op)));
-    p.ops_cap = n;
-  }
+  GCHK_AS(grow_buf(&p.d_ops, &p.ops_cap, n), "gpu::dmalloc((void **)&p.d_ops, n * sizeof(Op))");
   auto t0 = std::chrono::steady_clock::now();
   GCHK(gpu::h2d(p.d_ops, ops, n * sizeof(Op), p.stream));
   GCHK(gpu::sync(p.stream));
@@ -865,8 +746,36 @@ int Engine::apply_batch_device(const Op *d_ops, uint64_t n) {
   return inplace_fault_check();
 }
 
+// option "profile", for both schedulers: an event in front of, between and behind the kernels of every round of a chunk
+// (`per_round` events a round), summed into the prof_*_ms columns once the chunk has been synchronised
+struct RoundProfile {
+  Engine::Impl &p;
+  const uint32_t per_round;
+  int reserve(uint32_t rounds) {  // (the runtime's error code)
+    if (!p.profile || p.events.size() >= (size_t)per_round * rounds) return 0;
+    const size_t old = p.events.size();
+    p.events.resize((size_t)per_round * rounds);
+    for (size_t i = old; i < p.events.size(); i++)
+      if (int e = p.events[i].init()) return e;
+    return 0;
+  }
+  void mark(uint32_t r, uint32_t k) { if (p.profile) p.events[per_round * r + k].record(p.stream); }
+  void sum(uint32_t rounds, bool compact) {  // compact: a fourth kernel (o_big) ran between events 3 and 4
+    if (!p.profile) return;
+    for (uint32_t r = 0; r < rounds; r++) {
+      gpu::Event *ev = &p.events[per_round * r];
+      p.st.prof_plan_ms += gpu::Event::elapsed_ms(ev[0], ev[1]);
+      p.st.prof_check_ms += gpu::Event::elapsed_ms(ev[1], ev[2]);
+      p.st.prof_apply_ms += gpu::Event::elapsed_ms(ev[2], ev[3]);
+      if (compact) p.st.prof_compact_ms += gpu::Event::elapsed_ms(ev[3], ev[4]);
+      p.st.prof_launches += 1;
+    }
+  }
+};
+
 int Engine::run_rounds(const Op *d_ops, uint64_t n) {
   Impl &p = *p_;
+  RoundProfile prof{p, 4};
   p.live_is_snap = false;
   if (p.round > 0xFFFF0000u) GCHK(reset_tags(p));  // reservation tags would wrap
   GCHK(ensure_plans(p));
@@ -897,11 +806,7 @@ int Engine::run_rounds(const Op *d_ops, uint64_t n) {
       a.stats = p.d_stats;
       a.min_horizon = p.min_horizon;
       const uint32_t blocks = (p.max_horizon + 3) / 4;
-      if (p.profile && p.events.size() < 4ull * p.rounds_per_sync) {
-        const size_t old = p.events.size();
-        p.events.resize(4ull * p.rounds_per_sync);
-        for (size_t i = old; i < p.events.size(); i++) GCHK(p.events[i].init());
-      }
+      GCHK_AS(prof.reserve(p.rounds_per_sync), "p.events[i].init()");
       // rounds in this chunk: at least one per `hor` pending updates (every strict round commits at least one update and
       // at most the horizon), capped by rounds_per_sync; short batches — the single-update API — get 1-2 rounds, not 32
       uint32_t chunk_rounds = p.rounds_per_sync;
@@ -912,25 +817,18 @@ int Engine::run_rounds(const Op *d_ops, uint64_t n) {
       }
       for (uint32_t r = 0; r < chunk_rounds; r++) {
         a.round = ++p.round;
-        if (p.profile) p.events[4 * r + 0].record(p.stream);
+        prof.mark(r, 0);
         GPU_LAUNCH(p.stream, k_plan, blocks, 256, a);
-        if (p.profile) p.events[4 * r + 1].record(p.stream);
+        prof.mark(r, 1);
         GPU_LAUNCH(p.stream, k_check, blocks, 256, a);
-        if (p.profile) p.events[4 * r + 2].record(p.stream);
+        prof.mark(r, 2);
         GPU_LAUNCH(p.stream, k_apply, blocks, 256, a);
-        if (p.profile) p.events[4 * r + 3].record(p.stream);
+        prof.mark(r, 3);
       }
       GCHK(gpu::d2h(p.h_ctl, p.d_ctl, sizeof(Control), p.stream));
       GCHK(gpu::sync(p.stream));
       GCHK(gpu::last_error());
-      if (p.profile) {
-        for (uint32_t r = 0; r < chunk_rounds; r++) {
-          p.st.prof_plan_ms += gpu::Event::elapsed_ms(p.events[4 * r + 0], p.events[4 * r + 1]);
-          p.st.prof_check_ms += gpu::Event::elapsed_ms(p.events[4 * r + 1], p.events[4 * r + 2]);
-          p.st.prof_apply_ms += gpu::Event::elapsed_ms(p.events[4 * r + 2], p.events[4 * r + 3]);
-          p.st.prof_launches += 1;
-        }
-      }
+      prof.sum(chunk_rounds, false);
       p.st.round_syncs++;
       if (c.error) return fail(PPCSR_EINTERNAL, "device-side error " + std::to_string(c.error));
       const uint32_t npar = (p.round + 1) & 1u;
@@ -961,65 +859,60 @@ static int snap_commit(Engine::Impl &p, Engine::Impl::Snap &sn);
 static int snap_rollback(Engine::Impl &p, Engine::Impl::Snap &sn, Engine::Impl::Snap &other);
 static bool snap_in_step(const Engine::Impl &p, const Engine::Impl::Snap &sn);
 
-// Speculative rounds (pma_kernels.h, second half): epochs of at most `epoch_ops` updates, each with a rollback
-// snapshot; a validation failure replays the epoch with the strict prefix rounds, an exclusive update ends the epoch.
-int Engine::run_speculative(const Op *d_ops, uint64_t n) {
-  Impl &p = *p_;
-  GCHK(ensure_plans(p));
-  // per-slot and carry arrays
-  if (p.hslot_cap < p.opt_horizon) {
-    if (p.d_status) GPU_DFREE(p.d_status);
-    p.d_status = nullptr;
-    p.hslot_cap = 0;
-    GCHK(gpu::dmalloc((void **)&p.d_status, ((uint64_t)p.opt_horizon + 64) * sizeof(uint32_t)));  // (+64: padded to the launch grids)
-    if (p.d_vdbg) GPU_DFREE(p.d_vdbg);
-    GCHK(gpu::dmalloc((void **)&p.d_vdbg, ((uint64_t)p.opt_horizon + 64) * 4 * sizeof(uint32_t)));
-    p.hslot_cap = p.opt_horizon;
-  }
-  // carry lists: by round parity, kStripes sub-lists each (a round's deferred updates can all come from workgroups of one XCD)
-  const uint64_t carry_need = (uint64_t)p.opt_horizon + 8;
-  if (p.carry_cap < carry_need) {
-    if (p.d_carry0) GPU_DFREE(p.d_carry0);
-    if (p.d_carry1) GPU_DFREE(p.d_carry1);
-    p.d_carry0 = p.d_carry1 = nullptr;
-    p.carry_cap = 0;
-    GCHK(gpu::dmalloc((void **)&p.d_carry0, kStripes * carry_need * sizeof(uint32_t)));
-    GCHK(gpu::dmalloc((void **)&p.d_carry1, kStripes * carry_need * sizeof(uint32_t)));
-    p.carry_cap = carry_need;
-  }
-  // big-window path: windows of up to kBigLeaves leaves (and big_window slots) stay inside the round
-  uint32_t bigw = p.big_window;
-  while (bigw > kBigWindow && (bigw >> p.v.g.sh) > dev::kBigLeaves) bigw >>= 1;
-  const bool use_big = bigw > p.big_min;
-  if (use_big) {
-    if (!p.d_jobs) GCHK(gpu::dmalloc((void **)&p.d_jobs, kBigJobs * sizeof(dev::BigJob)));
-    const uint64_t need = (uint64_t)p.big_grid * bigw;
-    if (p.bigscratch_cap < need) {
-      if (p.d_bigscratch) GPU_DFREE(p.d_bigscratch);
-      p.d_bigscratch = nullptr;
-      p.bigscratch_cap = 0;
-      GCHK(gpu::dmalloc((void **)&p.d_bigscratch, need * sizeof(Edge)));
-      p.bigscratch_cap = need;
-    }
-  }
-  if (p.diag >= 2) {
-    if (p.dg_cap < n) {
-      if (p.d_dg) GPU_DFREE(p.d_dg);
-      p.d_dg = nullptr;
-      p.dg_cap = 0;
-      GCHK(gpu::dmalloc((void **)&p.d_dg, n * 4 * sizeof(uint32_t)));
-      p.dg_cap = n;
-    }
-    GCHK(gpu::dset(p.d_dg, 0, n * 4 * sizeof(uint32_t), p.stream));
-  }
-  p.stamps_clean = false;  // (stream indices start over with every batch)
-  uint64_t e0 = 0;
-  uint64_t forced_e1 = 0;  // after a rollback: end the retried epoch right after the update that failed validation
+// One speculative batch and its open epoch: the steps of Engine::run_speculative and the state they hand to each other
+struct Engine::SpecRun {
+  Engine &eng;
+  Impl &p;
+  const Op *const d_ops;
+  const uint64_t n;
+  // the batch
+  uint32_t bigw = 0;  // big-window path: windows of up to kBigLeaves leaves (and big_window slots) stay inside the round
+  bool use_big = false;
+  uint64_t e0 = 0, e1 = 0;  // the epoch: updates [e0, e1) of the stream
+  uint64_t forced_e1 = 0;   // after a rollback: end the retried epoch right after the update that failed validation
   int retries = 0;
-  const uint32_t kEpochShort = p.epoch_short;
-  if (p.cur_epoch == 0 || p.cur_epoch > p.epoch_ops) p.cur_epoch = p.epoch_ops;
-  while (e0 < n) {
-    uint64_t e1 = std::min<uint64_t>(e0 + p.cur_epoch, n);
+  // the open epoch
+  bool from_snap = false;  // its rollback point is the user's snapshot, not the epoch snapshot
+  int rs = 0;              // OptArgs::regshift
+  bool open = false;
+  ChunkPlan ch;
+  OptArgs a{};  // of the chunk launched last
+  RoundProfile prof;
+
+  SpecRun(Engine &e, const Op *ops, uint64_t count) : eng(e), p(*e.p_), d_ops(ops), n(count), prof{*e.p_, 5} {}
+  int fail(int code, const std::string &msg) { return eng.fail(code, msg); }
+
+  int grow_scratch() {
+    // per-slot and carry arrays
+    const uint64_t slots = (uint64_t)p.opt_horizon + 64;  // (+64: padded to the launch grids)
+    GCHK_AS(grow_buf(&p.d_status, &p.status_cap, slots), "gpu::dmalloc((void **)&p.d_status, ((uint64_t)p.opt_horizon + 64) * sizeof(uint32_t))");
+    GCHK_AS(grow_buf(&p.d_vdbg, &p.vdbg_cap, slots * 4), "gpu::dmalloc((void **)&p.d_vdbg, ((uint64_t)p.opt_horizon + 64) * 4 * sizeof(uint32_t))");
+    // carry lists: by round parity, kStripes sub-lists each (a round's deferred updates can all come from workgroups of one XCD)
+    const uint64_t carry_need = (uint64_t)p.opt_horizon + 8;
+    if (p.carry_cap < carry_need) {
+      uint64_t c0 = 0, c1 = 0;
+      p.carry_cap = 0;
+      GCHK_AS(grow_buf(&p.d_carry0, &c0, kStripes * carry_need), "gpu::dmalloc((void **)&p.d_carry0, kStripes * carry_need * sizeof(uint32_t))");
+      GCHK_AS(grow_buf(&p.d_carry1, &c1, kStripes * carry_need), "gpu::dmalloc((void **)&p.d_carry1, kStripes * carry_need * sizeof(uint32_t))");
+      p.carry_cap = carry_need;
+    }
+    bigw = p.big_window;
+    while (bigw > kBigWindow && (bigw >> p.v.g.sh) > dev::kBigLeaves) bigw >>= 1;
+    use_big = bigw > p.big_min;
+    if (use_big) {
+      if (!p.d_jobs) GCHK(gpu::dmalloc((void **)&p.d_jobs, kBigJobs * sizeof(dev::BigJob)));
+      GCHK_AS(grow_buf(&p.d_bigscratch, &p.bigscratch_cap, (uint64_t)p.big_grid * bigw), "gpu::dmalloc((void **)&p.d_bigscratch, need * sizeof(Edge))");
+    }
+    if (p.diag >= 2) {  // (four words per update of the batch)
+      GCHK_AS(grow_buf(&p.d_dg, &p.dg_cap, n * 4), "gpu::dmalloc((void **)&p.d_dg, n * 4 * sizeof(uint32_t))");
+      GCHK(gpu::dset(p.d_dg, 0, n * 4 * sizeof(uint32_t), p.stream));
+    }
+    return PPCSR_OK;
+  }
+
+  // the next epoch [e0, e1): its rollback point, its control block, and the launch that opens it
+  int open_epoch() {
+    e1 = std::min<uint64_t>(e0 + p.pol.epoch_len(), n);
     if (forced_e1 > e0 && forced_e1 < e1) e1 = forced_e1;
     if (p.round > 0xFFFF0000u) GCHK(reset_tags(p));
     // rollback point of the epoch: the epoch snapshot catches up with what the previous epoch wrote (dirty tags) — a full
@@ -1027,7 +920,7 @@ int Engine::run_speculative(const Op *d_ops, uint64_t n) {
     // ... and none at all while the live state still equals the user's snapshot (restore() or snapshot() came last and nothing
     // has written since): that snapshot IS the rollback point.  The epoch snapshot stays where it was; the next epoch that
     // needs it catches up by the tags, with what the restore re-stamped among them
-    const bool from_snap = p.live_is_snap && snap_in_step(p, p.snap);
+    from_snap = p.live_is_snap && snap_in_step(p, p.snap);
     if (!from_snap) GCHK(snap_commit(p, p.esnap));
     OptCtl &c = *p.h_octl;
     memset(&c, 0, sizeof(c));
@@ -1049,201 +942,256 @@ int Engine::run_speculative(const Op *d_ops, uint64_t n) {
     c.viol_idx = kMax;
     c.skip_idx = kMax;
     c.skip_round = 0;
-    // grid of a chunk: wide enough for the adapted width to grow during the chunk (x1.25 per full-width round), narrow at the
-    // tail, never narrower than the carry list (a round plans the whole of it) and never wider than opt_horizon
-    auto chunk_grid = [&p](uint32_t width, uint64_t pending, uint64_t carry) {
-      uint32_t gh = p.opt_horizon;
-      const uint64_t want = std::max<uint64_t>(1024, 4ull * (width ? width : p.opt_horizon));
-      if (want < gh) gh = (uint32_t)want;
-      const uint64_t pend = (pending + 255) & ~255ull;
-      if (pend < gh) gh = (uint32_t)std::max<uint64_t>(pend, 256);
-      const uint64_t need = (carry + 255) & ~255ull;
-      if (gh < need) gh = (uint32_t)std::min<uint64_t>(need, p.opt_horizon);
-      return gh;
-    };
-    c.max_horizon = chunk_grid(c.cur_h[pp0], e1 - e0, 0);  // (the first chunk's: the device never chooses a horizon wider than the launched grid)
-    {
-      // one launch opens the epoch (k_epoch_begin).  Validation stamps hold 1 + the stream index of the latest committed
-      // toucher: what earlier epochs of this batch left is smaller than anything this epoch compares with, so they are
-      // cleared at the start of a batch and after a rollback only (the rolled-back commits must not look like later updates
-      // to the retried ones)
-      const uint64_t leaves = p.v.g.N >> p.v.g.sh, nv = (uint64_t)p.n_cap + 1;
-      const uint32_t clear = p.stamps_clean ? 0u : 1u;
-      // (the loops are grid-stride: the grid only bounds the stride — one 16-byte store per thread and array up to 2048 workgroups)
-      const uint64_t quads = clear ? std::max(leaves, nv) / 4 + 1 : kStatShards * sizeof(StatShard) / 16;
-      GPU_LAUNCH(p.stream, k_epoch_begin, (uint32_t)std::min<uint64_t>((quads + 255) / 256, 2048), 256, p.d_wstamp, p.d_rstamp, leaves, p.d_vws, p.d_vrs, nv,
-                 clear, (const StatShard *)p.d_stats, p.d_stats_snap, p.d_octl, c);
-      p.stamps_clean = true;
+    c.max_horizon = chunk_grid(p.opt_horizon, c.cur_h[pp0], e1 - e0, 0);  // (the first chunk's: the device never chooses a horizon wider than the launched grid)
+    // one launch opens the epoch (k_epoch_begin).  Validation stamps hold 1 + the stream index of the latest committed
+    // toucher: what earlier epochs of this batch left is smaller than anything this epoch compares with, so they are
+    // cleared at the start of a batch and after a rollback only (the rolled-back commits must not look like later updates
+    // to the retried ones)
+    const uint64_t leaves = p.v.g.N >> p.v.g.sh, nv = (uint64_t)p.n_cap + 1;
+    const uint32_t clear = p.stamps_clean ? 0u : 1u;
+    // (the loops are grid-stride: the grid only bounds the stride — one 16-byte store per thread and array up to 2048 workgroups)
+    const uint64_t quads = clear ? std::max(leaves, nv) / 4 + 1 : kStatShards * sizeof(StatShard) / 16;
+    GPU_LAUNCH(p.stream, k_epoch_begin, (uint32_t)std::min<uint64_t>((quads + 255) / 256, 2048), 256, p.d_wstamp, p.d_rstamp, leaves, p.d_vws, p.d_vrs, nv,
+               clear, (const StatShard *)p.d_stats, p.d_stats_snap, p.d_octl, c);
+    p.stamps_clean = true;
+    rs =p.pol.region_shift(p.v.g.logN);
+    ch.open_epoch(c.cur_h[pp0], e1 - e0);
+    p.check.open_epoch();
+    p.big.open_epoch();
+    open = true;
+    return PPCSR_OK;
+  }
+
+  // OptArgs of a chunk (everything but the round number), from the engine as it stands
+  void fill_args() {
+    a.v = p.v;
+    a.v.big_window = use_big ? bigw : kBigWindow;
+    a.big_min = p.big_min;
+    a.jobs = use_big ? p.d_jobs : (dev::BigJob *)nullptr;
+    a.bigscratch = p.d_bigscratch;
+    a.bigscratch_stride = bigw;
+    a.ops = d_ops;
+    a.plans = p.d_plans;
+    a.status = p.d_status;
+    a.vdbg = p.d_vdbg;
+    a.carry0 = p.d_carry0;
+    a.carry1 = p.d_carry1;
+    a.carry_cap = (uint32_t)p.carry_cap;
+    a.ctl = p.d_octl;
+    a.stats = p.d_stats;
+    a.regfail = p.d_regfail;
+    a.pfail = p.d_pfail;
+    a.wstamp = p.d_wstamp;
+    a.rstamp = p.d_rstamp;
+    a.vws = p.d_vws;
+    a.vrs = p.d_vrs;
+    a.dslot = p.d_dslot;
+    a.regshift = rs;
+    a.diag = p.diag;
+    a.defer_barrier = p.defer_barrier;
+    a.dbg = p.dbg_repeat;
+    a.dg = p.diag >= 2 ? p.d_dg : (uint32_t *)nullptr;
+    a.soft_barrier = p.soft_barrier ? p.soft_barrier : a.v.big_window / 2u;
+    // while the rare-rollback rule keeps regions wide, overtakers are kept off a growing window by the region rule itself and
+    // the soft barrier only costs commits (a config #4 partition alone: 156 -> 96 rounds, 19.6 -> 13.9 ms, still no rollback)
+    if (!p.soft_barrier && p.pol.rare_rule_on()) a.soft_barrier = 0x40000000u;
+  }
+
+  // one chunk of rounds, then the control block as the last of them left it (*p.h_octl); the per-chunk policies take their look
+  int launch_chunk() {
+    OptCtl &c = *p.h_octl;
+    fill_args();
+    // the round kernels come in two instantiations: without / with the diagnostics compiled in
+    const bool extras = p.diag != 0 || p.dbg_repeat != 0;
+    // grid sized for the horizon the device last reported (it can only shrink within a chunk when fresh
+    // updates run out; it never exceeds opt_horizon)
+    const uint32_t gh = chunk_grid(p.opt_horizon, ch.width, ch.pending, ch.carry);
+    const uint32_t blocks = (gh + 3) / 4;
+    if (gh != c.max_horizon) {  // the device must never choose a horizon larger than the launched grid
+      GCHK(gpu::h2d(&p.d_octl->max_horizon, &gh, sizeof(uint32_t), p.stream));
+      c.max_horizon = gh;
     }
-    int rs = 0;
-    if (p.region_eff < p.region_slots) p.region_eff = p.region_slots;
-    while ((p.region_eff >> rs) > (uint32_t)p.v.g.logN) rs++;
-    bool epoch_open = true;
-    uint32_t cur_width = c.cur_h[pp0];  // the adapted width the device last reported
-    uint64_t carry_now = 0;            // deferred updates waiting in the carry list
-    unsigned long long jobs_seen = 0, rounds_seen = 0, planned_seen = 0, long_seen = 0;  // OptCtl counters at the last look
-    // tail sizing of the round chunks: updates still pending and updates committed per round (measured on the last chunk)
-    uint64_t chunk_pending = e1 - e0;
-    double chunk_cpr = 0.9 * (double)std::min<uint64_t>(cur_width, e1 - e0);
-    unsigned long long prev_rounds = 0, prev_committed = 0;
-    uint32_t excl_cooldown = 0;  // chunks to keep short after an exclusive update (the launches behind it in its chunk are wasted)
-    while (epoch_open) {
-      OptArgs a;
-      a.v = p.v;
-      a.v.big_window = use_big ? bigw : kBigWindow;
-      a.big_min = p.big_min;
-      a.jobs = use_big ? p.d_jobs : (dev::BigJob *)nullptr;
-      a.bigscratch = p.d_bigscratch;
-      a.bigscratch_stride = bigw;
-      a.ops = d_ops;
-      a.plans = p.d_plans;
-      a.status = p.d_status;
-      a.vdbg = p.d_vdbg;
-      a.carry0 = p.d_carry0;
-      a.carry1 = p.d_carry1;
-      a.carry_cap = (uint32_t)p.carry_cap;
-      a.ctl = p.d_octl;
-      a.stats = p.d_stats;
-      a.regfail = p.d_regfail;
-      a.pfail = p.d_pfail;
-      a.wstamp = p.d_wstamp;
-      a.rstamp = p.d_rstamp;
-      a.vws = p.d_vws;
-      a.vrs = p.d_vrs;
-      a.dslot = p.d_dslot;
-      a.regshift = rs;
-      a.diag = p.diag;
-      a.defer_barrier = p.defer_barrier;
-      // the round kernels come in two instantiations: without / with the diagnostics compiled in
-      const bool extras = p.diag != 0 || p.dbg_repeat != 0;
-      a.dbg = p.dbg_repeat;
-      a.dg = p.diag >= 2 ? p.d_dg : (uint32_t *)nullptr;
-      a.soft_barrier = p.soft_barrier ? p.soft_barrier : a.v.big_window / 2u;
-      // while the rare-rollback rule keeps regions wide, overtakers are kept off a growing window by the region rule itself and
-      // the soft barrier only costs commits (a config #4 partition alone: 156 -> 96 rounds, 19.6 -> 13.9 ms, still no rollback)
-      if (!p.soft_barrier && p.region_rare_span && p.region_eff >= p.region_rare) a.soft_barrier = 0x40000000u;
-      // grid sized for the horizon the device last reported (it can only shrink within a chunk when fresh
-      // updates run out; it never exceeds opt_horizon)
-      const uint32_t gh = chunk_grid(cur_width, chunk_pending, carry_now);
-      const uint32_t blocks = (gh + 3) / 4;
-      if (gh != c.max_horizon) {  // the device must never choose a horizon larger than the launched grid
-        GCHK(gpu::h2d(&p.d_octl->max_horizon, &gh, sizeof(uint32_t), p.stream));
-        c.max_horizon = gh;
-      }
-      // rounds in this chunk: as many as rounds_per_sync while that many are needed, fewer at the tail of the epoch so
-      // that the stream is not padded with launches that find `done` set (each still costs ~2 us of dispatch)
-      uint32_t rounds = p.rounds_per_sync;
-      {
-        const double per_round = std::max(1.0, 0.85 * chunk_cpr);
-        const double est = (double)chunk_pending / per_round + 2.0;
-        if (est < (double)rounds) rounds = (uint32_t)std::max(2.0, est);
-      }
-      if (excl_cooldown) {
-        rounds = std::min<uint32_t>(rounds, 8u);
-        excl_cooldown--;
-      }
-      if (p.profile && p.events.size() < 5ull * rounds) {
-        const size_t oldn = p.events.size();
-        p.events.resize(5ull * rounds);
-        for (size_t i = oldn; i < p.events.size(); i++) GCHK(p.events[i].init());
-      }
-      p.live_is_snap = false;
-      for (uint32_t r = 0; r < rounds; r++) {
-        a.round = ++p.round;
-        if (p.profile) p.events[5 * r + 0].record(p.stream);
-        if (extras) GPU_LAUNCH(p.stream, o_plan_x, blocks, 256, a); else GPU_LAUNCH(p.stream, o_plan, blocks, 256, a);
-        if (p.profile) p.events[5 * r + 1].record(p.stream);
-        // (o_check: a LANE per update, one wave per workgroup; the diagnostics build keeps a wave per update)
-        if (extras) GPU_LAUNCH(p.stream, o_check_x, blocks, 256, a);
-        else if (p.check_force >= 0 ? p.check_force == 1 : p.check_lanes) GPU_LAUNCH(p.stream, o_check, (gh + kCkThreads - 1) / kCkThreads, kCkThreads, a);
-        else GPU_LAUNCH(p.stream, o_check_w, blocks, 256, a);
-        if (p.profile) p.events[5 * r + 2].record(p.stream);
-        if (extras) GPU_LAUNCH(p.stream, o_apply_x, blocks, 256, a); else GPU_LAUNCH(p.stream, o_apply, blocks, 256, a);
-        if (p.profile) p.events[5 * r + 3].record(p.stream);
-        if (use_big && p.big_on) GPU_LAUNCH(p.stream, o_big, p.big_grid, 1024, a);  // the round's queued big-window rebalances (profile: the 'compact' column)
-        if (p.profile) p.events[5 * r + 4].record(p.stream);
-      }
-      {  // the last round's outcome, recorded for the host (the next round's o_plan will find the same)
-        a.round = p.round + 1;
-        GPU_LAUNCH(p.stream, o_settle, 1, 64, a);
-      }
-      GCHK(gpu::d2h(p.h_octl, p.d_octl, sizeof(OptCtl), p.stream));
-      GCHK(gpu::sync(p.stream));
-      GCHK(gpu::last_error());
-      if (p.profile) {
-        for (uint32_t r = 0; r < rounds; r++) {
-          p.st.prof_plan_ms += gpu::Event::elapsed_ms(p.events[5 * r + 0], p.events[5 * r + 1]);
-          p.st.prof_check_ms += gpu::Event::elapsed_ms(p.events[5 * r + 1], p.events[5 * r + 2]);
-          p.st.prof_apply_ms += gpu::Event::elapsed_ms(p.events[5 * r + 2], p.events[5 * r + 3]);
-          if (use_big && p.big_on) p.st.prof_compact_ms += gpu::Event::elapsed_ms(p.events[5 * r + 3], p.events[5 * r + 4]);  // (o_big, when it is in)
-          p.st.prof_launches += 1;
-        }
-      }
-      p.st.round_syncs++;
-      if (c.error) return fail(PPCSR_EINTERNAL, "device-side error " + std::to_string(c.error));
-      {  // which o_check for the next chunk: see Impl::check_lanes.  The lane kernel counts what it had to leave to the wave
-         // (each such update costs its wave a serial ~5 us): above ~1 in 64 a wave per update from the start is faster.  From the
-         // wave kernel the way back is a trial chunk every so often.
-        const unsigned long long dp = c.planned - planned_seen, dl = c.long_checks - long_seen;
-        planned_seen = c.planned;
-        long_seen = c.long_checks;
-        if (p.check_lanes) {
-          if (dp >= 1024 && dl * 64ull > dp) {
-            p.check_lanes = false;
-            p.check_wave_chunks = 0;
-          }
-        } else if (++p.check_wave_chunks >= 24u) {
-          p.check_lanes = true;
-        }
-      }
-      if (use_big) {  // keep / drop the o_big launch: see Impl::big_on.  Kept while a stream queues a window every few rounds (an
-                      // empty launch costs ~4 us, a round that finds none where it needs one costs the rest of its chunk)
-        const unsigned long long dj = c.jobs_total - jobs_seen, dr = c.rounds - rounds_seen;
-        jobs_seen = c.jobs_total;
-        rounds_seen = c.rounds;
-        if (dr) p.big_rate = 0.5 * p.big_rate + 0.5 * (double)dj / (double)dr;  // queued windows per round, running mean
-        p.big_on = p.big_rate >= 1.0 / 12.0;
-      }
+    const uint32_t rounds = ch.next_rounds(p.rounds_per_sync);
+    GCHK_AS(prof.reserve(rounds), "p.events[i].init()");
+    p.live_is_snap = false;
+    const bool big_in = use_big && p.big.on;
+    for (uint32_t r = 0; r < rounds; r++) {
+      a.round = ++p.round;
+      prof.mark(r, 0);
+      if (extras) GPU_LAUNCH(p.stream, o_plan_x, blocks, 256, a); else GPU_LAUNCH(p.stream, o_plan, blocks, 256, a);
+      prof.mark(r, 1);
+      // (o_check: a LANE per update, one wave per workgroup; the diagnostics build keeps a wave per update)
+      if (extras) GPU_LAUNCH(p.stream, o_check_x, blocks, 256, a);
+      else if (p.check.use_lanes()) GPU_LAUNCH(p.stream, o_check, (gh + kCkThreads - 1) / kCkThreads, kCkThreads, a);
+      else GPU_LAUNCH(p.stream, o_check_w, blocks, 256, a);
+      prof.mark(r, 2);
+      if (extras) GPU_LAUNCH(p.stream, o_apply_x, blocks, 256, a); else GPU_LAUNCH(p.stream, o_apply, blocks, 256, a);
+      prof.mark(r, 3);
+      if (big_in) GPU_LAUNCH(p.stream, o_big, p.big_grid, 1024, a);  // the round's queued big-window rebalances (profile: the 'compact' column)
+      prof.mark(r, 4);
+    }
+    a.round = p.round + 1;  // the last round's outcome, recorded for the host (the next round's o_plan will find the same)
+    GPU_LAUNCH(p.stream, o_settle, 1, 64, a);
+    GCHK(gpu::d2h(p.h_octl, p.d_octl, sizeof(OptCtl), p.stream));
+    GCHK(gpu::sync(p.stream));
+    GCHK(gpu::last_error());
+    prof.sum(rounds, big_in);
+    p.st.round_syncs++;
+    if (c.error) return fail(PPCSR_EINTERNAL, "device-side error " + std::to_string(c.error));
+    p.check.after_chunk(c.planned, c.long_checks);
+    if (use_big) p.big.after_chunk(c.jobs_total, c.rounds);
+    return PPCSR_OK;
+  }
+
+  // the next chunk takes the epoch up where the last round that ran (c.book_round) left it: what the round after it would
+  // plan, by ITS parity
+  void resume() {
+    const OptCtl &c = *p.h_octl;
+    const uint32_t par = (c.book_round + 1u) & 1u;
+    ch.resume(c.cur_h[par], c.used[par], c.e1 - c.nf[par]);
+  }
+
+  // the last round that ran (c.book_round) queued windows and no o_big followed: run it now, forget the launches that
+  // found the flag, go on from the next round with the launch back in
+  int late_big() {
+    const uint32_t R = p.h_octl->book_round;
+    a.round = R;
+    p.h_octl->need_big = 0;
+    GCHK(gpu::h2d(&p.d_octl->need_big, &p.h_octl->need_big, sizeof(uint32_t), p.stream));  // (first: o_big stands back while a flag is up)
+    GPU_LAUNCH(p.stream, o_big, p.big_grid, 1024, a);
+    GCHK(gpu::sync(p.stream));
+    p.round = R;
+    resume();
+    return PPCSR_OK;
+  }
+
+  // option "diag": why the epoch's planned updates did not commit
+  void diag_report() const {
+    const OptCtl &c = *p.h_octl;
+    fprintf(stderr, "[ppcsr diag] epoch [%llu,%llu) %s after %llu rounds: committed %llu planned %llu | not committed because: excl-kind %llu, "
+            "behind-barrier %llu, dup %llu, W-W %llu, W-after-R %llu, R-after-W %llu, sentinel-read %llu, sentinel-move %llu, region %llu, "
+            "growth-zone %llu, stamp %llu\n",
+            (unsigned long long)e0, (unsigned long long)e1, c.violation ? "ROLLBACK" : (c.excl ? "exclusive" : "done"), c.rounds, c.committed,
+            c.planned, c.why[0], c.why[1], c.why[2], c.why[3], c.why[4], c.why[5], c.why[6], c.why[7], c.why[8], c.why[9], c.why[10]);
+  }
+  // diag >= 2: the epoch's per-update trace and its updates, appended to `path` (tools/diag_chains.py reads it)
+  int diag_dump(const char *path) {
+    const OptCtl &c = *p.h_octl;
+    const uint64_t cnt = e1 - e0;
+    std::vector<uint32_t> tr(cnt * 4);
+    std::vector<Op> hops(cnt);
+    GCHK(gpu::d2h(tr.data(), p.d_dg + 4 * e0, cnt * 4 * sizeof(uint32_t), p.stream));
+    GCHK(gpu::d2h(hops.data(), d_ops + e0, cnt * sizeof(Op), p.stream));
+    GCHK(gpu::sync(p.stream));
+    if (FILE *f = fopen(path, "ab")) {
+      const uint64_t hdr[4] = {e0, e1, c.rounds, c.violation ? 1ull : 0ull};
+      fwrite(hdr, sizeof(hdr), 1, f);
+      fwrite(tr.data(), sizeof(uint32_t), tr.size(), f);
+      fwrite(hops.data(), sizeof(Op), hops.size(), f);
+      fclose(f);
+    }
+    GCHK(gpu::dset(p.d_dg + 4 * e0, 0, cnt * 4 * sizeof(uint32_t), p.stream));  // (a retried epoch starts its trace over)
+    return PPCSR_OK;
+  }
+
+  // a later update was committed before an earlier one whose footprint then reached it: roll the epoch back
+  // and retry it cut right after that update (nothing can overtake the last update of an epoch); after
+  // repeated failures replay the epoch with the strict prefix rounds
+  int rollback() {
+    const OptCtl &c = *p.h_octl;
+    p.st.rollbacks++;
+    if (getenv("PPCSR_TRACE_EPOCH"))
+      fprintf(stderr, "[ppcsr] rollback: epoch [%llu,%llu) viol_idx=%u excl=%u later=%u after %llu rounds; kind=%u leaf=%u stamp=%u what=%u wleaf=[%u,%u] index=%u nr=%u\n",
+              (unsigned long long)e0, (unsigned long long)e1, c.viol_idx, c.excl, c.excl_later, c.rounds, c.viol_info[0],
+              c.viol_info[1], c.viol_info[2], c.viol_info[3], c.viol_info[4], c.viol_info[5], c.viol_info[6], c.viol_info[7]);
+    if (from_snap) {
+      // the epoch started from the user's snapshot: back to it, and the retried epoch starts from it again
+      GCHK(snap_rollback(p, p.snap, p.esnap));
+      p.live_is_snap = true;
+    } else {
+      GCHK(snap_rollback(p, p.esnap, p.snap));
+    }
+    p.stamps_clean = false;
+    GCHK(gpu::d2d(p.d_stats, p.d_stats_snap, kStatShards * sizeof(StatShard), p.stream));
+    p.st.wasted_rounds += c.rounds;  // (kept apart: `rounds` / `committed` / `planned` describe committed work only)
+    p.pol.after_rollback();
+    const uint64_t cut = (uint64_t)c.viol_idx + 1;
+    if (retries < 3 && c.viol_idx != kMax && cut > e0 && cut < e1) {
+      retries++;
+      forced_e1 = cut;
+    } else {
+      int rc = eng.run_rounds(d_ops + e0, e1 - e0);
+      if (rc != PPCSR_OK) return rc;
+      e0 = e1;
+      retries = 0;
+      forced_e1 = 0;
+    }
+    open = false;
+    return PPCSR_OK;
+  }
+
+  // an exclusive update ran inside the epoch and the epoch goes on.  The launches queued behind the update's discovery did
+  // nothing; the next round takes the number after the last round that ran (c.book_round), finds that round's words as they
+  // were, minus the barrier the exclusive update raised (or it would be discovered again), and commits the update's slot as
+  // nothing (K_SKIP)
+  int continue_after_exclusive() {
+    OptCtl &c = *p.h_octl;
+    const uint32_t R = c.book_round;
+    c.excl = 0;
+    c.skip_idx = c.excl_idx;
+    c.skip_round = R + 1u;
+    c.gbar[R % 3u] = ~0ull;
+    GCHK(gpu::h2d(&p.d_octl->excl, &c.excl, sizeof(uint32_t), p.stream));
+    GCHK(gpu::h2d(&p.d_octl->skip_idx, &c.skip_idx, 2 * sizeof(uint32_t), p.stream));
+    GCHK(gpu::h2d(&p.d_octl->gbar[R % 3u], &c.gbar[R % 3u], sizeof(unsigned long long), p.stream));
+    GCHK(gpu::sync(p.stream));  // (h_octl is the landing buffer of the next chunk's control block)
+    p.round = R;
+    resume();
+    ch.excl_cooldown = 4;
+    return PPCSR_OK;
+  }
+
+  // the epoch ended cleanly: its counters join the engine's, the policy learns from it
+  void end_clean() {
+    const OptCtl &c = *p.h_octl;
+    if (getenv("PPCSR_TRACE_EPOCH"))
+      fprintf(stderr, "[ppcsr] epoch [%llu,%llu) rounds=%llu planned=%llu committed=%llu\n", (unsigned long long)e0, (unsigned long long)e1, c.rounds,
+              c.planned, c.committed);
+    p.st.rounds += c.rounds;
+    p.st.committed += c.committed;
+    p.st.planned += c.planned;
+    p.pol.after_clean_epoch(e1 - e0, c.committed, c.rounds);
+    e0 = e1;
+    retries = 0;
+    open = false;
+    const uint32_t npar = (c.book_round + 1u) & 1u;
+    if (c.cur_h[npar]) p.start_horizon = c.cur_h[npar];  // keep the adapted width for the next epoch
+  }
+};
+
+// Speculative rounds (pma_kernels.h, second half): epochs of at most `epoch_ops` updates, each with a rollback
+// snapshot; a validation failure replays the epoch with the strict prefix rounds, an exclusive update ends the epoch.
+// The length of the epochs and the width of their regions: EpochPolicy (pma_epoch_policy.h).
+int Engine::run_speculative(const Op *d_ops, uint64_t n) {
+  Impl &p = *p_;
+  GCHK(ensure_plans(p));
+  SpecRun s(*this, d_ops, n);
+  int rc = s.grow_scratch();
+  if (rc != PPCSR_OK) return rc;
+  p.stamps_clean = false;  // (stream indices start over with every batch)
+  p.pol.begin_batch();
+  OptCtl &c = *p.h_octl;
+  while (s.e0 < n) {
+    if ((rc = s.open_epoch()) != PPCSR_OK) return rc;
+    while (s.open) {
+      if ((rc = s.launch_chunk()) != PPCSR_OK) return rc;
       if (c.need_big && !c.violation) {
-        // the last round that ran (c.book_round) queued windows and no o_big followed: run it now, forget the launches that
-        // found the flag, go on from the next round with the launch back in
-        const uint32_t R = c.book_round;
-        a.round = R;
-        p.h_octl->need_big = 0;
-        GCHK(gpu::h2d(&p.d_octl->need_big, &p.h_octl->need_big, sizeof(uint32_t), p.stream));  // (first: o_big stands back while a flag is up)
-        GPU_LAUNCH(p.stream, o_big, p.big_grid, 1024, a);
-        GCHK(gpu::sync(p.stream));
-        p.round = R;
-        const uint32_t np2 = (R + 1u) & 1u;
-        cur_width = c.cur_h[np2];
-        carry_now = c.used[np2];
-        chunk_pending = (uint64_t)c.used[np2] + (uint64_t)(c.e1 - c.nf[np2]);
+        if ((rc = s.late_big()) != PPCSR_OK) return rc;
         continue;
       }
-      if (p.diag && (c.violation || c.excl || c.done))
-        fprintf(stderr, "[ppcsr diag] epoch [%llu,%llu) %s after %llu rounds: committed %llu planned %llu | not committed because: excl-kind %llu, "
-                "behind-barrier %llu, dup %llu, W-W %llu, W-after-R %llu, R-after-W %llu, sentinel-read %llu, sentinel-move %llu, region %llu, "
-                "growth-zone %llu, stamp %llu\n",
-                (unsigned long long)e0, (unsigned long long)e1, c.violation ? "ROLLBACK" : (c.excl ? "exclusive" : "done"), c.rounds, c.committed,
-                c.planned, c.why[0], c.why[1], c.why[2], c.why[3], c.why[4], c.why[5], c.why[6], c.why[7], c.why[8], c.why[9], c.why[10]);
-      if (p.diag >= 2 && (c.violation || c.done) && getenv("PPCSR_DIAG_DUMP")) {
-        const uint64_t cnt = e1 - e0;
-        std::vector<uint32_t> tr(cnt * 4);
-        std::vector<Op> hops(cnt);
-        GCHK(gpu::d2h(tr.data(), p.d_dg + 4 * e0, cnt * 4 * sizeof(uint32_t), p.stream));
-        GCHK(gpu::d2h(hops.data(), d_ops + e0, cnt * sizeof(Op), p.stream));
-        GCHK(gpu::sync(p.stream));
-        if (FILE *f = fopen(getenv("PPCSR_DIAG_DUMP"), "ab")) {
-          const uint64_t hdr[4] = {e0, e1, c.rounds, c.violation ? 1ull : 0ull};
-          fwrite(hdr, sizeof(hdr), 1, f);
-          fwrite(tr.data(), sizeof(uint32_t), tr.size(), f);
-          fwrite(hops.data(), sizeof(Op), hops.size(), f);
-          fclose(f);
-        }
-        GCHK(gpu::dset(p.d_dg + 4 * e0, 0, cnt * 4 * sizeof(uint32_t), p.stream));  // (a retried epoch starts its trace over)
-      }
-      // (after o_settle: what the next round would plan, by ITS parity)
-      const uint32_t npar = (c.book_round + 1u) & 1u;
+      if (p.diag && (c.violation || c.excl || c.done)) s.diag_report();
+      const char *dump = (p.diag >= 2 && (c.violation || c.done)) ? getenv("PPCSR_DIAG_DUMP") : nullptr;
+      if (dump && (rc = s.diag_dump(dump)) != PPCSR_OK) return rc;
       // An exclusive update runs now, alone, in the middle of the epoch: it is the lowest pending update, so it sees exactly
       // the state sequential execution gives it unless a LATER update was committed earlier on something it reads or
       // writes — validated with the stamps like every other update (k_exclusive, XValid).  Only a resize (double_list /
@@ -1251,9 +1199,8 @@ int Engine::run_speculative(const Op *d_ops, uint64_t n) {
       // and ends the epoch; everything else continues it: the update's slot commits as nothing in the next round (K_SKIP).
       bool excl_resized = false;
       if (c.excl && !c.violation) {
-        const uint64_t g = c.excl_idx;
         bool viol = false;
-        int rc = run_exclusive(Op{0, 0, 0}, 0, d_ops, (uint32_t)g, &viol, &excl_resized, c.excl_later != 0);
+        rc = run_exclusive(Op{0, 0, 0}, 0, d_ops, c.excl_idx, &viol, &excl_resized, c.excl_later != 0);
         if (rc != PPCSR_OK) return rc;
         if (viol) {
           c.violation = 1;
@@ -1261,115 +1208,21 @@ int Engine::run_speculative(const Op *d_ops, uint64_t n) {
         }
       }
       if (c.violation) {
-        // a later update was committed before an earlier one whose footprint then reached it: roll the epoch back
-        // and retry it cut right after that update (nothing can overtake the last update of an epoch); after
-        // repeated failures replay the epoch with the strict prefix rounds
-        p.st.rollbacks++;
-        if (getenv("PPCSR_TRACE_EPOCH"))
-          fprintf(stderr, "[ppcsr] rollback: epoch [%llu,%llu) viol_idx=%u excl=%u later=%u after %llu rounds; kind=%u leaf=%u stamp=%u what=%u wleaf=[%u,%u] index=%u nr=%u\n",
-                  (unsigned long long)e0, (unsigned long long)e1, c.viol_idx, c.excl, c.excl_later, c.rounds, c.viol_info[0],
-                  c.viol_info[1], c.viol_info[2], c.viol_info[3], c.viol_info[4], c.viol_info[5], c.viol_info[6], c.viol_info[7]);
-        if (from_snap) {
-          // the epoch started from the user's snapshot: back to it, and the retried epoch starts from it again
-          GCHK(snap_rollback(p, p.snap, p.esnap));
-          p.live_is_snap = true;
-        } else {
-          GCHK(snap_rollback(p, p.esnap, p.snap));
-        }
-        p.stamps_clean = false;
-        GCHK(gpu::d2d(p.d_stats, p.d_stats_snap, kStatShards * sizeof(StatShard), p.stream));
-        p.st.wasted_rounds += c.rounds;  // (kept apart: `rounds` / `committed` / `planned` describe committed work only)
-        uint32_t short_eff = kEpochShort;
-        p.grow_eff = p.epoch_grow_after;
-        if (p.epoch_adapt) {
-          const double D = (double)std::min<uint64_t>(p.since_rollback, 64ull * kEpochShort);
-          // (running mean with a fast attack downwards: a stream that starts to roll back often is recognised at once)
-          p.rb_dist = p.rb_dist < 0 ? 64.0 * kEpochShort : (D < p.rb_dist ? 0.25 * p.rb_dist + 0.75 * D : 0.5 * p.rb_dist + 0.5 * D);
-          p.since_rollback = 0;
-          uint32_t q = 2048;
-          while (2ull * q <= (uint64_t)(p.rb_dist / (double)p.epoch_adapt) && 2ull * q <= kEpochShort) q *= 2;
-          short_eff = std::min<uint32_t>(kEpochShort, q);
-          if (short_eff < kEpochShort) p.grow_eff = std::max<uint32_t>(p.epoch_grow_after, 4u);
-        }
-        p.cur_epoch = std::min<uint32_t>(p.cur_epoch, std::min<uint32_t>(p.epoch_ops, short_eff));
-        p.epoch_clean = 0;
-        {
-          const bool rare = p.epoch_adapt && p.region_rare && p.rb_dist >= (double)p.region_rare_dist && p.cpr_mean >= (double)p.region_rare_cpr;
-          p.region_eff = std::max(p.region_slots, rare ? std::max(p.region_wide, p.region_rare) : p.region_wide);
-          p.region_rare_span = rare ? (uint64_t)(p.region_rare_calm * p.rb_dist) : 0;
-        }
-        p.region_clean = 0;
-        const uint64_t cut = (uint64_t)c.viol_idx + 1;
-        if (retries < 3 && c.viol_idx != kMax && cut > e0 && cut < e1) {
-          retries++;
-          forced_e1 = cut;
-        } else {
-          int rc = run_rounds(d_ops + e0, e1 - e0);
-          if (rc != PPCSR_OK) return rc;
-          e0 = e1;
-          retries = 0;
-          forced_e1 = 0;
-        }
-        epoch_open = false;
+        if ((rc = s.rollback()) != PPCSR_OK) return rc;
       } else if (c.excl && excl_resized) {
         p.st.rounds += c.rounds;
         p.st.committed += c.committed + 1;
         p.st.planned += c.planned;
-        e0 = (uint64_t)c.excl_idx + 1;
-        retries = 0;
-        epoch_open = false;
+        s.e0 = (uint64_t)c.excl_idx + 1;
+        s.retries = 0;
+        s.open = false;
       } else if (c.excl) {
-        // the epoch goes on.  The launches queued behind the update's discovery did nothing; the next round takes the number
-        // after the last round that ran (c.book_round), finds that round's words as they were, minus the barrier the
-        // exclusive update raised (or it would be discovered again), and commits the update's slot as nothing (K_SKIP)
-        const uint32_t R = c.book_round;
-        p.h_octl->excl = 0;
-        p.h_octl->skip_idx = c.excl_idx;
-        p.h_octl->skip_round = R + 1u;
-        p.h_octl->gbar[R % 3u] = ~0ull;
-        GCHK(gpu::h2d(&p.d_octl->excl, &p.h_octl->excl, sizeof(uint32_t), p.stream));
-        GCHK(gpu::h2d(&p.d_octl->skip_idx, &p.h_octl->skip_idx, 2 * sizeof(uint32_t), p.stream));
-        GCHK(gpu::h2d(&p.d_octl->gbar[R % 3u], &p.h_octl->gbar[R % 3u], sizeof(unsigned long long), p.stream));
-        GCHK(gpu::sync(p.stream));  // (h_octl is the landing buffer of the next chunk's control block)
-        p.round = R;
-        cur_width = c.cur_h[npar];
-        carry_now = c.used[npar];
-        chunk_pending = (uint64_t)c.used[npar] + (uint64_t)(c.e1 - c.nf[npar]);
-        excl_cooldown = 4;
+        if ((rc = s.continue_after_exclusive()) != PPCSR_OK) return rc;
       } else if (c.done) {
-        if (getenv("PPCSR_TRACE_EPOCH"))
-          fprintf(stderr, "[ppcsr] epoch [%llu,%llu) rounds=%llu planned=%llu committed=%llu\n", (unsigned long long)e0, (unsigned long long)e1, c.rounds,
-                  c.planned, c.committed);
-        p.st.rounds += c.rounds;
-        p.st.committed += c.committed;
-        p.st.planned += c.planned;
-        p.since_rollback += e1 - e0;
-        if (c.rounds) {
-          const double cpr = (double)c.committed / (double)c.rounds;
-          p.cpr_mean = p.cpr_mean < 0 ? cpr : 0.75 * p.cpr_mean + 0.25 * cpr;
-        }
-        e0 = e1;
-        retries = 0;
-        epoch_open = false;
-        if (p.region_eff != p.region_slots) {
-          ++p.region_clean;
-          if (p.region_rare_span ? p.since_rollback >= p.region_rare_span : p.region_clean >= p.region_calm) {
-            p.region_eff = p.region_slots;
-            p.region_rare_span = 0;
-          }
-        }
-        if (++p.epoch_clean >= std::max(p.grow_eff, p.epoch_grow_after)) {
-          p.cur_epoch = (uint32_t)std::min<uint64_t>(p.epoch_ops, 2ull * p.cur_epoch);
-          p.epoch_clean = 0;
-        }
-        if (c.cur_h[npar]) p.start_horizon = c.cur_h[npar];  // keep the adapted width for the next epoch
+        s.end_clean();
       } else {
-        cur_width = c.cur_h[npar];
-        carry_now = c.used[npar];
-        chunk_pending = (uint64_t)c.used[npar] + (uint64_t)(c.e1 - c.nf[npar]);
-        if (c.rounds > prev_rounds) chunk_cpr = (double)(c.committed - prev_committed) / (double)(c.rounds - prev_rounds);
-        prev_rounds = c.rounds;
-        prev_committed = c.committed;
+        s.resume();
+        s.ch.measured(c.rounds, c.committed);
       }
     }
   }
@@ -1473,26 +1326,11 @@ int Engine::recheck_ranges() {
 }
 
 int Engine::ensure_scratch(uint64_t nleaves) {
-  Impl &p = *p_;
-  if (nleaves > p.rank_cap) {
-    if (p.d_rank) GPU_DFREE(p.d_rank);
-    p.d_rank = nullptr;
-    p.rank_cap = 0;
-    GCHK(gpu::dmalloc((void **)&p.d_rank, nleaves * sizeof(uint32_t)));
-    p.rank_cap = nleaves;
-  }
+  GCHK_AS(grow_buf(&p_->d_rank, &p_->rank_cap, nleaves), "gpu::dmalloc((void **)&p.d_rank, nleaves * sizeof(uint32_t))");
   return ensure_tiles((nleaves + kScanTile - 1) / kScanTile);
 }
-
 int Engine::ensure_tiles(uint64_t ntiles) {
-  Impl &p = *p_;
-  if (ntiles > p.tiles_cap) {
-    if (p.d_tiles) GPU_DFREE(p.d_tiles);
-    p.d_tiles = nullptr;
-    p.tiles_cap = 0;
-    GCHK(gpu::dmalloc((void **)&p.d_tiles, ntiles * sizeof(uint32_t)));
-    p.tiles_cap = ntiles;
-  }
+  GCHK_AS(grow_buf(&p_->d_tiles, &p_->tiles_cap, ntiles), "gpu::dmalloc((void **)&p.d_tiles, ntiles * sizeof(uint32_t))");
   return PPCSR_OK;
 }
 
@@ -1666,13 +1504,8 @@ int Engine::big_redistribute(uint64_t wstart, uint64_t wlen, bool sync) {
     }
   }
   const uint64_t need = whole ? v.g.N : wlen;
-  if (whole ? (p.scratch_cap != need) : (p.scratch_cap < need)) {  // a swapped-in buffer must be exactly N slots
-    if (p.d_scratch) GPU_DFREE(p.d_scratch);
-    p.d_scratch = nullptr;
-    p.scratch_cap = 0;
-    GCHK(gpu::dmalloc((void **)&p.d_scratch, need * sizeof(Edge)));
-    p.scratch_cap = need;
-  }
+  if (whole && p.scratch_cap != need) p.scratch_cap = 0;  // a swapped-in buffer must be exactly N slots: a larger one is replaced too
+  GCHK_AS(grow_buf(&p.d_scratch, &p.scratch_cap, need), "gpu::dmalloc((void **)&p.d_scratch, need * sizeof(Edge))");
   if (fused) {
     rc = rebalance_fused(v, v.items, wstart, wlen, v.g.sh, v.leafcnt + leaf_lo, true, wstart, wlen, p.d_scratch, wstart, v.leafcnt, 0);
     if (rc != PPCSR_OK) return rc;
@@ -1780,13 +1613,7 @@ int Engine::get_neighbourhood(int src, int *out, uint64_t cap, uint64_t *count) 
   *count = 0;
   if (src < 0 || (uint64_t)src >= n()) return PPCSR_OK;  // reference returns an empty vector (PCSR.cpp:903)
   GCHK(gpu::set_device(device_));
-  if (cap > p.nbr_cap) {
-    if (p.d_nbr) GPU_DFREE(p.d_nbr);
-    p.d_nbr = nullptr;
-    p.nbr_cap = 0;
-    GCHK(gpu::dmalloc((void **)&p.d_nbr, cap * sizeof(int)));
-    p.nbr_cap = cap;
-  }
+  GCHK_AS(grow_buf(&p.d_nbr, &p.nbr_cap, cap), "gpu::dmalloc((void **)&p.d_nbr, cap * sizeof(int))");
   GPU_LAUNCH(p.stream, k_neighbourhood, 1, 64, p.v, (uint32_t)src, (out && cap) ? p.d_nbr : (int *)nullptr, cap, p.d_total);
   GCHK(gpu::d2h(p.h_total, p.d_total, sizeof(unsigned long long), p.stream));
   GCHK(gpu::sync(p.stream));
@@ -1807,18 +1634,6 @@ int Engine::read_neighbourhood(int src) {
 // ---- batched reads (pma_query.h) -----------------------------------------------------------------------------------
 // staging of the host-buffer calls and the block sizes of a gather (Impl::Query: lookup_stage, gather_rows, gather_chunks,
 // gather_stage): no allocation grows with the number of queries
-
-// (re)allocate a device buffer to hold `need` elements; the old contents are not kept
-template <class T>
-static int grow_buf(T **b, uint64_t *cap, uint64_t need) {
-  if (need <= *cap && *b) return 0;
-  if (*b) gpu::dfree(*b);
-  *b = nullptr;
-  *cap = 0;
-  const int e = gpu::dmalloc((void **)b, need * sizeof(T));
-  if (e == 0) *cap = need;
-  return e;
-}
 
 // persistent grid of about `resident_waves` waves (the emulator reports none: a few workgroups) for `work` wave-sized items
 static uint32_t query_blocks(const Engine::Impl &p, uint64_t work) {
@@ -1870,14 +1685,7 @@ int Engine::lookup_edges(const uint32_t *src, const uint32_t *dst, uint64_t nq, 
     GPU_LAUNCH(p.stream, k_lookup_edges, query_blocks(p, (nq + 63) / 64), 256, p.v, src, dst, nq, values);
   } else {
     const uint64_t stage = std::min(nq, p.q.lookup_stage);
-    if (stage > p.q.lookup_cap) {
-      uint64_t c0 = p.q.lookup_cap, c1 = p.q.lookup_cap, c2 = p.q.lookup_cap;
-      if (grow_buf(&p.q.src, &c0, stage) || grow_buf(&p.q.dst, &c1, stage) || grow_buf(&p.q.val, &c2, stage)) {
-        p.q.lookup_cap = 0;
-        return fail(PPCSR_ENOMEM, "lookup_edges: staging");
-      }
-      p.q.lookup_cap = stage;
-    }
+    if (grow_bufs(&p.q.lookup_cap, stage, &p.q.src, &p.q.dst, &p.q.val)) return fail(PPCSR_ENOMEM, "lookup_edges: staging");
     for (uint64_t i0 = 0; i0 < nq; i0 += stage) {
       const uint64_t m = std::min(stage, nq - i0);
       GCHK(gpu::h2d(p.q.src, src + i0, m * sizeof(uint32_t), p.stream));
@@ -1915,12 +1723,7 @@ int Engine::gather_prepare(const uint32_t *q, uint64_t kb, uint64_t *kt, uint64_
   }
   if (chunks + 1 > g.chunk_cap) {
     const uint64_t need = std::max<uint64_t>(chunks + 1, 1024);
-    uint64_t c1 = g.chunk_cap, c2 = g.chunk_cap, c3 = g.chunk_cap;
-    if (grow_buf(&g.crow, &c1, need) || grow_buf(&g.ccnt, &c2, need) || grow_buf(&g.ooff, &c3, need)) {
-      g.chunk_cap = 0;
-      return fail(PPCSR_ENOMEM, "gather: chunk arrays");
-    }
-    g.chunk_cap = need;
+    if (grow_bufs(&g.chunk_cap, need, &g.crow, &g.ccnt, &g.ooff)) return fail(PPCSR_ENOMEM, "gather: chunk arrays");
   }
   if (chunks) {
     GCHK(gpu::dset(g.crow, 0, chunks * sizeof(uint32_t), p.stream));
@@ -1946,29 +1749,10 @@ int Engine::gather_neighbourhoods(const uint32_t *vertices, uint64_t k, uint64_t
   Impl::Query &g = p.q;
   GCHK(gpu::set_device(device_));
   const bool want = dests != nullptr || values != nullptr;
-  if (k) {
-    uint64_t c0 = g.rows_cap, c1 = g.rows_cap, c2 = g.rows_cap, c3 = g.rows_cap, c4 = g.rows_cap, c5 = g.rows_cap;
-    const uint64_t need = std::min(k, g.gather_rows) + 1;
-    if (need > g.rows_cap) {
-      if (grow_buf(&g.q, &c0, need) || grow_buf(&g.lo, &c1, need) || grow_buf(&g.len, &c2, need) || grow_buf(&g.nch, &c3, need) ||
-          grow_buf(&g.choff, &c4, need) || grow_buf(&g.rows, &c5, need)) {
-        g.rows_cap = 0;
-        return fail(PPCSR_ENOMEM, "gather: row arrays");
-      }
-      g.rows_cap = need;
-    }
-  }
-  if (want && !on_device && cap) {
-    uint64_t c0 = g.stage_cap, c1 = g.stage_cap;
-    const uint64_t need = std::min(cap, g.gather_stage);
-    if (need > g.stage_cap) {
-      if (grow_buf(&g.sdst, &c0, need) || grow_buf(&g.sval, &c1, need)) {
-        g.stage_cap = 0;
-        return fail(PPCSR_ENOMEM, "gather: output staging");
-      }
-      g.stage_cap = need;
-    }
-  }
+  if (k && grow_bufs(&g.rows_cap, std::min(k, g.gather_rows) + 1, &g.q, &g.lo, &g.len, &g.nch, &g.choff, &g.rows))
+    return fail(PPCSR_ENOMEM, "gather: row arrays");
+  if (want && !on_device && cap && grow_bufs(&g.stage_cap, std::min(cap, g.gather_stage), &g.sdst, &g.sval))
+    return fail(PPCSR_ENOMEM, "gather: output staging");
   uint64_t base = 0;  // edges of the rows before the block
   for (uint64_t i0 = 0; i0 < k;) {
     const uint64_t kb = std::min(k - i0, g.gather_rows);
@@ -2037,13 +1821,8 @@ int Engine::scan_count(Engine *part, uint32_t *tile_out, uint64_t *ntiles_out) {
   const uint64_t N = p.v.g.N, nchunks = (N + 63) / 64;
   bool fresh_state = (p.scan_nchunks != nchunks);  // the sentinel counts are laid out (and left zeroed) per array size
   p.scan_nchunks = nchunks;
-  if (p.scan_state_cap < 2 * nchunks) {
-    if (p.d_scan_state) GPU_DFREE(p.d_scan_state);
-    p.d_scan_state = nullptr;
-    p.scan_state_cap = 0;
-    GCHK(gpu::dmalloc((void **)&p.d_scan_state, 2 * nchunks * sizeof(uint32_t) + 64));
-    p.scan_state_cap = 2 * nchunks;
-  }
+  // (two u32 per chunk and 64 bytes of padding: nchunks + 8 of the buffer's 8-byte words)
+  GCHK_AS(grow_buf(&p.d_scan_state, &p.scan_state_cap, nchunks + 8), "gpu::dmalloc((void **)&p.d_scan_state, 2 * nchunks * sizeof(uint32_t) + 64)");
   uint32_t *d_cs = reinterpret_cast<uint32_t *>(p.d_scan_state), *d_cc = d_cs + nchunks;
   // tile of chunks per workgroup: as large as the workgroup while the array still yields thousands of tiles
   uint32_t tile = 256;

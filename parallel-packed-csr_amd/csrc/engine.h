@@ -229,6 +229,7 @@ class Engine {
 
  private:
   struct ConsumerScope;  // engine_consumers.cc
+  struct SpecRun;        // engine.cc: the steps of run_speculative
   Impl *p_;
   int device_ = 0;
   std::string err_;
