@@ -1196,30 +1196,22 @@ struct PlanRegs {
 PMA_DEV void store_plan_header(Plan *plan, uint32_t kind, uint32_t index, uint32_t gap, uint32_t wstart, uint32_t wlen, uint32_t wl, uint32_t wh,
                                uint32_t mv_lo, uint32_t mv_hi, uint32_t sleaf_b, uint32_t sleaf_e, uint32_t acalls, uint32_t aslots, uint32_t nr,
                                uint32_t nlong, uint32_t sdep, uint32_t idx, const Op &op) {
-  uint32_t w = 0;
-  w = wv::setlane<PW_KIND>(w, kind);
-  w = wv::setlane<PW_INDEX>(w, index);
-  w = wv::setlane<PW_GAP>(w, gap);
-  w = wv::setlane<PW_WSTART>(w, wstart);
-  w = wv::setlane<PW_WLEN>(w, wlen);
-  w = wv::setlane<PW_WLEAF_LO>(w, wl);
-  w = wv::setlane<PW_WLEAF_HI>(w, wh);
-  w = wv::setlane<PW_MV_LO>(w, mv_lo);
-  w = wv::setlane<PW_MV_HI>(w, mv_hi);
-  w = wv::setlane<PW_SLEAF_B>(w, sleaf_b);
-  w = wv::setlane<PW_SLEAF_E>(w, sleaf_e);
-  w = wv::setlane<PW_ALG>(w, (acalls << 28) | aslots);
-  w = wv::setlane<PW_NR>(w, nr);
-  w = wv::setlane<PW_NLONG>(w, nlong);
-  w = wv::setlane<PW_SDEP>(w, sdep);
-  w = wv::setlane<PW_IDX>(w, idx);
-  w = wv::setlane<PW_SRC>(w, op.src);
-  w = wv::setlane<PW_DST>(w, op.dst);
-  w = wv::setlane<PW_OP>(w, op.op);
-  if (wv::lane() < (int)PW_HEADER_WORDS) reinterpret_cast<uint32_t *>(plan)[wv::lane()] = w;
+  // (two interleaved halves, four words per block: see wv::setlanes — written one word at a time into one register the 19
+  //  fields were 16 pads, one scalar issue slot each)
+  uint32_t wa = 0, wb = 0;
+  wa = wv::setlanes<PW_KIND, PW_INDEX, PW_GAP, PW_WSTART>(wa, kind, index, gap, wstart);
+  wb = wv::setlanes<PW_WLEN, PW_WLEAF_LO, PW_WLEAF_HI, PW_MV_LO>(wb, wlen, wl, wh, mv_lo);
+  wa = wv::setlanes<PW_MV_HI, PW_SLEAF_B, PW_SLEAF_E, PW_ALG>(wa, mv_hi, sleaf_b, sleaf_e, (acalls << 28) | aslots);
+  wb = wv::setlanes<PW_NR, PW_NLONG, PW_SDEP, PW_IDX>(wb, nr, nlong, sdep, idx);
+  wa = wv::setlanes<PW_SRC, PW_DST, PW_OP, PW_PAD>(wa, op.src, op.dst, op.op, 0u);
+  if (wv::lane() < (int)PW_HEADER_WORDS) reinterpret_cast<uint32_t *>(plan)[wv::lane()] = wa | wb;
 }
-// op, idx (the update's stream index): wave-uniform
-PMA_DEV PlanRegs plan_op(const View &v, const Op op, Plan *plan, uint32_t idx) {
+// op, idx (the update's stream index): wave-uniform.  EXTRAS / dbg: the diagnostics build of o_plan executes a part of the plan twice
+// (OptArgs::dbg: PD_INSERT, PD_SENTINELS, PD_STORE), from an input the compiler cannot see through — the SQ counters of two runs
+// give that part's dynamic cost.  Without EXTRAS the loops below run once and are no code.
+enum PlanDbg : uint32_t { PD_INSERT = 8u, PD_SENTINELS = 16u, PD_STORE = 32u };
+template <bool EXTRAS = false>
+PMA_DEV PlanRegs plan_op(const View &v, const Op op, Plan *plan, uint32_t idx, uint32_t dbg = 0) {
   const int lane = wv::lane();
   const Geometry &g = v.g;
   RangeRec rr;
@@ -1290,13 +1282,17 @@ PMA_DEV PlanRegs plan_op(const View &v, const Op op, Plan *plan, uint32_t idx) {
         kind = K_DUP;
         wl = wh = leaf;
       } else {
-        const uint32_t gap_right = occupied ? find_gap_right(v, index + 1, kMaxSlide, gmask, gw) : index;
+        uint32_t gap_right = index;
         InsertPlan ip;
-        {
-          const RangeRec rr0 = rr;
-          if (!plan_insert_first(v, index, occupied, c_leaf, gap_right, rr, v.big_window, &lcache, &ip)) {
+        const RangeRec rr0 = rr;
+        for (int rep = (EXTRAS && (dbg & PD_INSERT)) ? 2 : 1; rep > 0; rep--) {
+          const uint32_t ix = EXTRAS ? wv::opaque(index) : index;
+          const uint32_t cl = EXTRAS ? wv::bcast(lcache.lc, (int)((ix >> g.sh) - lcache.base)) : c_leaf;
+          if (EXTRAS) rr = rr0;
+          gap_right = occupied ? find_gap_right(v, ix + 1, kMaxSlide, gmask, gw) : ix;
+          if (!plan_insert_first(v, ix, occupied, cl, gap_right, rr, v.big_window, &lcache, &ip)) {
             rr = rr0;  // (the general form starts over, retries included)
-            ip = plan_insert(v, index, occupied, c_leaf, gap_right, rr, v.big_window, &lcache);
+            ip = plan_insert(v, ix, occupied, cl, gap_right, rr, v.big_window, &lcache);
           }
         }
         // tries > 3 (PCSR.cpp:952-955): the reference gives up on leaf locks, takes the global write lock and runs
@@ -1421,11 +1417,12 @@ PMA_DEV PlanRegs plan_op(const View &v, const Op op, Plan *plan, uint32_t idx) {
   } else if (op.op == 0) {
     kind = K_NOOP;  // reference: unchecked out-of-range delete is UB; we ignore it
   }
-  if (kind == K_INSERT || kind == K_REMOVE) {
+  if (kind == K_INSERT || kind == K_REMOVE) for (int rep = (EXTRAS && (dbg & PD_SENTINELS)) ? 2 : 1; rep > 0; rep--) {
     // sentinels inside [lo, hi] = slide range U window.  Sentinel positions increase with the vertex id and
     // beg(src) < index <= beg(src+1), so they are the vertices src, src-1, ... and src+1, src+2, ... around `src`.
     // The first kW of both directions are in registers already (b0): no round trip for almost every update — a one-leaf
     // window holds a handful of sentinels at most.
+    if (EXTRAS) wstart = wv::opaque(wstart);
     const uint32_t lo = (wstart < index) ? wstart : index;
     const uint32_t whi = wstart + wlen - 1u;
     const uint32_t hi = (kind == K_INSERT && gap > whi) ? gap : whi;
@@ -1470,8 +1467,12 @@ PMA_DEV PlanRegs plan_op(const View &v, const Op op, Plan *plan, uint32_t idx) {
     }
   }
   const uint32_t nr = rr.nr;
-  store_ranges(rr, plan);
-  store_plan_header(plan, kind, index, gap, wstart, wlen, wl, wh, mv_lo, mv_hi, sleaf_b, sleaf_e, acalls, aslots, nr, rr.nlong, rr.sdep, idx, op);
+  for (int rep = (EXTRAS && (dbg & PD_STORE)) ? 2 : 1; rep > 0; rep--) {
+    if (EXTRAS) rr.nr = wv::opaque(rr.nr);
+    store_ranges(rr, plan);
+    store_plan_header(plan, EXTRAS ? wv::opaque(kind) : kind, index, gap, wstart, wlen, wl, wh, mv_lo, mv_hi, sleaf_b, sleaf_e, acalls, aslots, nr, rr.nlong,
+                      rr.sdep, idx, op);
+  }
   PlanRegs pr;
   pr.sdep = rr.sdep;
   pr.kind = kind;

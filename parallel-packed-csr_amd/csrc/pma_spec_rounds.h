@@ -90,7 +90,10 @@ struct OptArgs {
   int regshift;
   uint32_t diag;
   uint32_t dbg;  // diagnostics build only: bit 0 = o_plan plans every update twice, bit 1 = searches twice, bit 2 = evaluates the round's
-                 // bookkeeping twice (the SQ counters of two runs then give the cost of that part: tools/sq_run.sh)
+                 // bookkeeping twice (the SQ counters of two runs then give the cost of that part: tools/sq_run.sh); the rest of plan_op
+                 // in four parts: bit 3 = the insert plan (gap search, leaf count, plan_insert_first), bit 4 = the moved-sentinel range,
+                 // bit 5 = the record store (dev::PlanDbg), bit 6 = the reservations (o_reserve) twice.  Bit 7 does nothing: the
+                 // diagnostics build as the base of those differences
   uint32_t defer_barrier;  // 0: off
   uint32_t soft_barrier;   // slots: see o_plan
   // windows above big_min slots are rebalanced by a workgroup of o_big (job queue + one scratch stretch per workgroup)
@@ -273,6 +276,57 @@ PMA_KERNEL void k_epoch_begin(uint32_t *wstamp, uint32_t *rstamp, uint64_t leave
   if (tid == 0) *ctl = init;
 }
 
+// The reservations of one planned update, by its wave: the round's key (round, idx) left as a minimum on everything the plan writes,
+// reads or moves — straight from the registers of plan_op (pr; my_lo / my_hi: lane r holds read range r).  wid: the update's slot
+// in the round, used: slots below it hold deferred updates, rt: the round's set of barriers.
+PMA_DEV void o_reserve(const OptArgs &a, OptCtl *c, const dev::PlanRegs &pr, const Plan *pl, const Op &op, uint32_t idx, uint32_t wid, uint32_t used,
+                       uint32_t rt) {
+  const int lane = wv::lane();
+  const unsigned long long key = make_key(a.round, idx);
+  const uint32_t kind = pr.kind;
+  if (kind == K_EXCL) {
+    if (lane == 0) wv::atomic_min_u64(&c->gbar[rt], key);
+    return;
+  }
+  if (kind == K_DUP) {
+    // lane 0: the leaf's entry (what strong writers of the leaf test), lane 1: the slot's (what later duplicates of the slot test) — one instruction
+    unsigned long long *const e = lane == 0 ? &a.v.dres[pr.wleaf_lo] : &a.dslot[pr.index & (kDupSlots - 1u)];
+    if (lane < 2) wv::atomic_min_u64(e, key);
+  } else if (kind_strong(kind)) {
+    const uint32_t wl = pr.wleaf_lo, wh = pr.wleaf_hi;
+    for (uint32_t base = wl; base <= wh; base += 64) {  // (scalar trip count)
+      const uint32_t leaf = base + (uint32_t)lane;
+      if (leaf <= wh) wv::atomic_min_u64(&a.v.wres[leaf], key);
+    }
+    // an update whose window is already within two levels of the exclusive threshold is likely to turn exclusive
+    // once the earlier updates have landed: nothing later may overtake it (soft barrier)
+    // ... and so is an update that has ALREADY been deferred at least once and whose window is big (a.defer_barrier
+    // slots): its window keeps growing while it waits behind a hot range, and everything committed around it meanwhile
+    // is a candidate for a rollback
+    if ((pr.wlen >= a.soft_barrier || (a.defer_barrier && wid < used && pr.wlen >= a.defer_barrier)) && lane == 0) {
+      wv::atomic_min_u64(&c->sbar[rt], key);
+    }
+    const uint32_t ml = pr.mv_lo, mh = pr.mv_hi;
+    if (ml <= mh)
+      for (uint32_t base = ml;; base += 64u) {  // (32-bit counters: half the scalar arithmetic of a 64-bit trip count)
+        const uint32_t u = base + (uint32_t)lane;
+        if (u <= mh && u >= base) wv::atomic_min_u64(&a.v.vw[u], key);
+        if (mh - base < 64u) break;  // (no wrap-around at the top of the vertex range)
+      }
+  }
+  if (pr.nlong == 0u) {  // lane r holds read range r
+    if ((uint32_t)lane < pr.nr)
+      for (uint32_t leaf = pr.my_lo; leaf <= pr.my_hi; leaf++) wv::atomic_min_u64(&a.v.rres[leaf], key);
+  } else {
+    wv::fence();  // (rare) more ranges than lanes, or long ranges: walk the record this wave has just written
+    PMA_FOR_EACH_READ_LEAF(pl, lane, leaf, wv::atomic_min_u64(&a.v.rres[leaf], key));
+  }
+  if (kind_real(kind) && op.src < a.v.g.n) {  // readers of the positions of sentinels src and src+1 (only when the result depends on them)
+    // lane 0: sentinel src, lane 1: sentinel src + 1 — one instruction, as o_check reads them
+    const uint32_t u = op.src + (uint32_t)lane;
+    if (lane < 2 && ((pr.sdep >> lane) & 1u) && u < a.v.g.n) wv::atomic_min_u64(&a.v.vr[u], key);
+  }
+}
 // words of the round's state that wave 0 of a workgroup hands to the others (LDS, lane i <-> word i)
 enum RoundWord : int { RW_STOP = 0, RW_HOR, RW_USED, RW_NF, RW_PRE0, RW_SKIP_IDX = RW_PRE0 + (int)kStripes + 1, RW_SKIP_ROUND, RW_WORDS };
 static_assert(RW_WORDS <= 16, "round words");
@@ -297,20 +351,14 @@ PMA_DEV void o_plan_t(const OptArgs &a) {
       const RoundState rs = round_begin(a, c);
       if (wid == 0u && lane == 0) round_record(a, c, rs);
       stop = (rs.done | rs.excl | rs.error | rs.need_big) ? 1u : 0u;
-      w = wv::setlane<RW_HOR>(w, rs.hor);
-      w = wv::setlane<RW_USED>(w, rs.used);
-      w = wv::setlane<RW_NF>(w, rs.nf);
-      w = wv::setlane<RW_PRE0 + 0>(w, rs.pre[0]);
-      w = wv::setlane<RW_PRE0 + 1>(w, rs.pre[1]);
-      w = wv::setlane<RW_PRE0 + 2>(w, rs.pre[2]);
-      w = wv::setlane<RW_PRE0 + 3>(w, rs.pre[3]);
-      w = wv::setlane<RW_PRE0 + 4>(w, rs.pre[4]);
-      w = wv::setlane<RW_PRE0 + 5>(w, rs.pre[5]);
-      w = wv::setlane<RW_PRE0 + 6>(w, rs.pre[6]);
-      w = wv::setlane<RW_PRE0 + 7>(w, rs.pre[7]);
-      w = wv::setlane<RW_PRE0 + 8>(w, rs.pre[8]);
-      w = wv::setlane<RW_SKIP_IDX>(w, skip_idx);
-      w = wv::setlane<RW_SKIP_ROUND>(w, skip_round);
+      // (two interleaved halves, merged: see wv::setlanes; word RW_WORDS is nobody's)
+      static_assert(RW_WORDS == 15 && kStripes == 8, "the four blocks below");
+      uint32_t wb = 0;
+      w = wv::setlanes<RW_HOR, RW_USED, RW_NF, RW_PRE0 + 0>(w, rs.hor, rs.used, rs.nf, rs.pre[0]);
+      wb = wv::setlanes<RW_PRE0 + 1, RW_PRE0 + 2, RW_PRE0 + 3, RW_PRE0 + 4>(wb, rs.pre[1], rs.pre[2], rs.pre[3], rs.pre[4]);
+      w = wv::setlanes<RW_PRE0 + 5, RW_PRE0 + 6, RW_PRE0 + 7, RW_PRE0 + 8>(w, rs.pre[5], rs.pre[6], rs.pre[7], rs.pre[8]);
+      wb = wv::setlanes<RW_SKIP_IDX, RW_SKIP_ROUND, RW_WORDS, RW_WORDS>(wb, skip_idx, skip_round, 0u, 0u);
+      w |= wb;
     }
     w = wv::setlane<RW_STOP>(w, stop);
     if (lane < 16) rsh[lane] = w;
@@ -354,49 +402,9 @@ PMA_DEV void o_plan_t(const OptArgs &a) {
     if (r2.hor == 0xFFFFFFF0u) a.status[wid] = r2.nf;
   }
   // the plan record goes to memory for o_check / o_apply; this kernel reserves straight from the registers
-  const dev::PlanRegs pr = dev::plan_op(a.v, op, pl, idx);
-  const unsigned long long key = make_key(a.round, idx);
-  const uint32_t kind = pr.kind;
-  if (kind == K_EXCL) {
-    if (lane == 0) wv::atomic_min_u64(&c->gbar[rt], key);
-    return;
-  }
-  if (kind == K_DUP) {
-    // lane 0: the leaf's entry (what strong writers of the leaf test), lane 1: the slot's (what later duplicates of the slot test) — one instruction
-    unsigned long long *const e = lane == 0 ? &a.v.dres[pr.wleaf_lo] : &a.dslot[pr.index & (kDupSlots - 1u)];
-    if (lane < 2) wv::atomic_min_u64(e, key);
-  } else if (kind_strong(kind)) {
-    const uint32_t wl = pr.wleaf_lo, wh = pr.wleaf_hi;
-    for (uint32_t base = wl; base <= wh; base += 64) {  // (scalar trip count)
-      const uint32_t leaf = base + (uint32_t)lane;
-      if (leaf <= wh) wv::atomic_min_u64(&a.v.wres[leaf], key);
-    }
-    // an update whose window is already within two levels of the exclusive threshold is likely to turn exclusive
-    // once the earlier updates have landed: nothing later may overtake it (soft barrier)
-    // ... and so is an update that has ALREADY been deferred at least once and whose window is big (a.defer_barrier
-    // slots): its window keeps growing while it waits behind a hot range, and everything committed around it meanwhile
-    // is a candidate for a rollback
-    if ((pr.wlen >= a.soft_barrier || (a.defer_barrier && wid < used && pr.wlen >= a.defer_barrier)) && lane == 0) {
-      wv::atomic_min_u64(&c->sbar[rt], key);
-    }
-    const uint32_t ml = pr.mv_lo, mh = pr.mv_hi;
-    if (ml <= mh)
-      for (uint64_t base = ml; base <= (uint64_t)mh; base += 64) {
-        const uint64_t u = base + (uint64_t)lane;
-        if (u <= (uint64_t)mh) wv::atomic_min_u64(&a.v.vw[u], key);
-      }
-  }
-  if (pr.nlong == 0u) {  // lane r holds read range r
-    if ((uint32_t)lane < pr.nr)
-      for (uint32_t leaf = pr.my_lo; leaf <= pr.my_hi; leaf++) wv::atomic_min_u64(&a.v.rres[leaf], key);
-  } else {
-    wv::fence();  // (rare) more ranges than lanes, or long ranges: walk the record this wave has just written
-    PMA_FOR_EACH_READ_LEAF(pl, lane, leaf, wv::atomic_min_u64(&a.v.rres[leaf], key));
-  }
-  if (kind_real(kind) && op.src < a.v.g.n) {  // readers of the positions of sentinels src and src+1 (only when the result depends on them)
-    if (lane == 0 && (pr.sdep & 1u)) wv::atomic_min_u64(&a.v.vr[op.src], key);
-    if (lane == 1 && (pr.sdep & 2u) && op.src + 1u < a.v.g.n) wv::atomic_min_u64(&a.v.vr[op.src + 1u], key);
-  }
+  const dev::PlanRegs pr = dev::plan_op<EXTRAS>(a.v, op, pl, idx, EXTRAS ? a.dbg : 0u);
+  if (EXTRAS && (a.dbg & 64u)) o_reserve(a, c, pr, pl, op, wv::opaque(idx), wid, used, rt);
+  o_reserve(a, c, pr, pl, op, idx, wid, used, rt);
 }
 // (35 VGPRs; 8 waves per SIMD need <= 96 scalar registers: the planner is a chain of dependent loads, residency is throughput)
 PMA_KERNEL void PMA_LAUNCH_BOUNDS(256, 8) o_plan(OptArgs a) { o_plan_t<false>(a); }
@@ -510,8 +518,8 @@ PMA_DEV void o_check_one(const OptArgs &a, OptCtl *c, uint32_t par, uint32_t wid
       }
     }
   }
-  const bool anyfail = wv::ballot(fail) != 0;
-  const bool anybad = wv::ballot(stamp_bad) != 0;
+  const bool anyfail = wv::any(fail);
+  const bool anybad = wv::any(stamp_bad);
   if ((EXTRAS && a.diag) && anyfail) {
     uint32_t w = why, wb = blk;
     for (int o = 32; o > 0; o >>= 1) {

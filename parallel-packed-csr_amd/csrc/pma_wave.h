@@ -6,6 +6,22 @@
 
 #if defined(PPCSR_SIM)
 #include "sim_runtime.h"
+// The emulator's forms of vec / any / all / opaque / setlanes (their product forms and what they are for: below), on the runtime's
+// own collectives: vec and opaque make the claim of uni() and are checked like it, any / all are ballots of the live lanes.
+namespace ppcsr {
+namespace wv {
+inline uint32_t vec(uint32_t v) { return (uint32_t)sim::uniform64(v); }
+inline uint64_t vec(uint64_t v) { return sim::uniform64(v); }
+inline bool any(bool p) { return sim::ballot(p) != 0; }
+inline bool all(bool p) { return sim::ballot(!p) == 0; }
+inline uint32_t opaque(uint32_t v) { return (uint32_t)sim::uniform64(v); }
+template <int K0, int K1, int K2, int K3>
+inline uint32_t setlanes(uint32_t v, uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3) {
+  const int l = lane();
+  return l == K0 ? x0 : l == K1 ? x1 : l == K2 ? x2 : l == K3 ? x3 : v;
+}
+}  // namespace wv
+}  // namespace ppcsr
 #else
 #include <hip/hip_runtime.h>
 #define PMA_DEV __device__ __forceinline__
@@ -32,11 +48,49 @@ PMA_DEV bool uni(bool b) { return __builtin_amdgcn_readfirstlane(b ? 1 : 0) != 0
 PMA_DEV uint64_t uni(uint64_t v) {
   return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
 }
+// The other way round.  The scalar unit issues one instruction per wave every four cycles and is shared by the CU's four SIMDs; a
+// SIMD takes a wave64 vector instruction every two, and in the planning kernels it is mostly idle.  vec() states what uni() states
+// — the value is the same in every lane — and keeps it in a VECTOR register: the empty asm hides the value's origin from the
+// compiler's uniformity analysis, so the arithmetic that descends from it is VALU and its live range costs no scalar register
+// (zero instructions; not volatile: an unused one disappears).  The CPU emulator checks the claim like uni()'s.
+PMA_DEV uint32_t vec(uint32_t x) {
+  asm("" : "+v"(x));
+  return x;
+}
+PMA_DEV uint64_t vec(uint64_t x) {
+  asm("" : "+v"(x));
+  return x;
+}
+// Branches on such values: a ballot compared with 0 / with the full mask (all 64 lanes are active) — v_cmp into VCC and ONE scalar
+// branch, never an EXEC-mask region.  `if (p)` on a vec() value is a divergent branch to the compiler; `if (wv::any(p))` is not.
+PMA_DEV bool any(bool p) { return __ballot(p ? 1 : 0) != 0ull; }
+PMA_DEV bool all(bool p) { return __ballot(p ? 1 : 0) == ~0ull; }
+// measurement aid (diagnostics builds only: OptArgs::dbg): the uniform value x, as a scalar the compiler knows nothing about — what
+// is computed from it a second time is computed, not reused
+PMA_DEV uint32_t opaque(uint32_t x) {
+  uint32_t s = (uint32_t)__builtin_amdgcn_readfirstlane((int)x);
+  asm volatile("" : "+s"(s)::"memory");
+  return s;
+}
 // v with lane K replaced by the scalar `x` (v_writelane_b32; this compiler has no builtin for it)
 template <int K>
 PMA_DEV uint32_t setlane(uint32_t v, uint32_t x) {
   const uint32_t sx = (uint32_t)__builtin_amdgcn_readfirstlane((int)x);  // (the "s" constraint alone does not move a vector value)
   asm("v_writelane_b32 %0, %1, %2" : "+v"(v) : "s"(sx), "n"(K));
+  return v;
+}
+// v with lanes K0 .. K3 replaced by four scalars, as ONE asm block.  Behind every asm statement that writes a vector register the
+// compiler pads the next reader of that register with an s_nop (it cannot see that the statement is no sub-dword write); a chain
+// of N setlane() calls is N - 1 pads, each a scalar issue slot.  Writes to one register need no pad among themselves (the
+// compiler's own spill code issues them back to back).  Two such blocks that build DIFFERENT registers follow each other without
+// a pad as well: a record of many words is built as two interleaved halves and merged with one OR (store_plan_header).
+template <int K0, int K1, int K2, int K3>
+PMA_DEV uint32_t setlanes(uint32_t v, uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3) {
+  const uint32_t s0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)x0), s1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)x1);
+  const uint32_t s2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)x2), s3 = (uint32_t)__builtin_amdgcn_readfirstlane((int)x3);
+  asm("v_writelane_b32 %0, %1, %5\n\tv_writelane_b32 %0, %2, %6\n\tv_writelane_b32 %0, %3, %7\n\tv_writelane_b32 %0, %4, %8"
+      : "+v"(v)
+      : "s"(s0), "s"(s1), "s"(s2), "s"(s3), "n"(K0), "n"(K1), "n"(K2), "n"(K3));
   return v;
 }
 // lanes 0 .. N-1 of v as scalars (N x v_readlane_b32; the emulator does it in one rendezvous)

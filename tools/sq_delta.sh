@@ -1,5 +1,7 @@
 #!/bin/bash
 # dynamic instruction cost of parts of o_plan: SQ counters of the diagnostics build with a part executed twice (option dbg_repeat)
+# usage: sq_delta.sh BITS...   1 whole plan, 2 search, 4 bookkeeping, 8 insert plan, 16 moved-sentinel range, 32 record store,
+# 64 reservations, 128 nothing repeated (the base of the differences: 0 selects the product kernel, not the diagnostics build)
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 OUT="$ROOT/gpurun_out/sqd"
 rm -rf "$OUT"; mkdir -p "$OUT"
