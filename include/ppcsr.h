@@ -185,6 +185,53 @@ int ppcsr_betweenness(ppcsr_t h, const uint32_t *sources, uint64_t k, double *bc
  * intersect sorted ranges, so — as components, and unlike triangles — it also answers in the sequential regime
  * (stats.narrow == 0).  EINVAL: null handle, core and kmax both NULL. */
 int ppcsr_kcore(ppcsr_t h, uint32_t *core, uint32_t *kmax, double *device_ms);
+/* Greedy vertex colouring and the maximal independent set (MIS), in the undirected graph G that ppcsr_triangles counts in and
+ * ppcsr_kcore peels: the edge set ppcsr_components hooks (live non-sentinel slots, slot N - 1 excluded, local src < n,
+ * destinations >= n skipped), upper orientation — {a, b}, a < b < n, is an edge exactly when the pair (a, b) is stored; self-loops
+ * and stored pairs with src > dst play no part.  A pair is stored at most once, so G is simple.
+ * Vertex order.  Every vertex has a 64-bit key; u PRECEDES w iff key(u) > key(w), or the keys are equal and u < w.  With
+ * draw(v) = the counter-based draw (seed, v, 0) of ppcsr_sample_neighbours (splitmix64 three times), v the vertex id:
+ *   PPCSR_ORDER_RANDOM  key = draw(v)                                   random priorities
+ *   PPCSR_ORDER_DEGREE  key = (deg_G(v) << 32) | (draw(v) >> 32)        largest degree first, ties at random
+ *   PPCSR_ORDER_ID      key = 0 (the seed is ignored)                   ascending id: sequential first-fit
+ * colouring — colour[v] = the smallest non-negative integer that no neighbour w of v that precedes v carries (n entries, may be
+ *   NULL): sequential greedy colouring in the order, computed as Jones and Plassmann do.  An isolated vertex gets colour 0;
+ *   colour[v] <= deg_G(v).  *ncolours = 1 + the largest colour, 0 for n = 0 (may be NULL, not both).
+ * mis — in_set[v] = 1 iff no neighbour w of v that precedes v has in_set[w] = 1, else 0 (n bytes, may be NULL): the
+ *   lexicographically first maximal independent set in the order.  *size = the number of members (may be NULL, not both).
+ * Everything returned is unique, and for one order and seed in_set[v] == (colour[v] == 0).
+ * Same contract as every consumer: synchronous on the engine's stream, sees every batch applied before it, writes nothing to
+ * the graph (state, stats, dirty tags and snapshot unchanged), device_ms may be NULL, every refusal is made before the first
+ * launch.  Neither call intersects sorted ranges, so — as kcore — both also answer in the sequential regime
+ * (stats.narrow == 0).  EINVAL: null handle, both outputs NULL, an order other than the three above.  ENOMEM: a device
+ * allocation of the call failed (nothing written).
+ * Cost.  Let level(v) = 0 for a vertex without a preceding neighbour, else 1 + the largest level of one.  The colouring exports
+ * G as ppcsr_kcore does and then takes one launch and one host read per level; the MIS streams the arrays in place, at most
+ * two passes per level.  Random orders give few levels; PPCSR_ORDER_ID on a path of L vertices stored in id order is L levels,
+ * as the chains ppcsr_scc warns about.  Both loops are bounded — n rounds for the colouring, 2 n + 1 for the MIS — and report
+ * an error past that instead of spinning. */
+#define PPCSR_ORDER_RANDOM 0u
+#define PPCSR_ORDER_DEGREE 1u
+#define PPCSR_ORDER_ID 2u
+int ppcsr_colouring(ppcsr_t h, uint32_t order, uint64_t seed, uint32_t *colour, uint32_t *ncolours, double *device_ms);
+int ppcsr_mis(ppcsr_t h, uint32_t order, uint64_t seed, uint8_t *in_set, uint64_t *size, double *device_ms);
+/* Debugging: what the last colouring / mis call on this engine did — for a pppcsr_* call the engine that ran it, the first
+ * partition's (pppcsr_partition).  Kept on the host from the reads the loops make anyway and always on; all zeros before the
+ * first call.  Rounds, the widest frontier, members and undecided after round 1 are functions of the graph and the order.
+ * colouring:
+ *   out[0] rounds = levels of the order                     out[1] the widest frontier
+ *   out[2] frontier vertices handed to the long-list kernel (lists beyond 4096 entries)
+ *   out[3] adjacency entries, 2 |E(G)|                      out[4] colours
+ *   out[5] window passes of the long-list kernel beyond each vertex's first ("colour_window")
+ *   out[6] launches                                         out[7] host reads
+ * mis:
+ *   out[0] rounds                                           out[1] streaming passes of the rounds
+ *   out[2] members after round 1 (the local maxima)         out[3] undecided after round 1
+ *   out[4] size                                             out[5] degree passes (1 for PPCSR_ORDER_DEGREE, else 0)
+ *   out[6] launches                                         out[7] host reads
+ * EINVAL: null handle or out. */
+int ppcsr_debug_colouring_counters(ppcsr_t h, uint64_t out[8]);
+int ppcsr_debug_mis_counters(ppcsr_t h, uint64_t out[8]);
 /* Strongly connected components, over exactly the edge set ppcsr_bfs walks (live non-sentinel slots, slot N - 1 excluded, local
  * src < n, destinations >= n skipped), taken as DIRECTED; the edge values play no part.  A self-loop is an ordinary stored edge
  * that changes nothing: a vertex whose only cycle is its self-loop is an SCC of one vertex.
@@ -373,7 +420,9 @@ int ppcsr_stats(ppcsr_t h, ppcsr_stats_t *out);
  *              "rb_tile", "rb_min_tiles", "rb_prefetch", "rb_inplace_min" (partial windows of at least this many slots are
  *              rebalanced in place; 0 = always through the scratch array), "rb_inplace_cpw", "rb_inplace_lists"
  *   search     "search_narrow" (0: literal binary walk only)
- *   consumers  "msbfs_look" (0: the streaming pass of ppcsr_multi_bfs issues its ORs without first looking at next[w]; default 1)
+ *   consumers  "msbfs_look" (0: the streaming pass of ppcsr_multi_bfs issues its ORs without first looking at next[w]; default 1),
+ *              "colour_window" (test hook: colours per pass of ppcsr_colouring's long-list kernel over a list beyond 4096 entries;
+ *              a multiple of 64 in [64, 32768], anything else is EINVAL; default 32768)
  *   measuring  "profile" (1: HIP events around every round kernel, reported through ppcsr_stats), "diag" (1: why updates
  *              did not commit, per epoch, on stderr; 2: also a per-update dependency trace, PPCSR_DIAG_DUMP = file), "marker" (marker kernels for profile cuts), "test_block_rebalance"
  *   reads      test hooks that move the seams of the batched reads (defaults = the shipped sizes; values in [1, 2^32]):
@@ -530,6 +579,14 @@ int pppcsr_components(pppcsr_t h, uint32_t *labels, double *device_ms);
  * pppcsr_components; a partition in the sequential regime is answered.  EINVAL: null handle, core and kmax both NULL, or a
  * partition not resident in this process.  EUNSUPPORTED: the partitions sit on more than one device. */
 int pppcsr_kcore(pppcsr_t h, uint32_t *core, uint32_t *kmax, double *device_ms);
+/* ppcsr_colouring / ppcsr_mis over the GLOBAL vertex ids (colour: pppcsr_get_n entries, in_set: as many bytes; draw(v) takes
+ * the global id), one device call over every partition's array: an edge may have its two vertices in different partitions, and
+ * no output depends on the partitioning.  Same contract as pppcsr_kcore; a partition in the sequential regime is answered.  The
+ * counters are those of the engine that ran the call, the first partition's (pppcsr_partition).  EINVAL: null handle, both
+ * outputs NULL, an unknown order, or a partition not resident in this process.  EUNSUPPORTED: the partitions sit on more than
+ * one device.  ENOMEM: a device allocation of the call failed (nothing written). */
+int pppcsr_colouring(pppcsr_t h, uint32_t order, uint64_t seed, uint32_t *colour, uint32_t *ncolours, double *device_ms);
+int pppcsr_mis(pppcsr_t h, uint32_t order, uint64_t seed, uint8_t *in_set, uint64_t *size, double *device_ms);
 /* ppcsr_scc over the GLOBAL vertex ids (labels: pppcsr_get_n entries), one device call over every partition's array: an SCC may
  * span partitions, and the result does not depend on the partitioning.  Same contract as pppcsr_components; a partition in the
  * sequential regime is answered.  EINVAL: null handle, labels and count both NULL, or a partition not resident in this

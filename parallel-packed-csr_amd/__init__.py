@@ -81,10 +81,12 @@ EXPORTED = [
     "ppcsr_sample_neighbours", "ppcsr_sample_neighbours_device", "pppcsr_sample_neighbours",
     "ppcsr_random_walks", "ppcsr_random_walks_device", "pppcsr_random_walks", "ppcsr_degrees", "pppcsr_degrees", "ppcsr_debug_mulhi",
     "ppcsr_multi_bfs", "pppcsr_multi_bfs", "ppcsr_debug_multi_bfs_counters", "ppcsr_debug_dup_slot_entries",
+    "ppcsr_colouring", "pppcsr_colouring", "ppcsr_mis", "pppcsr_mis", "ppcsr_debug_colouring_counters", "ppcsr_debug_mis_counters",
 ]
 
 NO_PATH = 0xFFFFFFFFFFFFFFFF  # PPCSR_NO_PATH: what sssp reports for a vertex no path reaches
 NO_EDGE = 0xFFFFFFFF  # PPCSR_NO_EDGE: what lookup_edges reports for a pair that is not an edge
+ORDERS = {"random": 0, "degree": 1, "id": 2}  # PPCSR_ORDER_*: the vertex orders of colouring / mis
 NO_VERTEX = 0xFFFFFFFF  # PPCSR_NO_VERTEX: what sample_neighbours / random_walks report where there is nothing to pick from
 
 _LIBS = {}
@@ -189,6 +191,12 @@ def load_library(path=None):
     for name in ("ppcsr_multi_bfs", "pppcsr_multi_bfs"):
         getattr(L, name).argtypes = [c_vp, c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_debug_multi_bfs_counters.argtypes = [c_vp, c_vp]
+    for name in ("ppcsr_colouring", "pppcsr_colouring"):
+        getattr(L, name).argtypes = [c_vp, c_u32, c_u64, c_vp, ctypes.POINTER(c_u32), ctypes.POINTER(ctypes.c_double)]
+    for name in ("ppcsr_mis", "pppcsr_mis"):
+        getattr(L, name).argtypes = [c_vp, c_u32, c_u64, c_vp, ctypes.POINTER(c_u64), ctypes.POINTER(ctypes.c_double)]
+    L.ppcsr_debug_colouring_counters.argtypes = [c_vp, c_vp]
+    L.ppcsr_debug_mis_counters.argtypes = [c_vp, c_vp]
     L.ppcsr_bulk_build.argtypes = [c_vp, c_vp, c_u64, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_bfs.argtypes = [c_vp, c_u32, c_vp, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_pagerank.argtypes = [c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_double)]
@@ -345,6 +353,23 @@ class _Consumers:
         kmax = c_u32()
         ms = self._consumer("kcore", core.ctypes.data, ctypes.byref(kmax))
         return (core, kmax.value, ms) if with_ms else (core, kmax.value)
+
+    def colouring(self, order="random", seed=0, with_ms=False):
+        """(colour, ncolours[, ms]): greedy colouring of the upper-orientation graph kcore() peels, in the vertex order `order`
+        (a key of ORDERS or its number) with `seed`: colour[v] (uint32, global ids) is the smallest colour no preceding
+        neighbour carries; ncolours = 1 + the largest"""
+        colour = np.empty(self.get_n(), np.uint32)
+        ncol = c_u32()
+        ms = self._consumer("colouring", ORDERS.get(order, order), seed, colour.ctypes.data, ctypes.byref(ncol))
+        return (colour, ncol.value, ms) if with_ms else (colour, ncol.value)
+
+    def mis(self, order="random", seed=0, with_ms=False):
+        """(mask, size[, ms]): the lexicographically first maximal independent set of the same graph in the same order: mask[v]
+        (bool) iff no preceding neighbour is a member — for one order and seed, mask == (colouring()[0] == 0)"""
+        mask = np.empty(self.get_n(), np.uint8)
+        size = c_u64()
+        ms = self._consumer("mis", ORDERS.get(order, order), seed, mask.ctypes.data, ctypes.byref(size))
+        return (mask.astype(bool), size.value, ms) if with_ms else (mask.astype(bool), size.value)
 
     def scc(self, with_ms=False):
         """(labels, count[, ms]): strongly connected components of the stored DIRECTED graph: the smallest vertex id of every
@@ -633,6 +658,20 @@ class PCSR(_Consumers):
         self._chk(self.L.ppcsr_debug_multi_bfs_counters(self.h, out.ctypes.data))
         return out
 
+    def debug_colouring_counters(self):
+        """Debugging (ppcsr_debug_colouring_counters): uint64[8] of the last colouring call on this engine — rounds, the widest
+        frontier, vertices left to the long-list kernel, adjacency entries, colours, extra window passes, launches, host reads"""
+        out = np.zeros(8, np.uint64)
+        self._chk(self.L.ppcsr_debug_colouring_counters(self.h, out.ctypes.data))
+        return out
+
+    def debug_mis_counters(self):
+        """Debugging (ppcsr_debug_mis_counters): uint64[8] of the last mis call on this engine — rounds, streaming passes, members
+        and undecided after round 1, size, degree passes, launches, host reads"""
+        out = np.zeros(8, np.uint64)
+        self._chk(self.L.ppcsr_debug_mis_counters(self.h, out.ctypes.data))
+        return out
+
     def debug_scc_counters(self):
         """Debugging (ppcsr_debug_scc_counters): uint64[8] of the last scc call on this engine — vertices trimmed, trim sweeps,
         the pivot (2^64 - 1: none), vertices of its SCC, colouring rounds, vertices coloured, streaming passes, host reads"""
@@ -833,6 +872,14 @@ class PPPCSR(_Consumers):
     def debug_multi_bfs_counters(self):
         """the counters of the last multi_bfs call: kept by the engine that ran it, the first partition's"""
         return self.partition(0).debug_multi_bfs_counters()
+
+    def debug_colouring_counters(self):
+        """the counters of the last colouring call: kept by the engine that ran it, the first partition's"""
+        return self.partition(0).debug_colouring_counters()
+
+    def debug_mis_counters(self):
+        """the counters of the last mis call: kept by the engine that ran it, the first partition's"""
+        return self.partition(0).debug_mis_counters()
 
     def debug_scc_counters(self):
         """the counters of the last scc call: kept by the engine that ran it, the first partition's"""

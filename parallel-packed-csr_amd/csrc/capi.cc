@@ -197,6 +197,20 @@ int ppcsr_kcore(ppcsr_t h, uint32_t *core, uint32_t *kmax, double *device_ms) {
   const ppcsr::ConsumerRef self{h->e, 0};
   return ret(h->e, h->e->kcore_over(&self, 1, h->e->n(), core, kmax, device_ms));
 }
+int ppcsr_colouring(ppcsr_t h, uint32_t order, uint64_t seed, uint32_t *colour, uint32_t *ncolours, double *device_ms) {
+  H_CHECK();
+  if (!colour && !ncolours) return bad("colouring: null outputs");
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->colouring_over(&self, 1, h->e->n(), order, seed, colour, ncolours, device_ms));
+}
+int ppcsr_mis(ppcsr_t h, uint32_t order, uint64_t seed, uint8_t *in_set, uint64_t *size, double *device_ms) {
+  H_CHECK();
+  if (!in_set && !size) return bad("mis: null outputs");
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->mis_over(&self, 1, h->e->n(), order, seed, in_set, size, device_ms));
+}
+int ppcsr_debug_colouring_counters(ppcsr_t h, uint64_t out[8]) { H_CHECK(); return ret(h->e, h->e->colouring_counters(out)); }
+int ppcsr_debug_mis_counters(ppcsr_t h, uint64_t out[8]) { H_CHECK(); return ret(h->e, h->e->mis_counters(out)); }
 int ppcsr_scc(ppcsr_t h, uint32_t *labels, uint64_t *count, double *device_ms) {
   H_CHECK();
   if (!labels && !count) return bad("scc: null outputs");
@@ -842,6 +856,20 @@ int pppcsr_kcore(pppcsr_t h, uint32_t *core, uint32_t *kmax, double *device_ms) 
   PP_CHECK();
   if (!core && !kmax) return bad("kcore: null outputs");
   return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) { return ret(e, e->kcore_over(r, P, n, core, kmax, device_ms)); });
+}
+int pppcsr_colouring(pppcsr_t h, uint32_t order, uint64_t seed, uint32_t *colour, uint32_t *ncolours, double *device_ms) {
+  PP_CHECK();
+  if (!colour && !ncolours) return bad("colouring: null outputs");
+  if (order > 2u) return bad("colouring: unknown vertex order");
+  return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) {
+    return ret(e, e->colouring_over(r, P, n, order, seed, colour, ncolours, device_ms));
+  });
+}
+int pppcsr_mis(pppcsr_t h, uint32_t order, uint64_t seed, uint8_t *in_set, uint64_t *size, double *device_ms) {
+  PP_CHECK();
+  if (!in_set && !size) return bad("mis: null outputs");
+  if (order > 2u) return bad("mis: unknown vertex order");
+  return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) { return ret(e, e->mis_over(r, P, n, order, seed, in_set, size, device_ms)); });
 }
 int pppcsr_scc(pppcsr_t h, uint32_t *labels, uint64_t *count, double *device_ms) {
   PP_CHECK();

@@ -107,6 +107,16 @@ class Engine {
   // core numbers of the upper-orientation graph triangles counts in (pma_cores.h), in either regime: core (total_n entries,
   // may be null), *kmax (may be null): the largest core number
   int kcore_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t *core, uint32_t *kmax, double *device_ms);
+  // greedy colouring and the maximal independent set of the same graph in a fixed vertex order (pma_colour.h; the definitions:
+  // include/ppcsr.h), in either regime.  order: PPCSR_ORDER_*, anything else is refused before the first launch.  colour
+  // (total_n entries) / *ncolours and in_set (total_n bytes) / *size may each be null.  *_counters: what the last call on this
+  // engine did (ppcsr_debug_colouring_counters / ppcsr_debug_mis_counters)
+  int colouring_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t order, uint64_t seed, uint32_t *colour, uint32_t *ncolours,
+                     double *device_ms);
+  int mis_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t order, uint64_t seed, uint8_t *in_set, uint64_t *size,
+               double *device_ms);
+  int colouring_counters(uint64_t out[8]);
+  int mis_counters(uint64_t out[8]);
   // strongly connected components (pma_scc.h), in either regime: labels[v] = smallest vertex id of v's SCC (total_n entries, may
   // be null), *count = number of SCCs (may be null).  scc_counters: what the last scc_over on this engine did
   // (ppcsr_debug_scc_counters, include/ppcsr.h)

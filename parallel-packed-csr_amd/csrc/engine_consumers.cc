@@ -1,5 +1,5 @@
 // Host drivers of the graph-algorithm consumers (kernels: pma_consumer.h, pma_scan.h, pma_paths.h, pma_cores.h, pma_centrality.h,
-// pma_scc.h, pma_msf.h, pma_intersect.h, pma_truss.h, pma_sample.h, pma_msbfs.h).  Included at the end of engine.cc: part of the engine's single translation unit, in the library
+// pma_scc.h, pma_msf.h, pma_intersect.h, pma_truss.h, pma_sample.h, pma_msbfs.h, pma_colour.h).  Included at the end of engine.cc: part of the engine's single translation unit, in the library
 // (csrc/ppcsr_hip.hip) and in the emulator (tests/hostsim/ppcsr_sim.cpp) alike.
 namespace ppcsr {
 
@@ -210,6 +210,27 @@ struct Engine::ConsumerScope {
     return PPCSR_OK;
   }
 
+  // Stage 1 of pma_cores.h, shared by kcore_over and colouring_over: from the cleared deg[] / fill[] to the compact symmetric
+  // adjacency of G.  The degree pass, the three launches of the scan (off[n] = 2 |E(G)|), the host read of that total, the
+  // allocation of the lists (the call's alloc_code when it fails), the fill pass.  *adj: the lists; *entries: their length.
+  int symmetric_adjacency(uint32_t P, uint32_t *d_deg, uint32_t *d_fill, unsigned long long *d_off, unsigned long long *d_tiles, uint32_t ntiles,
+                          uint32_t **adj, uint64_t *entries) {
+    const uint32_t nn = n_;
+    GPU_LAUNCH(p.stream, k_kc_degree, pass_grid(), 256, tab_, P, nn, d_deg);
+    GPU_LAUNCH(p.stream, k_kc_tile_sums, grid_for(ntiles, 1, 65536), 256, (const uint32_t *)d_deg, nn, ntiles, d_tiles);
+    GPU_LAUNCH(p.stream, k_kc_scan_tiles, 1, 64, d_tiles, ntiles, d_off + nn);
+    GPU_LAUNCH(p.stream, k_kc_scan_write, grid_for(ntiles, 1, 65536), 256, (const uint32_t *)d_deg, nn, ntiles, (const unsigned long long *)d_tiles, d_off);
+    unsigned long long total = 0;
+    const int e = read_back(&total, d_off + nn, sizeof(total));
+    if (e != PPCSR_OK) return e;
+    uint32_t *d_adj = alloc<uint32_t>("d_adj", std::max<uint64_t>(total, 1));
+    if (rc != PPCSR_OK) return rc;
+    GPU_LAUNCH(p.stream, k_kc_fill, pass_grid(), 256, tab_, P, nn, (const unsigned long long *)d_off, d_fill, d_adj);
+    *adj = d_adj;
+    *entries = total;
+    return PPCSR_OK;
+  }
+
   // sample_over / walks_over: the hubs among d_q[0, k) (d_q == nullptr: among all vertices) and their measure prefix
   int sample_hubs(uint32_t P, const uint32_t *d_q, uint64_t k, bool weighted, SmHubs *hb);
 };
@@ -412,7 +433,6 @@ int Engine::kcore_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, u
   ConsumerScope cs(this);
   const int rc = cs.open(parts, P, nn);
   if (rc != PPCSR_OK) return rc;
-  const ConsumerPart *tab = cs.table();
   const uint64_t words = cs.words();
   const uint32_t ntiles = (uint32_t)(((uint64_t)nn + kKcTile - 1) / kKcTile);
   uint32_t *d_deg = cs.alloc<uint32_t>("d_deg", words), *d_core = cs.alloc<uint32_t>("d_core", words), *d_fill = cs.alloc<uint32_t>("d_fill", words);
@@ -428,16 +448,10 @@ int Engine::kcore_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, u
     GCHK(gpu::dset(d_deg, 0, words * sizeof(uint32_t), cs.stream()));
     GCHK(gpu::dset(d_fill, 0, words * sizeof(uint32_t), cs.stream()));
     GPU_LAUNCH(cs.stream(), k_kc_init, cs.vert_grid(), 256, d_core, nn);
-    GPU_LAUNCH(cs.stream(), k_kc_degree, cs.pass_grid(), 256, tab, P, nn, d_deg);
-    GPU_LAUNCH(cs.stream(), k_kc_tile_sums, grid_for(ntiles, 1, 65536), 256, (const uint32_t *)d_deg, nn, ntiles, d_tiles);
-    GPU_LAUNCH(cs.stream(), k_kc_scan_tiles, 1, 64, d_tiles, ntiles, d_off + nn);
-    GPU_LAUNCH(cs.stream(), k_kc_scan_write, grid_for(ntiles, 1, 65536), 256, (const uint32_t *)d_deg, nn, ntiles, (const unsigned long long *)d_tiles, d_off);
-    unsigned long long entries = 0;
-    int e = cs.read_back(&entries, d_off + nn, sizeof(entries));
+    uint32_t *d_adj = nullptr;
+    uint64_t entries = 0;  // (2 |E(G)|: not needed here)
+    int e = cs.symmetric_adjacency(P, d_deg, d_fill, d_off, d_tiles, ntiles, &d_adj, &entries);
     if (e != PPCSR_OK) return e;
-    uint32_t *d_adj = cs.alloc<uint32_t>("d_adj", std::max<uint64_t>(entries, 1));
-    if (cs.rc != PPCSR_OK) return cs.rc;
-    GPU_LAUNCH(cs.stream(), k_kc_fill, cs.pass_grid(), 256, tab, P, nn, (const unsigned long long *)d_off, d_fill, d_adj);
     // stage 2
     uint32_t h_cnt[4] = {0, 0, 0, 0};  // (host copy of the three words of the counter block that are in use, padded to 16 bytes)
     uint32_t *cur = d_f0, *nxt = d_f1;
@@ -473,6 +487,168 @@ int Engine::kcore_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, u
   if (core && nn) GCHK(gpu::d2h(core, d_core, (uint64_t)nn * sizeof(uint32_t), cs.stream()));
   if (kmax) *kmax = top;
   return cs.done(device_ms);
+}
+
+// Greedy colouring in a fixed vertex order (pma_colour.h).  Stage 1 is k-core's (symmetric_adjacency); then the keys of the
+// order, one streaming pass for pred[], the first frontier, and one round per level of the order's DAG: a launch, one host
+// read of the small counter block and, if the round deferred long lists, k_col_long and a second read.  A vertex enters one
+// frontier, so more rounds than vertices is reported as an error instead of spinning, and so is a loop that ends with
+// vertices left over.  device_ms covers the whole call, as kcore_over's.  A failed allocation is PPCSR_ENOMEM here.
+int Engine::colouring_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t order, uint64_t seed, uint32_t *colour,
+                           uint32_t *ncolours, double *device_ms) {
+  const uint32_t nn = total_n;
+  if (order > kColOrderId) return fail(PPCSR_EINVAL, "colouring: unknown vertex order");  // (refused before the device is even selected)
+  ConsumerScope cs(this, PPCSR_ENOMEM);
+  const int rc = cs.open(parts, P, nn);
+  if (rc != PPCSR_OK) return rc;
+  const ConsumerPart *tab = cs.table();
+  const uint64_t words = cs.words();
+  const uint32_t ntiles = (uint32_t)(((uint64_t)nn + kKcTile - 1) / kKcTile);
+  uint32_t *d_deg = cs.alloc<uint32_t>("d_deg", words), *d_col = cs.alloc<uint32_t>("d_col", words), *d_fill = cs.alloc<uint32_t>("d_fill", words);
+  uint32_t *d_pred = cs.alloc<uint32_t>("d_pred", words);
+  uint32_t *d_f0 = cs.alloc<uint32_t>("d_f0", words), *d_f1 = cs.alloc<uint32_t>("d_f1", words);  // (a vertex enters one frontier once: no list exceeds n)
+  uint32_t *d_long = cs.alloc<uint32_t>("d_long", words);
+  unsigned long long *d_key = cs.alloc<unsigned long long>("d_key", words);
+  unsigned long long *d_off = cs.alloc<unsigned long long>("d_off", words + 1), *d_tiles = cs.alloc<unsigned long long>("d_tiles", std::max<uint64_t>(ntiles, 1));
+  uint32_t *d_cnt = cs.alloc<uint32_t>("d_cnt", kColCntWords);
+  if (cs.rc != PPCSR_OK) return cs.rc;
+  const uint32_t window = p_->colour_window;
+  uint64_t ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t &rounds = ctr[0], &launches = ctr[6], &reads = ctr[7];
+  uint32_t h_cnt[4] = {0, 0, 0, 0};  // next frontier, deferred lists, extra window passes, the largest colour
+  const auto read_cnt = [&](uint32_t nwords) {
+    reads++;
+    return cs.read_back(h_cnt, d_cnt, nwords * sizeof(uint32_t));
+  };
+  cs.start();
+  if (nn) {
+    // stage 1: deg[], off[] (off[nn] = 2 |E(G)|), adj[]
+    GCHK(gpu::dset(d_deg, 0, words * sizeof(uint32_t), cs.stream()));
+    GCHK(gpu::dset(d_fill, 0, words * sizeof(uint32_t), cs.stream()));
+    GCHK(gpu::dset(d_pred, 0, words * sizeof(uint32_t), cs.stream()));
+    GCHK(gpu::dset(d_cnt, 0, kColCntWords * sizeof(uint32_t), cs.stream()));
+    GPU_LAUNCH(cs.stream(), k_kc_init, cs.vert_grid(), 256, d_col, nn);
+    uint32_t *d_adj = nullptr;
+    int e = cs.symmetric_adjacency(P, d_deg, d_fill, d_off, d_tiles, ntiles, &d_adj, &ctr[3]);
+    if (e != PPCSR_OK) return e;
+    reads++;
+    // the order, pred[] and the first frontier
+    GPU_LAUNCH(cs.stream(), k_col_keys, cs.vert_grid(), 256, order, (unsigned long long)seed, (const uint32_t *)d_deg, nn, d_key);
+    GPU_LAUNCH(cs.stream(), k_col_pred, cs.pass_grid(), 256, tab, P, nn, (const unsigned long long *)d_key, d_pred);
+    uint32_t *cur = d_f0, *nxt = d_f1;
+    GPU_LAUNCH(cs.stream(), k_col_collect, grid_for(nn, 256), 256, (const uint32_t *)d_pred, nn, cur, d_cnt);
+    launches += 9;  // (k_kc_init, the five of stage 1, these three)
+    e = read_cnt(1);
+    if (e != PPCSR_OK) return e;
+    uint64_t done = 0;
+    for (uint32_t nfront = h_cnt[0]; nfront > 0; nfront = h_cnt[0]) {
+      if (rounds == nn) return fail(PPCSR_EHIP, "colouring: more rounds than the graph has vertices");
+      rounds++;
+      done += nfront;
+      ctr[1] = std::max<uint64_t>(ctr[1], nfront);
+      GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), cs.stream()));
+      GPU_LAUNCH(cs.stream(), k_col_round, cs.list_grid(nfront), 256, (const unsigned long long *)d_off, (const uint32_t *)d_adj, (const uint32_t *)cur,
+                 nfront, d_col, d_pred, nxt, d_long, d_cnt);
+      launches++;
+      e = read_cnt(4);
+      if (e != PPCSR_OK) return e;
+      if (h_cnt[1]) {  // lists beyond one wave's reach: a workgroup each, appending to the same frontier
+        ctr[2] += h_cnt[1];
+        GPU_LAUNCH(cs.stream(), k_col_long, grid_for(h_cnt[1], 1, 1024), 256, (const unsigned long long *)d_off, (const uint32_t *)d_adj,
+                   (const uint32_t *)d_long, h_cnt[1], window, d_col, d_pred, nxt, d_cnt);
+        launches++;
+        e = read_cnt(4);
+        if (e != PPCSR_OK) return e;
+      }
+      std::swap(cur, nxt);
+    }
+    if (done != nn) return fail(PPCSR_EHIP, "colouring: the rounds ended with vertices left uncoloured");
+    ctr[4] = (uint64_t)h_cnt[3] + 1;
+    ctr[5] = h_cnt[2];
+  }
+  cs.stop();
+  if (colour && nn) GCHK(gpu::d2h(colour, d_col, (uint64_t)nn * sizeof(uint32_t), cs.stream()));
+  const int done = cs.done(device_ms);
+  if (done != PPCSR_OK) return done;
+  if (ncolours) *ncolours = (uint32_t)ctr[4];
+  for (int i = 0; i < 8; i++) p_->colour_ctr[i] = ctr[i];
+  return PPCSR_OK;
+}
+int Engine::colouring_counters(uint64_t out[8]) {
+  if (!out) return fail(PPCSR_EINVAL, "colouring counters: no output");
+  for (int i = 0; i < 8; i++) out[i] = p_->colour_ctr[i];
+  return PPCSR_OK;
+}
+
+// The lexicographically first maximal independent set in the same vertex orders (pma_colour.h), in place: per round one
+// streaming pass, one vertex launch and one host read of the striped count (vertices left, vertices that joined).  Every round
+// decides a vertex, and the bound the header documents is 2 n + 1 rounds: past it an error, not a spin.
+int Engine::mis_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t order, uint64_t seed, uint8_t *in_set, uint64_t *size,
+                     double *device_ms) {
+  const uint32_t nn = total_n;
+  if (order > kColOrderId) return fail(PPCSR_EINVAL, "mis: unknown vertex order");
+  ConsumerScope cs(this, PPCSR_ENOMEM);
+  const int rc = cs.open(parts, P, nn);
+  if (rc != PPCSR_OK) return rc;
+  const ConsumerPart *tab = cs.table();
+  const uint64_t words = cs.words();
+  unsigned long long *d_key = cs.alloc<unsigned long long>("d_key", words);
+  uint8_t *d_state = cs.alloc<uint8_t>("d_state", words), *d_out = cs.alloc<uint8_t>("d_out", words);
+  uint32_t *d_blocked = cs.alloc<uint32_t>("d_blocked", words);
+  uint32_t *d_deg = order == kColOrderDegree ? cs.alloc<uint32_t>("d_deg", words) : nullptr;
+  ConsumerScope::Striped<unsigned long long, kMisStripeWords> cnt(cs, "d_cnt");
+  unsigned long long *const d_cnt = cnt.dev;
+  if (cs.rc != PPCSR_OK) return cs.rc;
+  uint64_t ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t &rounds = ctr[0], &passes = ctr[1], &members = ctr[4], &launches = ctr[6], &reads = ctr[7];
+  cs.start();
+  if (nn) {
+    if (d_deg) {
+      GCHK(gpu::dset(d_deg, 0, words * sizeof(uint32_t), cs.stream()));
+      GPU_LAUNCH(cs.stream(), k_kc_degree, cs.pass_grid(), 256, tab, P, nn, d_deg);
+      ctr[5]++;
+      launches++;
+    }
+    GPU_LAUNCH(cs.stream(), k_col_keys, cs.vert_grid(), 256, order, (unsigned long long)seed, (const uint32_t *)d_deg, nn, d_key);
+    launches++;
+    GCHK(gpu::dset(d_state, kMisUndecided, words, cs.stream()));
+    GCHK(gpu::dset(d_out, 0, words, cs.stream()));
+    GCHK(gpu::dset(d_blocked, 0, words * sizeof(uint32_t), cs.stream()));  // (rounds count from 1)
+    for (uint64_t left = nn; left > 0;) {
+      if (rounds > 2 * (uint64_t)nn) return fail(PPCSR_EHIP, "mis: more than 2 n + 1 rounds");
+      rounds++;
+      GCHK(cnt.zero());
+      GPU_LAUNCH(cs.stream(), k_mis_pass, cs.pass_grid(), 256, tab, P, nn, (uint32_t)rounds, (const unsigned long long *)d_key,
+                 (const uint8_t *)d_state, d_out, d_blocked);
+      GPU_LAUNCH(cs.stream(), k_mis_step, cs.vert_grid(), 256, nn, (uint32_t)rounds, d_state, (const uint8_t *)d_out, (const uint32_t *)d_blocked,
+                 d_cnt);
+      passes++;
+      launches += 2;
+      const int e = cnt.read();
+      if (e != PPCSR_OK) return e;
+      reads++;
+      const uint64_t all = cnt.sum(), joined = all >> 32, undecided = all & 0xFFFFFFFFull;
+      if (undecided >= left) return fail(PPCSR_EHIP, "mis: a round decided nothing");
+      members += joined;
+      left = undecided;
+      if (rounds == 1) {
+        ctr[2] = joined;
+        ctr[3] = undecided;
+      }
+    }
+  }
+  cs.stop();
+  if (in_set && nn) GCHK(gpu::d2h(in_set, d_state, (uint64_t)nn, cs.stream()));
+  const int done = cs.done(device_ms);
+  if (done != PPCSR_OK) return done;
+  if (size) *size = members;
+  for (int i = 0; i < 8; i++) p_->mis_ctr[i] = ctr[i];
+  return PPCSR_OK;
+}
+int Engine::mis_counters(uint64_t out[8]) {
+  if (!out) return fail(PPCSR_EINVAL, "mis counters: no output");
+  for (int i = 0; i < 8; i++) out[i] = p_->mis_ctr[i];
+  return PPCSR_OK;
 }
 
 // Strongly connected components (pma_scc.h): trim to a fixpoint, forward-backward reach from one pivot, then colouring rounds

@@ -34,5 +34,6 @@
 #include "pma_isect_probe.h"
 #include "pma_query.h"
 #include "pma_sample.h"
+#include "pma_colour.h"
 #include "pma_msbfs.h"
 #include "pma_exchange.h"

@@ -180,5 +180,11 @@ inline unsigned long long atomic_or_u64(unsigned long long *p, unsigned long lon
 #else
 PMA_DEV unsigned long long atomic_or_u64(unsigned long long *p, unsigned long long v) { return atomicOr(p, v); }
 #endif
+// OR into a 64-bit word of LDS, nothing back (ds_or_b64: the forbidden-colour sets of pma_colour.h)
+#if defined(PPCSR_SIM)
+inline void lds_or_u64(unsigned long long *p, unsigned long long v) { *p |= v; }
+#else
+PMA_DEV void lds_or_u64(unsigned long long *p, unsigned long long v) { (void)atomicOr(p, v); }
+#endif
 }  // namespace wv
 }  // namespace ppcsr
