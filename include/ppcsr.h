@@ -232,6 +232,51 @@ int ppcsr_mis(ppcsr_t h, uint32_t order, uint64_t seed, uint8_t *in_set, uint64_
  * EINVAL: null handle or out. */
 int ppcsr_debug_colouring_counters(ppcsr_t h, uint64_t out[8]);
 int ppcsr_debug_mis_counters(ppcsr_t h, uint64_t out[8]);
+/* Label-propagation communities and modularity, in the same undirected graph G (the paragraph above ppcsr_colouring): {a, b},
+ * a < b < n, is an edge iff the pair (a, b) is stored.  The WEIGHT of {a, b} is that stored pair's value with
+ * PPCSR_COMMUNITY_WEIGHTED in flags and 1 without it (a stored value lies in [1, 2^32 - 2]); pairs with src > dst, self-loops
+ * and destinations >= n play no part.
+ * Schedule.  colour[] is the answer of ppcsr_colouring(order, seed).  CLASS c is the set of vertices with colour c and at least
+ *   one neighbour.  A SWEEP runs the classes 0, 1, ..., C - 1 in turn; a STEP handles one class.
+ * Step.  For every v of the class, score(l) = the sum of the weights of v's edges to neighbours that carry label l, a 64-bit
+ *   sum.  M = the largest score.  v keeps its label if its own label scores M; otherwise it takes the SMALLEST label that
+ *   scores M.  A class is an independent set, so a step reads no label that it writes: the result is that of the sequential
+ *   sweep in (colour, id) order and is unique for one order and seed.
+ * Start and end.  Labels start at init[v] (n entries; an entry >= n is EINVAL and nothing is written); init == NULL means
+ *   label[v] = v.  Passing the previous answer as init is the warm start after a batch of updates.  The call ends after the
+ *   first sweep that changes no label, or after max_sweeps sweeps (0: until convergence).  A vertex without a neighbour keeps
+ *   its label.
+ * Outputs.  labels[v] (n entries, may be NULL): the raw labels, vertex ids.  *ncommunities: the number of distinct values in
+ *   labels.  *sweeps: the sweeps run, the last, changeless one included (0 only for n = 0).  Each may be NULL, not all three.
+ * Termination.  A vertex changes its label only to one of strictly larger score, and the members of a class are not adjacent,
+ *   so no neighbour moves in the same step: every change raises the total weight of the edges whose two ends agree by at
+ *   least 1, and that total is bounded by W(G), the weight of all edges.  So at most W(G) changes happen and a call without
+ *   max_sweeps ends after at most W(G) + 1 sweeps (checked, not trusted: past it an error).  This is the semi-synchronous
+ *   scheme of Cordasco and Gargano (2010) on the label propagation of Raghavan, Albert and Kumara (2007); a fully synchronous
+ *   update can flip for ever on a bipartite graph, this one cannot.
+ * Modularity (Newman and Girvan 2004) of ANY labels[] (n entries, each < n, else EINVAL):
+ *   out[0] = 2 W(G)                                          out[1] = sum over communities c of 2 in_c: the weight inside, doubled
+ *   out[2], out[3] = the low and the high word of S = sum over c of tot_c^2, tot_c = the sum of the weighted degrees of c
+ *   *q = out[1] / out[0] - S / out[0]^2, formed in doubles on the host from these exact integers; 0 when out[0] is 0.
+ *   out and q may each be NULL, not both.  The sums are 64-bit: W(G) < 2^63 is the caller's to keep.
+ * Same contract as every consumer: synchronous, sees every batch applied before it, writes nothing to the graph, device_ms may
+ * be NULL, answers in the sequential regime (stats.narrow == 0).  EINVAL, refused before the device is selected: null handle,
+ * an unknown order, flag bits other than PPCSR_COMMUNITY_WEIGHTED, a bad init / labels entry, NULL labels for modularity, all
+ * outputs NULL.  ENOMEM: a device allocation of the call failed (nothing written).
+ * Cost.  ppcsr_colouring's, then per sweep at most three launches per class (lists of at most 64 entries, of at most 512, and
+ * longer ones: csrc/pma_community.h) and one host read. */
+#define PPCSR_COMMUNITY_WEIGHTED 1u
+int ppcsr_label_propagation(ppcsr_t h, uint32_t order, uint64_t seed, uint32_t flags, uint32_t max_sweeps, const uint32_t *init, uint32_t *labels,
+                            uint64_t *ncommunities, uint32_t *sweeps, double *device_ms);
+int ppcsr_modularity(ppcsr_t h, const uint32_t *labels, uint32_t flags, uint64_t out[4], double *q, double *device_ms);
+/* Debugging: what the last label_propagation call on this engine did (for a pppcsr_ call: the first partition's engine).
+ *   out[0] sweeps                                            out[1] classes that are not empty
+ *   out[2] label changes in all                              out[3] label changes of the last sweep (0 iff converged)
+ *   out[4] communities                                       out[5] vertices with a list beyond 512 entries (a workgroup each)
+ *   out[6] hash passes of those beyond each one's first, summed over the sweeps ("lp_table_slots"; depends on the scheme)
+ *   out[7] launches
+ * [0] - [5] are functions of the graph, the order, the flags and init.  EINVAL: null handle or out. */
+int ppcsr_debug_community_counters(ppcsr_t h, uint64_t out[8]);
 /* Strongly connected components, over exactly the edge set ppcsr_bfs walks (live non-sentinel slots, slot N - 1 excluded, local
  * src < n, destinations >= n skipped), taken as DIRECTED; the edge values play no part.  A self-loop is an ordinary stored edge
  * that changes nothing: a vertex whose only cycle is its self-loop is an SCC of one vertex.
@@ -423,6 +468,8 @@ int ppcsr_stats(ppcsr_t h, ppcsr_stats_t *out);
  *   consumers  "msbfs_look" (0: the streaming pass of ppcsr_multi_bfs issues its ORs without first looking at next[w]; default 1),
  *              "colour_window" (test hook: colours per pass of ppcsr_colouring's long-list kernel over a list beyond 4096 entries;
  *              a multiple of 64 in [64, 32768], anything else is EINVAL; default 32768)
+ *              "lp_table_slots" (test hook: slots of the label table a workgroup of ppcsr_label_propagation keeps for a list beyond
+ *              512 entries; a power of two in [64, 4096], anything else is EINVAL; default 4096)
  *   measuring  "profile" (1: HIP events around every round kernel, reported through ppcsr_stats), "diag" (1: why updates
  *              did not commit, per epoch, on stderr; 2: also a per-update dependency trace, PPCSR_DIAG_DUMP = file), "marker" (marker kernels for profile cuts), "test_block_rebalance"
  *   reads      test hooks that move the seams of the batched reads (defaults = the shipped sizes; values in [1, 2^32]):
@@ -587,6 +634,12 @@ int pppcsr_kcore(pppcsr_t h, uint32_t *core, uint32_t *kmax, double *device_ms);
  * one device.  ENOMEM: a device allocation of the call failed (nothing written). */
 int pppcsr_colouring(pppcsr_t h, uint32_t order, uint64_t seed, uint32_t *colour, uint32_t *ncolours, double *device_ms);
 int pppcsr_mis(pppcsr_t h, uint32_t order, uint64_t seed, uint8_t *in_set, uint64_t *size, double *device_ms);
+/* ppcsr_label_propagation / ppcsr_modularity over the GLOBAL vertex ids (init, labels: pppcsr_get_n entries; the colours are
+ * pppcsr_colouring's).  Same definitions, same statuses; as for every pppcsr_ consumer, EINVAL for a partition not resident in
+ * this process and EUNSUPPORTED for partitions on more than one device.  The answers do not depend on the partitioning. */
+int pppcsr_label_propagation(pppcsr_t h, uint32_t order, uint64_t seed, uint32_t flags, uint32_t max_sweeps, const uint32_t *init, uint32_t *labels,
+                             uint64_t *ncommunities, uint32_t *sweeps, double *device_ms);
+int pppcsr_modularity(pppcsr_t h, const uint32_t *labels, uint32_t flags, uint64_t out[4], double *q, double *device_ms);
 /* ppcsr_scc over the GLOBAL vertex ids (labels: pppcsr_get_n entries), one device call over every partition's array: an SCC may
  * span partitions, and the result does not depend on the partitioning.  Same contract as pppcsr_components; a partition in the
  * sequential regime is answered.  EINVAL: null handle, labels and count both NULL, or a partition not resident in this

@@ -82,11 +82,13 @@ EXPORTED = [
     "ppcsr_random_walks", "ppcsr_random_walks_device", "pppcsr_random_walks", "ppcsr_degrees", "pppcsr_degrees", "ppcsr_debug_mulhi",
     "ppcsr_multi_bfs", "pppcsr_multi_bfs", "ppcsr_debug_multi_bfs_counters", "ppcsr_debug_dup_slot_entries",
     "ppcsr_colouring", "pppcsr_colouring", "ppcsr_mis", "pppcsr_mis", "ppcsr_debug_colouring_counters", "ppcsr_debug_mis_counters",
+    "ppcsr_label_propagation", "pppcsr_label_propagation", "ppcsr_modularity", "pppcsr_modularity", "ppcsr_debug_community_counters",
 ]
 
 NO_PATH = 0xFFFFFFFFFFFFFFFF  # PPCSR_NO_PATH: what sssp reports for a vertex no path reaches
 NO_EDGE = 0xFFFFFFFF  # PPCSR_NO_EDGE: what lookup_edges reports for a pair that is not an edge
 ORDERS = {"random": 0, "degree": 1, "id": 2}  # PPCSR_ORDER_*: the vertex orders of colouring / mis
+COMMUNITY_WEIGHTED = 1  # PPCSR_COMMUNITY_WEIGHTED: label_propagation / modularity weigh an edge by its stored value
 NO_VERTEX = 0xFFFFFFFF  # PPCSR_NO_VERTEX: what sample_neighbours / random_walks report where there is nothing to pick from
 
 _LIBS = {}
@@ -196,6 +198,12 @@ def load_library(path=None):
     for name in ("ppcsr_mis", "pppcsr_mis"):
         getattr(L, name).argtypes = [c_vp, c_u32, c_u64, c_vp, ctypes.POINTER(c_u64), ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_debug_colouring_counters.argtypes = [c_vp, c_vp]
+    for name in ("ppcsr_label_propagation", "pppcsr_label_propagation"):
+        getattr(L, name).argtypes = [c_vp, c_u32, c_u64, c_u32, c_u32, c_vp, c_vp, ctypes.POINTER(c_u64), ctypes.POINTER(c_u32),
+                                     ctypes.POINTER(ctypes.c_double)]
+    for name in ("ppcsr_modularity", "pppcsr_modularity"):
+        getattr(L, name).argtypes = [c_vp, c_vp, c_u32, c_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
+    L.ppcsr_debug_community_counters.argtypes = [c_vp, c_vp]
     L.ppcsr_debug_mis_counters.argtypes = [c_vp, c_vp]
     L.ppcsr_bulk_build.argtypes = [c_vp, c_vp, c_u64, ctypes.POINTER(ctypes.c_double)]
     L.ppcsr_bfs.argtypes = [c_vp, c_u32, c_vp, ctypes.POINTER(ctypes.c_double)]
@@ -370,6 +378,32 @@ class _Consumers:
         size = c_u64()
         ms = self._consumer("mis", ORDERS.get(order, order), seed, mask.ctypes.data, ctypes.byref(size))
         return (mask.astype(bool), size.value, ms) if with_ms else (mask.astype(bool), size.value)
+
+    def label_propagation(self, order="random", seed=0, weighted=False, max_sweeps=0, init=None, with_ms=False):
+        """(labels, ncommunities, sweeps[, ms]): label-propagation communities of the graph colouring() colours, class by class of
+        colouring(order, seed): a vertex takes the label of largest weight among its neighbours (its own on a tie, else the
+        smallest), until a sweep changes nothing or max_sweeps (0: none).  labels (uint32, global ids) start at init (the warm
+        start: the previous answer) or at the vertex ids; weighted: an edge counts with its stored value"""
+        labels = np.empty(self.get_n(), np.uint32)
+        start = None if init is None else np.ascontiguousarray(init, np.uint32)
+        if start is not None and len(start) != len(labels):
+            raise ValueError("init needs one label per vertex")
+        ncom, sweeps = c_u64(), c_u32()
+        ms = self._consumer("label_propagation", ORDERS.get(order, order), seed, COMMUNITY_WEIGHTED if weighted else 0, max_sweeps,
+                            None if start is None else start.ctypes.data, labels.ctypes.data, ctypes.byref(ncom), ctypes.byref(sweeps))
+        return (labels, ncom.value, sweeps.value, ms) if with_ms else (labels, ncom.value, sweeps.value)
+
+    def modularity(self, labels, weighted=False, with_ms=False):
+        """(q, words[, ms]): Newman-Girvan modularity of any labels (one per vertex, each below n) in the same graph.  words =
+        uint64[4]: 2 W(G), twice the weight inside communities, and the low and high word of the sum of tot_c^2 — exact; q is
+        formed from them in doubles"""
+        lab = np.ascontiguousarray(labels, np.uint32)
+        if len(lab) != self.get_n():
+            raise ValueError("modularity needs one label per vertex")
+        words = np.zeros(4, np.uint64)
+        q = ctypes.c_double()
+        ms = self._consumer("modularity", lab.ctypes.data, COMMUNITY_WEIGHTED if weighted else 0, words.ctypes.data, ctypes.byref(q))
+        return (q.value, words, ms) if with_ms else (q.value, words)
 
     def scc(self, with_ms=False):
         """(labels, count[, ms]): strongly connected components of the stored DIRECTED graph: the smallest vertex id of every
@@ -665,6 +699,13 @@ class PCSR(_Consumers):
         self._chk(self.L.ppcsr_debug_colouring_counters(self.h, out.ctypes.data))
         return out
 
+    def debug_community_counters(self):
+        """Debugging (ppcsr_debug_community_counters): uint64[8] of the last label_propagation call on this engine — sweeps,
+        classes, label changes, changes of the last sweep, communities, workgroup-tier vertices, extra hash passes, launches"""
+        out = np.zeros(8, np.uint64)
+        self._chk(self.L.ppcsr_debug_community_counters(self.h, out.ctypes.data))
+        return out
+
     def debug_mis_counters(self):
         """Debugging (ppcsr_debug_mis_counters): uint64[8] of the last mis call on this engine — rounds, streaming passes, members
         and undecided after round 1, size, degree passes, launches, host reads"""
@@ -876,6 +917,10 @@ class PPPCSR(_Consumers):
     def debug_colouring_counters(self):
         """the counters of the last colouring call: kept by the engine that ran it, the first partition's"""
         return self.partition(0).debug_colouring_counters()
+
+    def debug_community_counters(self):
+        """the counters of the last label_propagation call: kept by the engine that ran it, the first partition's"""
+        return self.partition(0).debug_community_counters()
 
     def debug_mis_counters(self):
         """the counters of the last mis call: kept by the engine that ran it, the first partition's"""

@@ -211,6 +211,21 @@ int ppcsr_mis(ppcsr_t h, uint32_t order, uint64_t seed, uint8_t *in_set, uint64_
 }
 int ppcsr_debug_colouring_counters(ppcsr_t h, uint64_t out[8]) { H_CHECK(); return ret(h->e, h->e->colouring_counters(out)); }
 int ppcsr_debug_mis_counters(ppcsr_t h, uint64_t out[8]) { H_CHECK(); return ret(h->e, h->e->mis_counters(out)); }
+int ppcsr_label_propagation(ppcsr_t h, uint32_t order, uint64_t seed, uint32_t flags, uint32_t max_sweeps, const uint32_t *init, uint32_t *labels,
+                            uint64_t *ncommunities, uint32_t *sweeps, double *device_ms) {
+  H_CHECK();
+  if (!labels && !ncommunities && !sweeps) return bad("label propagation: null outputs");
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->label_propagation_over(&self, 1, h->e->n(), order, seed, flags, max_sweeps, init, labels, ncommunities, sweeps, device_ms));
+}
+int ppcsr_modularity(ppcsr_t h, const uint32_t *labels, uint32_t flags, uint64_t out[4], double *q, double *device_ms) {
+  H_CHECK();
+  if (!labels) return bad("modularity: no labels");
+  if (!out && !q) return bad("modularity: null outputs");
+  const ppcsr::ConsumerRef self{h->e, 0};
+  return ret(h->e, h->e->modularity_over(&self, 1, h->e->n(), labels, flags, out, q, device_ms));
+}
+int ppcsr_debug_community_counters(ppcsr_t h, uint64_t out[8]) { H_CHECK(); return ret(h->e, h->e->community_counters(out)); }
 int ppcsr_scc(ppcsr_t h, uint32_t *labels, uint64_t *count, double *device_ms) {
   H_CHECK();
   if (!labels && !count) return bad("scc: null outputs");
@@ -870,6 +885,23 @@ int pppcsr_mis(pppcsr_t h, uint32_t order, uint64_t seed, uint8_t *in_set, uint6
   if (!in_set && !size) return bad("mis: null outputs");
   if (order > 2u) return bad("mis: unknown vertex order");
   return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) { return ret(e, e->mis_over(r, P, n, order, seed, in_set, size, device_ms)); });
+}
+int pppcsr_label_propagation(pppcsr_t h, uint32_t order, uint64_t seed, uint32_t flags, uint32_t max_sweeps, const uint32_t *init, uint32_t *labels,
+                             uint64_t *ncommunities, uint32_t *sweeps, double *device_ms) {
+  PP_CHECK();
+  if (!labels && !ncommunities && !sweeps) return bad("label propagation: null outputs");
+  if (order > 2u) return bad("label propagation: unknown vertex order");
+  if (flags & ~PPCSR_COMMUNITY_WEIGHTED) return bad("label propagation: unknown flag bits");
+  return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) {
+    return ret(e, e->label_propagation_over(r, P, n, order, seed, flags, max_sweeps, init, labels, ncommunities, sweeps, device_ms));
+  });
+}
+int pppcsr_modularity(pppcsr_t h, const uint32_t *labels, uint32_t flags, uint64_t out[4], double *q, double *device_ms) {
+  PP_CHECK();
+  if (!labels) return bad("modularity: no labels");
+  if (!out && !q) return bad("modularity: null outputs");
+  if (flags & ~PPCSR_COMMUNITY_WEIGHTED) return bad("modularity: unknown flag bits");
+  return over_parts(h, [&](Engine *e, Refs r, uint32_t P, uint32_t n) { return ret(e, e->modularity_over(r, P, n, labels, flags, out, q, device_ms)); });
 }
 int pppcsr_scc(pppcsr_t h, uint32_t *labels, uint64_t *count, double *device_ms) {
   PP_CHECK();

@@ -129,6 +129,8 @@ struct Engine::Impl {
   uint64_t msbfs_ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the same for multi_bfs_over (ppcsr_debug_multi_bfs_counters)
   uint64_t colour_ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the same for colouring_over (ppcsr_debug_colouring_counters)
   uint64_t mis_ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // the same for mis_over (ppcsr_debug_mis_counters)
+  uint64_t lp_ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // the same for label_propagation_over (ppcsr_debug_community_counters)
+  uint32_t lp_table_slots = kLpTableMax;  // slots of k_lp_step_block's label table (test hook: 64 forces the hash passes)
   uint32_t colour_window = kColWindowMax;  // colours per pass of k_col_long (test hook: 64 exercises the window loop)
   uint32_t msbfs_look = 1;  // multi_bfs_over's pass looks at next[w] before it issues an OR (0: the variant tools/multibfs_bench.py measures)
   // dirty tags: writers stamp View::ldirty / vdirty with `serial`; every snapshot synchronisation advances it
@@ -620,6 +622,11 @@ int Engine::set_option(const char *key, int64_t value) {
   if (k == "colour_window") {  // test hook: colours per pass of k_col_long over a long list
     if (value < 64 || value > (int64_t)kColWindowMax || value % 64) return fail(PPCSR_EINVAL, "colour_window must be a multiple of 64 in [64, 32768]");
     p.colour_window = (uint32_t)value;
+    return PPCSR_OK;
+  }
+  if (k == "lp_table_slots") {  // test hook: slots of the label table of k_lp_step_block
+    if (value < 64 || value > (int64_t)kLpTableMax || (value & (value - 1))) return fail(PPCSR_EINVAL, "lp_table_slots must be a power of two in [64, " + std::to_string(kLpTableMax) + "]");
+    p.lp_table_slots = (uint32_t)value;
     return PPCSR_OK;
   }
   if (k == "region_slots") {

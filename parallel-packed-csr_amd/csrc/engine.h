@@ -116,6 +116,17 @@ class Engine {
   int mis_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t order, uint64_t seed, uint8_t *in_set, uint64_t *size,
                double *device_ms);
   int colouring_counters(uint64_t out[8]);
+  // label-propagation communities under the colouring's schedule, and the modularity of any labels (pma_community.h; the
+  // definitions: include/ppcsr.h), in either regime.  order / flags: anything unknown, and an init entry >= total_n, is refused
+  // before the device is selected.  init (total_n entries) may be null: label[v] = v.  labels (total_n entries), *ncommunities
+  // and *sweeps may each be null.  modularity_over: labels (total_n entries, each < total_n), out[4] and *q (either may be null).
+  // community_counters: what the last label_propagation_over on this engine did (ppcsr_debug_community_counters)
+  int label_propagation_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t order, uint64_t seed, uint32_t flags,
+                             uint32_t max_sweeps, const uint32_t *init, uint32_t *labels, uint64_t *ncommunities, uint32_t *sweeps,
+                             double *device_ms);
+  int modularity_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const uint32_t *labels, uint32_t flags, uint64_t out[4], double *q,
+                      double *device_ms);
+  int community_counters(uint64_t out[8]);
   int mis_counters(uint64_t out[8]);
   // strongly connected components (pma_scc.h), in either regime: labels[v] = smallest vertex id of v's SCC (total_n entries, may
   // be null), *count = number of SCCs (may be null).  scc_counters: what the last scc_over on this engine did

@@ -1,5 +1,5 @@
 // Host drivers of the graph-algorithm consumers (kernels: pma_consumer.h, pma_scan.h, pma_paths.h, pma_cores.h, pma_centrality.h,
-// pma_scc.h, pma_msf.h, pma_intersect.h, pma_truss.h, pma_sample.h, pma_msbfs.h, pma_colour.h).  Included at the end of engine.cc: part of the engine's single translation unit, in the library
+// pma_scc.h, pma_msf.h, pma_intersect.h, pma_truss.h, pma_sample.h, pma_msbfs.h, pma_colour.h, pma_community.h).  Included at the end of engine.cc: part of the engine's single translation unit, in the library
 // (csrc/ppcsr_hip.hip) and in the emulator (tests/hostsim/ppcsr_sim.cpp) alike.
 namespace ppcsr {
 
@@ -228,6 +228,90 @@ struct Engine::ConsumerScope {
     GPU_LAUNCH(p.stream, k_kc_fill, pass_grid(), 256, tab_, P, nn, (const unsigned long long *)d_off, d_fill, d_adj);
     *adj = d_adj;
     *entries = total;
+    return PPCSR_OK;
+  }
+
+  // The device side of colouring_over, shared with label_propagation_over, which needs the adjacency and the colours ON THE
+  // DEVICE: the buffers (colour_alloc: eleven allocations, in this order), and from the cleared buffers to the last round
+  // (colour_run; n > 0).  Afterwards d_deg, d_off, d_adj (2 |E(G)| = ctr[3] entries) and d_col hold the graph and the answer;
+  // d_fill equals d_deg; d_pred, d_f0, d_f1, d_long, d_key, d_tiles and d_cnt are free.  ctr: the counters of
+  // ppcsr_debug_colouring_counters.
+  struct ColourStage {
+    uint32_t *d_deg = nullptr, *d_col = nullptr, *d_fill = nullptr, *d_pred = nullptr, *d_f0 = nullptr, *d_f1 = nullptr, *d_long = nullptr;
+    unsigned long long *d_key = nullptr, *d_off = nullptr, *d_tiles = nullptr;
+    uint32_t *d_cnt = nullptr, *d_adj = nullptr;
+    uint32_t ntiles = 0;
+    uint64_t ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  };
+  void colour_alloc(ColourStage *st) {
+    const uint64_t w = words();
+    st->ntiles = (uint32_t)(((uint64_t)n_ + kKcTile - 1) / kKcTile);
+    st->d_deg = alloc<uint32_t>("d_deg", w), st->d_col = alloc<uint32_t>("d_col", w), st->d_fill = alloc<uint32_t>("d_fill", w);
+    st->d_pred = alloc<uint32_t>("d_pred", w);
+    st->d_f0 = alloc<uint32_t>("d_f0", w), st->d_f1 = alloc<uint32_t>("d_f1", w);  // (a vertex enters one frontier once: no list exceeds n)
+    st->d_long = alloc<uint32_t>("d_long", w);
+    st->d_key = alloc<unsigned long long>("d_key", w);
+    st->d_off = alloc<unsigned long long>("d_off", w + 1), st->d_tiles = alloc<unsigned long long>("d_tiles", std::max<uint64_t>(st->ntiles, 1));
+    st->d_cnt = alloc<uint32_t>("d_cnt", kColCntWords);
+  }
+  int colour_run(uint32_t P, uint32_t order, uint64_t seed, ColourStage *st) {
+    const uint32_t nn = n_;
+    const uint64_t w = words();
+    uint32_t *const d_deg = st->d_deg, *const d_col = st->d_col, *const d_fill = st->d_fill, *const d_pred = st->d_pred, *const d_long = st->d_long;
+    uint32_t *const d_cnt = st->d_cnt;
+    unsigned long long *const d_key = st->d_key, *const d_off = st->d_off;
+    const uint32_t window = p.colour_window;
+    uint64_t(&ctr)[8] = st->ctr;
+    uint64_t &rounds = ctr[0], &launches = ctr[6], &reads = ctr[7];
+    uint32_t h_cnt[4] = {0, 0, 0, 0};  // next frontier, deferred lists, extra window passes, the largest colour
+    const auto read_cnt = [&](uint32_t nwords) {
+      reads++;
+      return read_back(h_cnt, d_cnt, nwords * sizeof(uint32_t));
+    };
+    // stage 1: deg[], off[] (off[nn] = 2 |E(G)|), adj[]
+    GCHK(gpu::dset(d_deg, 0, w * sizeof(uint32_t), p.stream));
+    GCHK(gpu::dset(d_fill, 0, w * sizeof(uint32_t), p.stream));
+    GCHK(gpu::dset(d_pred, 0, w * sizeof(uint32_t), p.stream));
+    GCHK(gpu::dset(d_cnt, 0, kColCntWords * sizeof(uint32_t), p.stream));
+    GPU_LAUNCH(p.stream, k_kc_init, vert_grid(), 256, d_col, nn);
+    uint32_t *d_adj = nullptr;
+    int e = symmetric_adjacency(P, d_deg, d_fill, d_off, st->d_tiles, st->ntiles, &d_adj, &ctr[3]);
+    if (e != PPCSR_OK) return e;
+    st->d_adj = d_adj;
+    reads++;
+    // the order, pred[] and the first frontier
+    GPU_LAUNCH(p.stream, k_col_keys, vert_grid(), 256, order, (unsigned long long)seed, (const uint32_t *)d_deg, nn, d_key);
+    GPU_LAUNCH(p.stream, k_col_pred, pass_grid(), 256, tab_, P, nn, (const unsigned long long *)d_key, d_pred);
+    uint32_t *cur = st->d_f0, *nxt = st->d_f1;
+    GPU_LAUNCH(p.stream, k_col_collect, grid_for(nn, 256), 256, (const uint32_t *)d_pred, nn, cur, d_cnt);
+    launches += 9;  // (k_kc_init, the five of stage 1, these three)
+    e = read_cnt(1);
+    if (e != PPCSR_OK) return e;
+    uint64_t done = 0;
+    for (uint32_t nfront = h_cnt[0]; nfront > 0; nfront = h_cnt[0]) {
+      if (rounds == nn) return fail(PPCSR_EHIP, "colouring: more rounds than the graph has vertices");
+      rounds++;
+      done += nfront;
+      ctr[1] = std::max<uint64_t>(ctr[1], nfront);
+      GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), p.stream));
+      GPU_LAUNCH(p.stream, k_col_round, list_grid(nfront), 256, (const unsigned long long *)d_off, (const uint32_t *)d_adj, (const uint32_t *)cur,
+                 nfront, d_col, d_pred, nxt, d_long, d_cnt);
+      launches++;
+      e = read_cnt(4);
+      if (e != PPCSR_OK) return e;
+      if (h_cnt[1]) {  // lists beyond one wave's reach: a workgroup each, appending to the same frontier
+        ctr[2] += h_cnt[1];
+        GPU_LAUNCH(p.stream, k_col_long, grid_for(h_cnt[1], 1, 1024), 256, (const unsigned long long *)d_off, (const uint32_t *)d_adj,
+                   (const uint32_t *)d_long, h_cnt[1], window, d_col, d_pred, nxt, d_cnt);
+        launches++;
+        e = read_cnt(4);
+        if (e != PPCSR_OK) return e;
+      }
+      std::swap(cur, nxt);
+    }
+    if (done != nn) return fail(PPCSR_EHIP, "colouring: the rounds ended with vertices left uncoloured");
+    ctr[4] = (uint64_t)h_cnt[3] + 1;
+    ctr[5] = h_cnt[2];
     return PPCSR_OK;
   }
 
@@ -494,6 +578,7 @@ int Engine::kcore_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, u
 // read of the small counter block and, if the round deferred long lists, k_col_long and a second read.  A vertex enters one
 // frontier, so more rounds than vertices is reported as an error instead of spinning, and so is a loop that ends with
 // vertices left over.  device_ms covers the whole call, as kcore_over's.  A failed allocation is PPCSR_ENOMEM here.
+// (The device side is ConsumerScope::colour_alloc / colour_run, which label_propagation_over runs as its first stage.)
 int Engine::colouring_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t order, uint64_t seed, uint32_t *colour,
                            uint32_t *ncolours, double *device_ms) {
   const uint32_t nn = total_n;
@@ -501,82 +586,214 @@ int Engine::colouring_over(const ConsumerRef *parts, uint32_t P, uint32_t total_
   ConsumerScope cs(this, PPCSR_ENOMEM);
   const int rc = cs.open(parts, P, nn);
   if (rc != PPCSR_OK) return rc;
-  const ConsumerPart *tab = cs.table();
-  const uint64_t words = cs.words();
-  const uint32_t ntiles = (uint32_t)(((uint64_t)nn + kKcTile - 1) / kKcTile);
-  uint32_t *d_deg = cs.alloc<uint32_t>("d_deg", words), *d_col = cs.alloc<uint32_t>("d_col", words), *d_fill = cs.alloc<uint32_t>("d_fill", words);
-  uint32_t *d_pred = cs.alloc<uint32_t>("d_pred", words);
-  uint32_t *d_f0 = cs.alloc<uint32_t>("d_f0", words), *d_f1 = cs.alloc<uint32_t>("d_f1", words);  // (a vertex enters one frontier once: no list exceeds n)
-  uint32_t *d_long = cs.alloc<uint32_t>("d_long", words);
-  unsigned long long *d_key = cs.alloc<unsigned long long>("d_key", words);
-  unsigned long long *d_off = cs.alloc<unsigned long long>("d_off", words + 1), *d_tiles = cs.alloc<unsigned long long>("d_tiles", std::max<uint64_t>(ntiles, 1));
-  uint32_t *d_cnt = cs.alloc<uint32_t>("d_cnt", kColCntWords);
+  ConsumerScope::ColourStage st;
+  cs.colour_alloc(&st);
   if (cs.rc != PPCSR_OK) return cs.rc;
-  const uint32_t window = p_->colour_window;
-  uint64_t ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  uint64_t &rounds = ctr[0], &launches = ctr[6], &reads = ctr[7];
-  uint32_t h_cnt[4] = {0, 0, 0, 0};  // next frontier, deferred lists, extra window passes, the largest colour
-  const auto read_cnt = [&](uint32_t nwords) {
-    reads++;
-    return cs.read_back(h_cnt, d_cnt, nwords * sizeof(uint32_t));
-  };
   cs.start();
   if (nn) {
-    // stage 1: deg[], off[] (off[nn] = 2 |E(G)|), adj[]
-    GCHK(gpu::dset(d_deg, 0, words * sizeof(uint32_t), cs.stream()));
-    GCHK(gpu::dset(d_fill, 0, words * sizeof(uint32_t), cs.stream()));
-    GCHK(gpu::dset(d_pred, 0, words * sizeof(uint32_t), cs.stream()));
-    GCHK(gpu::dset(d_cnt, 0, kColCntWords * sizeof(uint32_t), cs.stream()));
-    GPU_LAUNCH(cs.stream(), k_kc_init, cs.vert_grid(), 256, d_col, nn);
-    uint32_t *d_adj = nullptr;
-    int e = cs.symmetric_adjacency(P, d_deg, d_fill, d_off, d_tiles, ntiles, &d_adj, &ctr[3]);
+    const int e = cs.colour_run(P, order, seed, &st);
     if (e != PPCSR_OK) return e;
-    reads++;
-    // the order, pred[] and the first frontier
-    GPU_LAUNCH(cs.stream(), k_col_keys, cs.vert_grid(), 256, order, (unsigned long long)seed, (const uint32_t *)d_deg, nn, d_key);
-    GPU_LAUNCH(cs.stream(), k_col_pred, cs.pass_grid(), 256, tab, P, nn, (const unsigned long long *)d_key, d_pred);
-    uint32_t *cur = d_f0, *nxt = d_f1;
-    GPU_LAUNCH(cs.stream(), k_col_collect, grid_for(nn, 256), 256, (const uint32_t *)d_pred, nn, cur, d_cnt);
-    launches += 9;  // (k_kc_init, the five of stage 1, these three)
-    e = read_cnt(1);
-    if (e != PPCSR_OK) return e;
-    uint64_t done = 0;
-    for (uint32_t nfront = h_cnt[0]; nfront > 0; nfront = h_cnt[0]) {
-      if (rounds == nn) return fail(PPCSR_EHIP, "colouring: more rounds than the graph has vertices");
-      rounds++;
-      done += nfront;
-      ctr[1] = std::max<uint64_t>(ctr[1], nfront);
-      GCHK(gpu::dset(d_cnt, 0, 2 * sizeof(uint32_t), cs.stream()));
-      GPU_LAUNCH(cs.stream(), k_col_round, cs.list_grid(nfront), 256, (const unsigned long long *)d_off, (const uint32_t *)d_adj, (const uint32_t *)cur,
-                 nfront, d_col, d_pred, nxt, d_long, d_cnt);
-      launches++;
-      e = read_cnt(4);
-      if (e != PPCSR_OK) return e;
-      if (h_cnt[1]) {  // lists beyond one wave's reach: a workgroup each, appending to the same frontier
-        ctr[2] += h_cnt[1];
-        GPU_LAUNCH(cs.stream(), k_col_long, grid_for(h_cnt[1], 1, 1024), 256, (const unsigned long long *)d_off, (const uint32_t *)d_adj,
-                   (const uint32_t *)d_long, h_cnt[1], window, d_col, d_pred, nxt, d_cnt);
-        launches++;
-        e = read_cnt(4);
-        if (e != PPCSR_OK) return e;
-      }
-      std::swap(cur, nxt);
-    }
-    if (done != nn) return fail(PPCSR_EHIP, "colouring: the rounds ended with vertices left uncoloured");
-    ctr[4] = (uint64_t)h_cnt[3] + 1;
-    ctr[5] = h_cnt[2];
   }
   cs.stop();
-  if (colour && nn) GCHK(gpu::d2h(colour, d_col, (uint64_t)nn * sizeof(uint32_t), cs.stream()));
+  if (colour && nn) GCHK(gpu::d2h(colour, st.d_col, (uint64_t)nn * sizeof(uint32_t), cs.stream()));
   const int done = cs.done(device_ms);
   if (done != PPCSR_OK) return done;
-  if (ncolours) *ncolours = (uint32_t)ctr[4];
-  for (int i = 0; i < 8; i++) p_->colour_ctr[i] = ctr[i];
+  if (ncolours) *ncolours = (uint32_t)st.ctr[4];
+  for (int i = 0; i < 8; i++) p_->colour_ctr[i] = st.ctr[i];
   return PPCSR_OK;
 }
 int Engine::colouring_counters(uint64_t out[8]) {
   if (!out) return fail(PPCSR_EINVAL, "colouring counters: no output");
   for (int i = 0; i < 8; i++) out[i] = p_->colour_ctr[i];
+  return PPCSR_OK;
+}
+
+// Label-propagation communities (pma_community.h; the definition: include/ppcsr.h).  The colouring's stage first — adjacency and
+// colours stay on the device — then, for the weighted form, the second adjacency with the values; the counting sort of the
+// vertices by (colour, tier) and ONE read of the bucket offsets; then sweeps: per class up to three launches over host-known
+// ranges, per sweep one read of the striped counters.  The buffers the colouring's rounds are done with carry the labels
+// (d_f0), the class lists (d_f1) and the marks of the community count (d_long).  Every change raises the weight of the edges
+// whose ends agree, so the sweeps end; the bound on them (that weight plus one) is checked instead of trusted.
+int Engine::label_propagation_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, uint32_t order, uint64_t seed, uint32_t flags,
+                                   uint32_t max_sweeps, const uint32_t *init, uint32_t *labels, uint64_t *ncommunities, uint32_t *sweeps,
+                                   double *device_ms) {
+  const uint32_t nn = total_n;
+  // (all refused before the device is even selected)
+  if (order > kColOrderId) return fail(PPCSR_EINVAL, "label propagation: unknown vertex order");
+  if (flags & ~kLpWeighted) return fail(PPCSR_EINVAL, "label propagation: unknown flag bits");
+  if (init)
+    for (uint32_t v = 0; v < nn; v++)
+      if (init[v] >= nn) return fail(PPCSR_EINVAL, "label propagation: an initial label is not a vertex id");
+  const bool weighted = (flags & kLpWeighted) != 0;
+  ConsumerScope cs(this, PPCSR_ENOMEM);
+  const int rc = cs.open(parts, P, nn);
+  if (rc != PPCSR_OK) return rc;
+  ConsumerScope::ColourStage st;
+  cs.colour_alloc(&st);
+  ConsumerScope::Striped<unsigned long long, kLpStripeWords> cnt(cs, "d_lpcnt");
+  if (cs.rc != PPCSR_OK) return cs.rc;
+  unsigned long long *const d_stripes = cnt.stripes();
+  uint64_t ctr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t &nsweeps = ctr[0], &classes = ctr[1], &changes = ctr[2], &last = ctr[3], &launches = ctr[7];
+  cs.start();
+  if (nn) {
+    int e = cs.colour_run(P, order, seed, &st);
+    if (e != PPCSR_OK) return e;
+    launches += st.ctr[6];
+    const ConsumerPart *const tab = cs.table();  // (a launch's arguments are copies of plain pointers)
+    uint32_t *const d_lab = st.d_f0, *const d_list = st.d_f1, *const d_fill = st.d_fill;
+    const uint32_t *const d_col = st.d_col;
+    uint8_t *const d_mark = reinterpret_cast<uint8_t *>(st.d_long);
+    const unsigned long long *const d_off = st.d_off;
+    const uint32_t *const d_adj = st.d_adj;
+    const uint64_t entries = st.ctr[3];
+    unsigned long long *d_wadj = nullptr;
+    if (weighted) {
+      d_wadj = cs.alloc<unsigned long long>("d_wadj", std::max<uint64_t>(entries, 1));
+      if (cs.rc != PPCSR_OK) return cs.rc;
+      GCHK(gpu::dset(d_fill, 0, cs.words() * sizeof(uint32_t), cs.stream()));
+      GPU_LAUNCH(cs.stream(), k_lp_fill_weighted, cs.pass_grid(), 256, tab, P, nn, d_off, d_fill, d_wadj);
+      launches++;
+    }
+    // the class lists: buckets 3 * colour + tier, their offsets read once
+    const uint32_t buckets = 3u * (uint32_t)st.ctr[4];
+    uint32_t *d_hist = cs.alloc<uint32_t>("d_hist", 3ull * buckets + 1);  // hist[buckets], first[buckets + 1], cursor[buckets]
+    if (cs.rc != PPCSR_OK) return cs.rc;
+    uint32_t *const d_first = d_hist + buckets, *const d_cursor = d_first + buckets + 1;
+    GCHK(gpu::dset(d_hist, 0, (uint64_t)buckets * sizeof(uint32_t), cs.stream()));
+    GPU_LAUNCH(cs.stream(), k_lp_hist, cs.vert_grid(), 256, d_col, d_off, nn, d_hist);
+    GPU_LAUNCH(cs.stream(), k_lp_scan, 1, 64, (const uint32_t *)d_hist, buckets, d_first, d_cursor);
+    GPU_LAUNCH(cs.stream(), k_lp_class_fill, cs.vert_grid(), 256, d_col, d_off, nn, d_cursor, d_list);
+    launches += 3;
+    std::vector<uint32_t> first(buckets + 1, 0);
+    e = cs.read_back(first.data(), d_first, (uint64_t)(buckets + 1) * sizeof(uint32_t));
+    if (e != PPCSR_OK) return e;
+    for (uint32_t c = 0; 3 * c < buckets; c++) {
+      if (first[3 * c + 3] > first[3 * c]) classes++;
+      ctr[5] += first[3 * c + 3] - first[3 * c + 2];
+    }
+    // the labels
+    if (init)
+      GCHK(gpu::h2d(d_lab, init, (uint64_t)nn * sizeof(uint32_t), cs.stream()));
+    else
+      GPU_LAUNCH(cs.stream(), k_lp_identity, cs.vert_grid(), 256, d_lab, nn);
+    // the sweeps
+    const uint64_t heaviest = weighted ? 0xFFFFFFFFull : 1ull;
+    const uint64_t bound = entries / 2 > (~0ull - 1) / heaviest ? ~0ull : entries / 2 * heaviest + 1;  // (W(G) + 1, saturating)
+    const uint32_t slots = p_->lp_table_slots;
+    for (;;) {
+      if (nsweeps == bound) return fail(PPCSR_EHIP, "label propagation: more sweeps than the graph has weight");
+      nsweeps++;
+      GCHK(cnt.zero());
+      for (uint32_t b = 0; b < buckets; b++) {
+        const uint32_t count = first[b + 1] - first[b];
+        if (!count) continue;
+        const uint32_t *const part = d_list + first[b];
+        launches++;
+        // (the launches differ in the kernel alone: tier = b % 3, and the weighted form reads the 8-byte entries)
+#define LP_STEP(kernel, grid, ...)                                                                                      \
+  do {                                                                                                                   \
+    if (weighted)                                                                                                        \
+      GPU_LAUNCH(cs.stream(), kernel<true>, grid, 256, d_off, d_adj, (const unsigned long long *)d_wadj, part, count, __VA_ARGS__); \
+    else                                                                                                                 \
+      GPU_LAUNCH(cs.stream(), kernel<false>, grid, 256, d_off, d_adj, (const unsigned long long *)d_wadj, part, count, __VA_ARGS__); \
+  } while (0)
+        if (b % 3 == 0)
+          LP_STEP(k_lp_step_lanes, cs.list_grid(count), d_lab, d_stripes);
+        else if (b % 3 == 1)
+          LP_STEP(k_lp_step_wave, cs.list_grid(count), d_lab, d_stripes);
+        else
+          LP_STEP(k_lp_step_block, grid_for(count, 1, 1024), slots, d_lab, d_stripes);
+#undef LP_STEP
+      }
+      e = cnt.read();
+      if (e != PPCSR_OK) return e;
+      if (cnt.sum(kLpCntFault)) return fail(PPCSR_EHIP, "label propagation: a list overflowed its label table in every hash split");
+      last = cnt.sum(kLpCntChanges);
+      changes += last;
+      ctr[6] += cnt.sum(kLpCntPasses);
+      if (last == 0 || nsweeps == max_sweeps) break;
+    }
+    // the labels in use
+    GCHK(cnt.zero());
+    GCHK(gpu::dset(d_mark, 0, nn, cs.stream()));
+    GPU_LAUNCH(cs.stream(), k_lp_mark, cs.vert_grid(), 256, (const uint32_t *)d_lab, nn, d_mark);
+    GPU_LAUNCH(cs.stream(), k_lp_count_marks, cs.vert_grid(), 256, (const uint8_t *)d_mark, nn, d_stripes);
+    launches += 2;
+    e = cnt.read();
+    if (e != PPCSR_OK) return e;
+    ctr[4] = cnt.sum(kLpCntLabels);
+    cs.stop();
+    if (labels) GCHK(gpu::d2h(labels, d_lab, (uint64_t)nn * sizeof(uint32_t), cs.stream()));
+  } else {
+    cs.stop();
+  }
+  const int done = cs.done(device_ms);
+  if (done != PPCSR_OK) return done;
+  if (ncommunities) *ncommunities = ctr[4];
+  if (sweeps) *sweeps = (uint32_t)nsweeps;
+  for (int i = 0; i < 8; i++) p_->lp_ctr[i] = ctr[i];
+  return PPCSR_OK;
+}
+int Engine::community_counters(uint64_t out[8]) {
+  if (!out) return fail(PPCSR_EINVAL, "community counters: no output");
+  for (int i = 0; i < 8; i++) out[i] = p_->lp_ctr[i];
+  return PPCSR_OK;
+}
+
+// Modularity of any labels (pma_community.h): the labels go up, one streaming pass adds the weights to tot[label] and to the
+// striped counters, a vertex pass squares and sums tot[] into one 128-bit partial per workgroup; one read of the counters,
+// one of the partials.  q is formed here, in doubles: out[1] / out[0] - S / out[0]^2.
+int Engine::modularity_over(const ConsumerRef *parts, uint32_t P, uint32_t total_n, const uint32_t *labels, uint32_t flags, uint64_t out[4],
+                            double *q, double *device_ms) {
+  const uint32_t nn = total_n;
+  if (flags & ~kLpWeighted) return fail(PPCSR_EINVAL, "modularity: unknown flag bits");
+  if (!labels && nn) return fail(PPCSR_EINVAL, "modularity: no labels");
+  for (uint32_t v = 0; v < nn; v++)
+    if (labels[v] >= nn) return fail(PPCSR_EINVAL, "modularity: a label is not below the number of vertices");
+  ConsumerScope cs(this, PPCSR_ENOMEM);
+  const int rc = cs.open(parts, P, nn);
+  if (rc != PPCSR_OK) return rc;
+  const uint64_t words = cs.words();
+  const uint32_t grid = cs.vert_grid();
+  uint32_t *d_lab = cs.alloc<uint32_t>("d_lab", words);
+  unsigned long long *d_tot = cs.alloc<unsigned long long>("d_tot", words), *d_part = cs.alloc<unsigned long long>("d_part", 2ull * grid);
+  ConsumerScope::Striped<unsigned long long, kLpStripeWords> cnt(cs, "d_lpcnt");
+  if (cs.rc != PPCSR_OK) return cs.rc;
+  const ConsumerPart *const tab = cs.table();  // (a launch's arguments are copies of plain pointers)
+  unsigned long long *const d_stripes = cnt.stripes();
+  uint64_t res[4] = {0, 0, 0, 0};
+  cs.start();
+  if (nn) {
+    GCHK(gpu::h2d(d_lab, labels, (uint64_t)nn * sizeof(uint32_t), cs.stream()));
+    GCHK(gpu::dset(d_tot, 0, words * sizeof(unsigned long long), cs.stream()));
+    GCHK(cnt.zero());
+    if (flags & kLpWeighted)
+      GPU_LAUNCH(cs.stream(), k_lp_mod_pass<true>, cs.pass_grid(), 256, tab, P, nn, (const uint32_t *)d_lab, d_tot, d_stripes);
+    else
+      GPU_LAUNCH(cs.stream(), k_lp_mod_pass<false>, cs.pass_grid(), 256, tab, P, nn, (const uint32_t *)d_lab, d_tot, d_stripes);
+    GPU_LAUNCH(cs.stream(), k_lp_mod_squares, grid, 256, (const unsigned long long *)d_tot, nn, d_part);
+    int e = cnt.read();
+    if (e != PPCSR_OK) return e;
+    std::vector<unsigned long long> part(2ull * grid, 0);
+    e = cs.read_back(part.data(), d_part, part.size() * sizeof(unsigned long long));
+    if (e != PPCSR_OK) return e;
+    res[0] = 2 * cnt.sum(kLpCntWeight);
+    res[1] = 2 * cnt.sum(kLpCntInside);
+    for (uint32_t b = 0; b < grid; b++) {
+      res[2] += part[2ull * b];
+      res[3] += part[2ull * b + 1] + (res[2] < part[2ull * b] ? 1u : 0u);
+    }
+  }
+  cs.stop();
+  const int done = cs.done(device_ms);
+  if (done != PPCSR_OK) return done;
+  if (out)
+    for (int i = 0; i < 4; i++) out[i] = res[i];
+  if (q) {
+    const double m2 = (double)res[0], squares = (double)res[3] * 18446744073709551616.0 + (double)res[2];
+    *q = res[0] ? (double)res[1] / m2 - squares / m2 / m2 : 0.0;
+  }
   return PPCSR_OK;
 }
 

@@ -35,5 +35,6 @@
 #include "pma_query.h"
 #include "pma_sample.h"
 #include "pma_colour.h"
+#include "pma_community.h"
 #include "pma_msbfs.h"
 #include "pma_exchange.h"

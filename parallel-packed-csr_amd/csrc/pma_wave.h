@@ -186,5 +186,14 @@ inline void lds_or_u64(unsigned long long *p, unsigned long long v) { *p |= v; }
 #else
 PMA_DEV void lds_or_u64(unsigned long long *p, unsigned long long v) { (void)atomicOr(p, v); }
 #endif
+// the label tables of pma_community.h, in LDS: claim a 32-bit key word (ds_cmpst_rtn_b32: the old value back) and add to the
+// 64-bit score beside it, nothing back (ds_add_u64)
+#if defined(PPCSR_SIM)
+inline uint32_t lds_cas_u32(uint32_t *p, uint32_t expect, uint32_t v) { uint32_t o = *p; if (o == expect) *p = v; return o; }
+inline void lds_add_u64(unsigned long long *p, unsigned long long v) { *p += v; }
+#else
+PMA_DEV uint32_t lds_cas_u32(uint32_t *p, uint32_t expect, uint32_t v) { return atomicCAS(p, expect, v); }
+PMA_DEV void lds_add_u64(unsigned long long *p, unsigned long long v) { (void)atomicAdd(p, v); }
+#endif
 }  // namespace wv
 }  // namespace ppcsr
